@@ -11,7 +11,10 @@ fused kernel covers the whole batch in ONE launch).  Inputs are resident in HBM 
 ring of distinct noise frames (48 x 24.9 MB = 1.2 GB, far beyond the 256 MiB Infinity Cache) is cycled so no step
 re-reads cached input, and every frame is written to its own 132.7 MB output buffer.
 
-    python bench.py                       # N=1, finishes in a few minutes incl. the CPU baseline
+    python bench.py                       # N=1: set-up, settle, warm-up, the timed steps, the line
+    python bench.py --full                # ... and every side measurement (CPU baseline, copy / traffic-shape ceilings, per-frame and
+                                          #     host-sample paths, batches on lanes): a few minutes
+    python bench.py --dump-outputs DIR    # ... and the last timed step's render targets as DIR/*.npy (see dump_outputs)
     python bench.py --gpus 8 --steps 50 --warmup 5      # starts its own 8 ranks (one per GPU) under torch.distributed.run
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29500 \
         bench.py --gpus 8 --steps 50 --warmup 5         # the driver's form: the ranks exist already, nothing is spawned
@@ -118,6 +121,47 @@ def noise_frame_gpu(torch, wl, nbytes, pitch, gen):
         raise ValueError("workload format")
     assert buf.numel() == nbytes, (buf.numel(), nbytes)
     return buf.contiguous()
+
+
+DUMP_MAX_BYTES = 48 << 20       # what --dump-outputs writes at most, the pixel index included (the option's cap is 64 MB)
+
+
+def dump_outputs(out_dir, torch, targets, output_format, seed=0x4D50):
+    """--dump-outputs DIR: the render targets of the last timed step, i.e. what mpcvr_process_batch hands its caller, as
+    DIR/render_targets.npy (float32) of shape (frames, H, W, 4) — or, when that would exceed DUMP_MAX_BYTES,
+    (frames, P, 4) at the same P pixels of every frame, a seeded sample whose row-major pixel indices go to
+    DIR/render_targets_pixel_index.npy (float64).  The 4 channels are the target's own codes in memory order: B, G, R, A for
+    B8G8R8A8 (0..255), R, G, B, A for R10G10B10A2 (0..1023, alpha 0..3).  The inputs are the seeded noise ring, so the same
+    arguments give the same arrays on every run: two builds of the project compare output for output."""
+    import numpy as np
+    from videorenderer_amd import api
+    os.makedirs(out_dir, exist_ok=True)
+    h, w = targets[0].shape[:2]
+    npix = h * w
+    idx = None
+    if 16 * len(targets) * npix > DUMP_MAX_BYTES:       # 4 float32 codes per pixel and frame + one float64 index per pixel
+        per_frame = DUMP_MAX_BYTES // (16 * len(targets) + 8)
+        idx = np.sort(np.random.default_rng(seed).choice(npix, per_frame, replace=False))
+        idx_dev = torch.from_numpy(idx).to(targets[0].device)
+    frames = []
+    for t in targets:
+        if output_format == api.OUT_RGB10A2:
+            px = t.contiguous().view(torch.int32).reshape(npix)
+            px = px if idx is None else px[idx_dev]
+            px = torch.stack([px & 1023, (px >> 10) & 1023, (px >> 20) & 1023, (px >> 30) & 3], dim=-1)
+        else:
+            px = t.reshape(npix, 4)
+            px = px if idx is None else px[idx_dev]
+        frames.append(px.to(torch.float32).cpu().numpy())
+    out = np.stack(frames)
+    if idx is None:
+        out = out.reshape(len(targets), h, w, 4)
+    np.save(os.path.join(out_dir, "render_targets.npy"), out)
+    index_path = os.path.join(out_dir, "render_targets_pixel_index.npy")
+    if idx is not None:
+        np.save(index_path, idx.astype(np.float64))
+    elif os.path.exists(index_path):            # an earlier, sampled dump's index does not describe this one
+        os.remove(index_path)
 
 
 def _oracle_cdll(O, native=False):
@@ -309,13 +353,19 @@ def main():
     ap.add_argument("--flags", type=int, default=0, help="mpcvr_settings.flags (2 = pass-per-kernel path)")
     ap.add_argument("--settle", type=float, default=1.0,
                     help="seconds of untimed launches BEFORE the counted warm-up (clock ramp: a cold part reads ~5 %% low over a 40 ms run); stated in config")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-host-path", action="store_true", help="skip the PCIe-inclusive (host sample) measurement")
+    ap.add_argument("--full", action="store_true", help="also run the side measurements beside the headline (empirical copy / traffic-shape "
+                    "ceilings, host-sample and per-frame paths, batches on lanes, CPU baseline); a plain run times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the render targets of the last timed step to DIR/*.npy "
+                    "(float32 codes; a fixed, seeded pixel sample when the batch is larger than the cap)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-host-path", action="store_true", help="with --full: skip the PCIe-inclusive (host sample), per-frame and lanes measurements")
     ap.add_argument("--src", default=None, help="WxH: override the workload's source size (secondary rows, e.g. 1920x1080)")
     ap.add_argument("--scale", type=int, default=None, help="integer upscale factor override (the fused kernel covers 2)")
     ap.add_argument("--rendezvous-only", action="store_true", help="the N-rank flow without pixels (rendezvous, blob broadcast, reductions, the line's "
                     "distributed block): runs without a GPU; the CPU suite's check of `--gpus N` starting its own ranks")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # `--gpus N` from a plain shell starts its own N ranks (round 6: it used to warn and measure ONE GPU)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -431,9 +481,15 @@ def main():
           "fps": args.batch * args.steps / my_elapsed, "kernel_ms_per_launch": my_launch_ms, "path": path}
     ranks = vdist.gather_objects(me)
 
+    # the last timed step's render targets, before any side measurement below reuses them
+    if rank == 0 and args.dump_outputs:
+        k = ((args.warmup + args.steps - 1) * args.batch) % ring
+        dump_outputs(args.dump_outputs, torch, [dsts[(k + j) % ring] for j in range(args.batch)], wl.get("output_format", 0))
+
+    # everything below up to the line is a side measurement (--full): the headline needs only the timed steps above
     # empirical HBM ceiling beside the 8 TB/s vendor figure: a large device-to-device copy, read + write bytes
     copy_gbps = None
-    if rank == 0:
+    if rank == 0 and args.full:
         n_el = 1 << 30
         a_ = torch.empty(n_el, dtype=torch.uint8, device="cuda")
         b_ = torch.empty(n_el, dtype=torch.uint8, device="cuda")
@@ -451,7 +507,7 @@ def main():
     # it writes and flatters them): the library's own probe kernel — each 16-byte word of a sample read once, fanned out to `fan` words of
     # a target, no arithmetic — over the same ring of samples and targets as the timed steps
     shape_gbps, shape_fan = None, None
-    if rank == 0:
+    if rank == 0 and args.full:
         import ctypes as C
         Lp = api.load_library()
         src16 = nbytes // 16 * 16
@@ -479,7 +535,7 @@ def main():
     # launch (round 6: mpcvr_bandwidth_probe_up2x — strips of 120 source columns marching down a segment, two luma rows + a chroma row read and
     # four target rows written per step as 16-byte pieces, no arithmetic), plus the same stores alone and the same loads alone
     up2x_shape = None
-    if rank == 0 and wl["cformat"] == 2 and s == 2 and (dw, dh) == (2 * w, 2 * h):
+    if rank == 0 and args.full and wl["cformat"] == 2 and s == 2 and (dw, dh) == (2 * w, 2 * h):
         import ctypes as C
         Lp = api.load_library()
         nb = min(args.batch, 64)
@@ -512,7 +568,7 @@ def main():
     # PCIe-inclusive rate of the reference's own calling pattern (CopySample from host memory, then Process), frame by
     # frame through the 3-slot upload ring: reported beside `value`, never as `value` (inputs-resident is the metric)
     host_path = None
-    if rank == 0 and world == 1 and not args.no_host_path:
+    if rank == 0 and args.full and world == 1 and not args.no_host_path:
         nf = 96
         host_frame = srcs[0].cpu()
         pinned = host_frame.clone().pin_memory()
@@ -541,7 +597,7 @@ def main():
     # place) + mpcvr_process, one frame per call, on a context that owns its stream like a C / C++ host's — reported beside `value`, which
     # is the mpcvr_process_batch rate.  Two figures: frames dealt to the context's frame lanes (default) and strictly one after the other.
     per_frame = None
-    if rank == 0 and world == 1 and not args.no_host_path:
+    if rank == 0 and args.full and world == 1 and not args.no_host_path:
         import ctypes as C
         L = api.load_library()
         sp = [C.c_void_p(t.data_ptr()) for t in srcs]
@@ -602,7 +658,7 @@ def main():
     # the stream-ordered rate the roofline block's per-launch duration belongs to.  Two batches' worth of distinct render targets (consecutive
     # batches that share a target are kept in order, i.e. would not overlap).
     batch_lanes = None
-    if rank == 0 and world == 1 and not args.no_host_path:
+    if rank == 0 and args.full and world == 1 and not args.no_host_path:
         st3 = api.default_settings(iUpscaling=wl["iUpscaling"], iDownscaling=wl.get("iDownscaling", 2), flags=args.flags,
                                    output_format=wl.get("output_format", 0), bUseDither=wl.get("bUseDither", 1))
         vp3 = api.VideoProcessor(st3, device=dev, use_torch_stream=False)
@@ -683,7 +739,7 @@ def main():
             "config": {"workload": f"{args.workload}: {wl['desc']}", "frames_per_step_per_gpu": args.batch,
                        "input_ring_frames": ring, "path": path, "sharding": "frames by index, no data-path collective",
                        "fps_per_gpu": round(fps / world, 2), "algorithmic_bytes_per_frame": algo_bytes,
-                       "settle_s": args.settle, "settle_steps": settle_steps,
+                       "settle_s": args.settle, "settle_steps": settle_steps, "side_measurements": bool(args.full),
                        "distributed": dict(vdist.describe_backend(), collective="one broadcast of rank 0's parameter blob at set-up",
                                            per_rank_fps_min=round(min(r["fps"] for r in ranks), 2), per_rank_fps_max=round(max(r["fps"] for r in ranks), 2),
                                            devices=[{k: r[k] for k in ("rank", "device_index", "device", "pci_bus_id", "visible")} for r in ranks],
@@ -706,7 +762,7 @@ def main():
         if valu_issue:
             valu_issue["hbm_frac_at_full_issue"] = round(achieved / HBM_PEAK_GBS / valu_issue["frac"], 4)
             res["roofline"]["co_limit"] = valu_issue
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(wl, extfmt)
         if host_path:
             res["host_sample_path"] = host_path

@@ -22,6 +22,30 @@ def bits(x):
     return struct.unpack("<I", struct.pack("<f", x))[0]
 
 
+def csp_sweep(L, fn):
+    """The random procamp sweep of tests/test_oracle_pins.py::test_csp_matrix_matches_live_reference through `fn` of library `L`
+    (orc_csp_matrix of the oracle, ref_csp_matrix of the reference): {"space,levels,bits": sha256 of the fp32 matrix and constant
+    words of the group's 16 calls, in call order}."""
+    import hashlib
+    import numpy as np
+    rng = np.random.default_rng(7)
+    out = {}
+    for space in (0, 1, 2, 3, 4, 8):
+        for levels in (0, 1, 2):
+            for nbits in (8, 10, 16):
+                h = hashlib.sha256()
+                for _ in range(8):
+                    b, ct = rng.uniform(-100, 100) / 255, rng.uniform(0, 2)
+                    hue, s = rng.uniform(-np.pi, np.pi), rng.uniform(0, 2)
+                    for gray in (0, 1):
+                        m = (C.c_float * 9)()
+                        cc = (C.c_float * 3)()
+                        getattr(L, fn)(space, levels, nbits, b, ct, hue, s, gray, m, cc)
+                        h.update(np.array(m, dtype=np.float32).tobytes() + np.array(cc, dtype=np.float32).tobytes())
+                out[f"{space},{levels},{nbits}"] = h.hexdigest()
+    return out
+
+
 def main():
     O.build(ref=True)
     R = O.ref()
@@ -49,6 +73,11 @@ def main():
     with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "csputils_ref.json"), "w") as f:
         json.dump(out, f)
     print(f"wrote {len(cases)} csp cases")
+    sweep = dict(source="Source/csputils.cpp of the reference via oracle/_ref (real reference code): csp_sweep(R, 'ref_csp_matrix')",
+                 sha256=csp_sweep(R, "ref_csp_matrix"))
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "csputils_sweep_ref.json"), "w") as f:
+        json.dump(sweep, f, indent=0)
+    print(f"wrote {len(sweep['sha256'])} csp sweep groups")
 
 
 if __name__ == "__main__":

@@ -72,7 +72,9 @@ def test_bench_gpus_n_spawns_n_ranks_by_itself():
     used to warn and measure one GPU).  --rendezvous-only is that flow without pixels, so it runs here: rendezvous over gloo, the blob
     broadcast, MAX over ranks, every rank's self-description in the line."""
     import json
-    out = _bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--rendezvous-only"])
+    # gloo is what a box without a GPU picks by itself; named here so that a box with one GPU runs the same flow (its default, nccl,
+    # refuses two ranks on one device)
+    out = _bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--rendezvous-only"], dict(MPCVR_DIST_BACKEND="gloo"))
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout                     # ONE line, from rank 0

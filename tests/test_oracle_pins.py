@@ -47,20 +47,17 @@ def test_csp_matrix_matches_reference_fixtures(oracle):
 
 
 def test_csp_matrix_matches_live_reference(oracle):
+    """A random procamp sweep (864 calls): the oracle's matrices are the reference code's, bit for bit — against its answers recorded in
+    tests/golden/csputils_sweep_ref.json, and against the reference code itself where oracle/_ref is built."""
+    from tests.golden.make_golden import csp_sweep
+    with open(os.path.join(HERE, "golden", "csputils_sweep_ref.json")) as f:
+        rec = json.load(f)["sha256"]
+    assert len(rec) == 54
+    got = csp_sweep(oracle.lib(), "orc_csp_matrix")
+    assert [k for k in rec if got.get(k) != rec[k]] == []
     R = oracle.ref()
-    if R is None:
-        pytest.skip("oracle/_ref not built (no /root/reference here)")
-    rng = np.random.default_rng(7)
-    for space in (0, 1, 2, 3, 4, 8):
-        for levels in (0, 1, 2):
-            for bits in (8, 10, 16):
-                for _ in range(8):
-                    b, ct = rng.uniform(-100, 100) / 255, rng.uniform(0, 2)
-                    h, s = rng.uniform(-np.pi, np.pi), rng.uniform(0, 2)
-                    for gray in (0, 1):
-                        a = csp(oracle.lib(), "orc_csp_matrix", space, levels, bits, b, ct, h, s, gray)
-                        r = csp(R, "ref_csp_matrix", space, levels, bits, b, ct, h, s, gray)
-                        assert np.array_equal(a[0], r[0]) and np.array_equal(a[1], r[1])
+    if R is not None:
+        assert csp_sweep(R, "ref_csp_matrix") == rec
 
 
 def test_known_answer_matrices(oracle):
@@ -205,20 +202,23 @@ def test_pq_hlg_grey_pins(oracle):
 
 
 def test_hlsl_constants_against_reference_text(oracle):
+    """The PQ / HLG constants of the reference's shader text drive the oracle's transfer functions.  They are recorded in
+    tests/golden/hlsl_constants_ref.json; where the reference is mounted the recording is checked against the text itself."""
+    rec = json.load(open(os.path.join(HERE, "golden", "hlsl_constants_ref.json")))
+    consts, b67 = rec["st2084"], rec["hlg"]
     base = "/root/reference/Shaders/convert"
-    if not os.path.isdir(base):
-        pytest.skip("reference not mounted")
-    src = open(os.path.join(base, "st2084.hlsl")).read()
-    consts = {}
-    for name, expr in re.findall(r"static const float (ST2084_\w+)\s*=\s*([^;]+);", src):
-        consts[name] = eval(expr.replace("f", ""))
+    if os.path.isdir(base):
+        src = open(os.path.join(base, "st2084.hlsl")).read()
+        live = {name: eval(expr.replace("f", "")) for name, expr in re.findall(r"static const float (ST2084_\w+)\s*=\s*([^;]+);", src)}
+        assert live == consts
+        hl = open(os.path.join(base, "hlg.hlsl")).read()
+        assert {"B67_" + k: float(re.search(r"B67_%s = ([0-9.]+)" % k, hl).group(1)) for k in "abc"} == b67
     x = np.float64(0.6)
     p = x ** (1.0 / consts["ST2084_m2"])
     p = max(p - consts["ST2084_c1"], 0) / (consts["ST2084_c2"] - consts["ST2084_c3"] * p)
     ref = p ** (1.0 / consts["ST2084_m1"]) * 80.0
     assert abs(oracle.lib().orc_st2084_to_linear(0.6, 80.0) - ref) < 1e-4 * ref
-    hl = open(os.path.join(base, "hlg.hlsl")).read()
-    a, b, c = (float(re.search(r"B67_%s = ([0-9.]+)" % k, hl).group(1)) for k in "abc")
+    a, b, c = (b67["B67_" + k] for k in "abc")
     v = (C.c_float * 3)(0.8, 0.8, 0.8)
     oracle.lib().orc_hlg_to_linear(v)
     lin = np.exp((0.8 - c) / a) + b

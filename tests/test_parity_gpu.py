@@ -3065,6 +3065,56 @@ def test_bench_through_rccl_in_a_world_of_one(mpcvr, torch_cuda):
     assert r["n_gpus"] == 1 and r["value"] > 0 and r["config"]["path"] == "fused_up2x"
 
 
+def _bench_line(args, timeout=600):
+    import json
+    root = os.path.dirname(HERE)
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + args, capture_output=True, text=True, timeout=timeout, cwd=root)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout
+    return json.loads(lines[0])
+
+
+def test_bench_dump_outputs_is_the_last_step(mpcvr, torch_cuda, tmp_path):
+    """bench.py --dump-outputs: the render targets of the last timed step as float32 codes, the same arrays from two runs with the same
+    arguments, and the very bytes mpcvr_process_batch gives for those ring frames; a plain run does none of --full's side measurements."""
+    from bench import WORKLOADS, noise_frame_gpu
+    from videorenderer_amd import api
+    torch = torch_cuda
+    small = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--settle", "0", "--batch", "2", "--ring", "3", "--src", "256x144"]
+    r = _bench_line(small + ["--dump-outputs", str(tmp_path / "a")])
+    _bench_line(small + ["--dump-outputs", str(tmp_path / "b")])
+    assert r["steps"] == 3 and r["ms_per_step"] > 0 and r["config"]["side_measurements"] is False
+    assert "cpu_baseline" not in r and "process_per_frame" not in r and r["roofline"]["empirical_copy_peak_GBps"] is None
+    a = np.load(tmp_path / "a" / "render_targets.npy")
+    assert a.dtype == np.float32 and a.shape == (2, 288, 512, 4)
+    assert np.array_equal(a, np.load(tmp_path / "b" / "render_targets.npy"))
+    assert not (tmp_path / "a" / "render_targets_pixel_index.npy").exists()
+    # the last step is step 1 + 3 - 1 = 3: ring offset 3 * 2 % 3 = 0, i.e. the ring's frames 0 and 1 (bench.py's seeded noise)
+    wl = dict(WORKLOADS["c3hdr"], w=256, h=144)
+    vp = api.VideoProcessor(api.default_settings(iUpscaling=wl["iUpscaling"], iDownscaling=2, flags=0, output_format=0, bUseDither=1), device=0)
+    vp.InitMediaType(wl["cformat"], 256, 144, extfmt=api.make_extfmt(**wl["ext"]))
+    vp.SetWindowRect((0, 0, 512, 288))
+    vp.SetVideoRect((0, 0, 512, 288))
+    nbytes, pitch = vp.GetFrameBytes()
+    gen = torch.Generator(device="cuda")
+    gen.manual_seed(0x4D50)
+    srcs = [noise_frame_gpu(torch, wl, nbytes, pitch, gen) for _ in range(2)]
+    dsts = [torch.zeros((288, 512, 4), dtype=torch.uint8, device="cuda") for _ in range(2)]
+    vp.ProcessBatch(vp.PrepareBatch(srcs, dsts), None, 512 * 4)
+    vp.Synchronize()
+    vp.close()
+    assert np.array_equal(a, np.stack([d.cpu().numpy() for d in dsts]).astype(np.float32))
+    # a full-size batch is a seeded sample at the same pixels of every frame, under the 64 MB cap
+    big = ["--gpus", "1", "--steps", "1", "--warmup", "0", "--settle", "0", "--batch", "2", "--ring", "2"]
+    _bench_line(big + ["--dump-outputs", str(tmp_path / "c")])
+    s = np.load(tmp_path / "c" / "render_targets.npy")
+    idx = np.load(tmp_path / "c" / "render_targets_pixel_index.npy")
+    assert s.dtype == np.float32 and idx.dtype == np.float64 and s.shape == (2, idx.size, 4)
+    assert np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < 7680 * 4320
+    assert sum(os.path.getsize(tmp_path / "c" / f) for f in os.listdir(tmp_path / "c")) <= 64e6
+
+
 def test_bandwidth_probe_moves_what_it_says(mpcvr, torch_cuda):
     """mpcvr_bandwidth_probe (csrc/vp_probe.hip, bench.py's traffic-shaped ceiling): every 16-byte word of the source read once, `fan` words written."""
     import ctypes as C
