@@ -82,13 +82,6 @@ CHipVideoProcessor::~CHipVideoProcessor()
         if (d.pinned) (void)hipHostFree(d.pinned);
         if (d.done) (void)hipEventDestroy(d.done);
     }
-    for (int i = 1; i < kLanes; i++) {
-        Lane &l = m_lanes[i];
-        l.conv.Release(); l.mid.Release(); l.post.Release();
-        if (l.done) (void)hipEventDestroy(l.done);
-        if (l.stream) (void)hipStreamDestroy(l.stream);
-    }
-    if (m_fork) (void)hipEventDestroy(m_fork);
     if (m_evStreamMark) (void)hipEventDestroy(m_evStreamMark);
     for (FrameLane &fl : m_flanes) {
         if (fl.stream) { (void)hipStreamSynchronize(fl.stream); (void)hipStreamDestroy(fl.stream); }
@@ -255,39 +248,7 @@ CHipVideoProcessor::FrameLane *CHipVideoProcessor::PickFrameLane(const void *rt)
     return pick;
 }
 
-// ---- whole batches on the lanes (see FrameLane) ----
-// The same rule as for single frames — nothing a batch touches may be shared with the batch beside it — checked on the route the batch will
-// take: the exact-2x kernel, the strip / periodic kernel reading the samples themselves, the same-size block convert; default tier only.
-bool CHipVideoProcessor::BatchLanesUsable(int n, const void *const *srcs, void *const *dsts, int rtPitch)
-{
-    static const bool off = [] { const char *e = std::getenv("MPCVR_NO_BATCH_LANES"); return e && *e && *e != '0'; }();
-    if (off || !m_ownStream || n < 2 || !m_srcParams || m_doviValid || m_dvFrames) return false;
-    if (m_cfg.flags & (MPCVR_FLAG_NO_FRAME_LANES | MPCVR_FLAG_NO_FUSED | MPCVR_FLAG_NO_FAST_CONVERT | MPCVR_FLAG_NO_STRIP)) return false;
-    if (m_srcParams->cformat == MPCVR_CF_V210 || m_srcParams->layout == LAY_RGB) return false;
-    if (m_plan.errdiff || m_plan.hdr_tonemap || rtPitch < m_windowRect.Width() * 4) return false;
-    bool aligned = true;
-    for (int i = 0; i < n; i++) {
-        if (!srcs[i] || !dsts[i] || ((uintptr_t)srcs[i] & 3) != 0) return false;
-        if (((uintptr_t)dsts[i] & 15) != 0) aligned = false;
-    }
-    // Two launches in flight were measured to pay on every such route (same box, bench.py process_batch_on_lanes against `value`, a quarter of
-    // a second of batches each; profiles/r06/bench_batch_lanes_all_routes_call32.txt, bench_batch_lanes_call27.txt): same-size block convert
-    // +11-16 %, exact-2x kernel +2-5 % (4K -> 8K, four rounds of waves per batch) to +15 % (1080p -> 4K, one round), strip / periodic kernel
-    // +11-29 % (1080p -> 1440p 99.8 k -> 116.4 k frames/s, 720p -> 1080p 190 k -> 246 k), fused Jinc2m +4 %.  (An earlier table that had
-    // the strip kernels LOSE was a wall clock around 30 launches of 0.3 ms: it measured the closing synchronize.)
-    if (m_plan.fused_up2x) return true;
-    if (m_strip) {
-        FusedStripParams sp{};
-        return FillStripParams((const uint8_t *)srcs[0], dsts[0], rtPitch, MakeStore(dsts[0], rtPitch, m_plan.swap_fmt, true), &sp) && !sp.surface_mode;
-    }
-    if (m_plan.direct_convert) {
-        FusedParams conv{}, direct{};
-        m_batchRepacked = false; m_batchSrc16 = false;           // (BatchPlan reads them; ProcessBatchRoutesOn sets them again)
-        return BatchPlan((const uint8_t *)srcs[0], dsts[0], rtPitch, aligned, &conv, &direct);
-    }
-    return false;
-}
-
+// ---- whole batches on the lanes (see FrameLane; which batches may take them: ProcessBatchRoutes) ----
 // the lane of the batch about to be queued (the two take turns), ordered behind everything still in flight on OTHER lanes that writes one
 // of its render targets: single frames (their ring entries) and batches
 CHipVideoProcessor::FrameLane *CHipVideoProcessor::PickBatchLane(int n, void *const *dsts)
@@ -935,7 +896,7 @@ HRESULT CHipVideoProcessor::UpdatePlan()
         m_period = m_stripSurf && FusedPeriodTakes(sp);
     }
     m_planDirty = false;
-    UseLane(0);
+    UseContextResources();
     if (LogLevel() >= 2)
         std::fprintf(stderr, "mpcvr[%p]: plan %s (%dx%d -> %dx%d in %dx%d)\n", (void *)this, GetPathInfo().c_str(), m_srcRectWidth, m_srcRectHeight,
                      m_videoRect.Width(), m_videoRect.Height(), m_windowRect.Width(), m_windowRect.Height());
@@ -963,26 +924,9 @@ HRESULT CHipVideoProcessor::UploadJincPhases(const DrawCoords &dc, DevBuffer &bu
     return MPCVR_S_OK;
 }
 
-void CHipVideoProcessor::UseLane(int lane)
+void CHipVideoProcessor::UseContextResources()
 {
-    if (lane == 0) { m_run = m_stream; m_runConv = m_TexConvertOutput.ptr; m_runMid = m_TexResize.ptr; m_runPost = m_TexPost.ptr; return; }
-    Lane &l = m_lanes[lane];
-    m_run = l.stream; m_runConv = l.conv.ptr; m_runMid = l.mid.ptr; m_runPost = l.post.ptr;
-}
-
-HRESULT CHipVideoProcessor::PrepareLanes(int lanes)
-{
-    HRESULT hr;
-    if (!m_fork && (hr = CheckHip(hipEventCreateWithFlags(&m_fork, hipEventDisableTiming), "fork event"))) return hr;
-    for (int i = 1; i < lanes; i++) {
-        Lane &l = m_lanes[i];
-        if (!l.stream && (hr = CheckHip(hipStreamCreateWithFlags(&l.stream, hipStreamNonBlocking), "lane stream"))) return hr;
-        if (!l.done && (hr = CheckHip(hipEventCreateWithFlags(&l.done, hipEventDisableTiming), "lane event"))) return hr;
-        if (m_convBytes && (hr = CheckHip(l.conv.CheckCreate(m_convBytes), "lane convert output"))) return hr;
-        if (m_midBytes && (hr = CheckHip(l.mid.CheckCreate(m_midBytes), "lane resize texture"))) return hr;
-        if (m_postBytes && (hr = CheckHip(l.post.CheckCreate(m_postBytes), "lane post-scale texture"))) return hr;
-    }
-    return MPCVR_S_OK;
+    m_run = m_stream; m_runConv = m_TexConvertOutput.ptr; m_runMid = m_TexResize.ptr; m_runPost = m_TexPost.ptr;
 }
 
 // m_PSConvColorData.bEnable — DX11VideoProcessor.cpp:849-853: interleaved RGB skips the convert draw unless brightness
@@ -1352,7 +1296,7 @@ HRESULT CHipVideoProcessor::Process(void *pRenderTarget, int rtPitch, const CRec
     if (dstRect && !dstRect->IsRectNull()) { if ((hr = SetVideoRect(*dstRect))) return hr; }
     if (rtPitch < m_windowRect.Width() * 4) return Fail(MPCVR_E_INVALIDARG, "render-target pitch smaller than a row");
     if (m_planDirty && (hr = UpdatePlan())) return hr;
-    UseLane(0);
+    UseContextResources();
     FrameLane *fl = (m_noLanesOnce || !FrameLanesUsable()) ? nullptr : PickFrameLane(pRenderTarget);
     m_inflight = fl ? FrameLaneCount() : 1;           // the kernels size their segments for that many frames side by side
     if (fl) {
@@ -1386,7 +1330,7 @@ HRESULT CHipVideoProcessor::Process(void *pRenderTarget, int rtPitch, const CRec
     MarkConsumed();
     if (fl) NoteLaneFrame(fl, pRenderTarget);
     m_inflight = 1;
-    UseLane(0);
+    UseContextResources();
     m_timed = true;
     return hr;
 }
@@ -1402,269 +1346,228 @@ HRESULT CHipVideoProcessor::ProcessBatch(int n, const void *const *srcs, void *c
     return hr;
 }
 
+// One batch: validated, classified once (ClassifyBatch), then run on one of two lanes beside the batch before it when its route shares nothing
+// with it (FrameLane); everything else — and every batch of a context on a caller's stream — in stream order on the context stream
 HRESULT CHipVideoProcessor::ProcessBatchRoutes(int n, const void *const *srcs, void *const *dsts, int rtPitch)
 {
-    // a batch that is one launch with nothing shared runs on one of two lanes, beside the batch before it (FrameLane); everything else —
-    // and every batch of a context on a caller's stream — in stream order on the context stream
-    FrameLane *bl = nullptr;
-    if (m_bInit && m_srcParams && n > 1 && srcs && dsts && !m_keepStart) {
-        (void)hipSetDevice(m_device);
-        HRESULT hr;
-        if (m_planDirty && (hr = UpdatePlan())) return hr;
-        if (BatchLanesUsable(n, srcs, dsts, rtPitch)) bl = PickBatchLane(n, dsts);
-    }
-    m_lastBatchLane = bl ? (int)(bl - m_flanes) : -1;
-    if (!bl) return ProcessBatchRoutesOn(n, srcs, dsts, rtPitch);
-    LaneWaitsForStream(bl);                  // behind whatever the context stream was given since the lane last looked
-    hipStream_t const ctx = m_stream;
-    m_stream = bl->stream; m_batchOnLane = true;
-    UseLane(0);
-    const HRESULT hr = ProcessBatchRoutesOn(n, srcs, dsts, rtPitch);
-    m_stream = ctx; m_batchOnLane = false;
-    UseLane(0);
-    NoteLaneBatch(bl, n, dsts);
-    return hr;
-}
-
-HRESULT CHipVideoProcessor::ProcessBatchRoutesOn(int n, const void *const *srcs, void *const *dsts, int rtPitch)
-{
+    m_lastBatchLane = -1;
     if (!m_bInit || !m_srcParams) return Fail(MPCVR_E_NOT_VALID_STATE, "InitMediaType has not been called");
     if (n <= 0 || !srcs || !dsts) return Fail(MPCVR_E_INVALIDARG, "empty batch");
     if (rtPitch < m_windowRect.Width() * 4) return Fail(MPCVR_E_INVALIDARG, "render-target pitch smaller than a row");
     (void)hipSetDevice(m_device);
     HRESULT hr;
-    if (!m_keepStart) m_startRecorded = false;
     if (m_planDirty && (hr = UpdatePlan())) return hr;
-    if (!m_batchOnLane) {
+    for (int i = 0; i < n; i++)
+        if (!srcs[i] || !dsts[i]) return Fail(MPCVR_E_POINTER, "null frame in batch");
+    BatchRoutePlan rp = ClassifyBatch(n, srcs, dsts, rtPitch);
+    // The same rule as for single frames — nothing a batch touches may be shared with the batch beside it — read off the route the batch takes:
+    // the exact-2x kernel, the strip / periodic kernel reading the samples themselves, the same-size block convert (no intermediate surface; a
+    // repacked v210 batch reads the shared m_batchTex); default tier only.  Two launches in flight were measured to pay on every such route (same
+    // box, bench.py process_batch_on_lanes against `value`, a quarter of a second of batches each; profiles/r06/bench_batch_lanes_all_routes_call32.txt,
+    // bench_batch_lanes_call27.txt): same-size block convert +11-16 %, exact-2x kernel +2-5 % (4K -> 8K, four rounds of waves per batch) to +15 %
+    // (1080p -> 4K, one round), strip / periodic kernel +11-29 % (1080p -> 1440p 99.8 k -> 116.4 k frames/s, 720p -> 1080p 190 k -> 246 k), fused
+    // Jinc2m +4 %.  (An earlier table that had the strip kernels LOSE was a wall clock around 30 launches of 0.3 ms: it measured the closing synchronize.)
+    static const bool lanesOff = [] { const char *e = std::getenv("MPCVR_NO_BATCH_LANES"); return e && *e && *e != '0'; }();
+    const bool laneRoute = rp.route == BatchRoute::FusedUp2x || rp.route == BatchRoute::Strip || rp.route == BatchRoute::DirectConvert;
+    const bool onLane = laneRoute && !rp.repackSlot && !lanesOff && m_ownStream && n >= 2 && !m_doviValid && !m_dvFrames && !m_plan.errdiff && !m_plan.hdr_tonemap &&
+                        !(m_cfg.flags & (MPCVR_FLAG_NO_FRAME_LANES | MPCVR_FLAG_NO_FUSED | MPCVR_FLAG_NO_FAST_CONVERT | MPCVR_FLAG_NO_STRIP));
+    FrameLane *const bl = onLane ? PickBatchLane(n, dsts) : nullptr;
+    hipStream_t const ctx = m_stream;
+    if (bl) {
+        m_lastBatchLane = (int)(bl - m_flanes);
+        LaneWaitsForStream(bl);              // behind whatever the context stream was given since the lane last looked
+        m_stream = bl->stream;
+    } else {
         (void)JoinFrameLanes(false);         // a batch runs on the context stream, behind every single frame still in flight
         NoteStreamWork();                    // ... and single frames queued after it run behind the batch (LaneWaitsForStream)
     }
-    for (int i = 0; i < n; i++)
-        if (!srcs[i] || !dsts[i]) return Fail(MPCVR_E_POINTER, "null frame in batch");
+    UseContextResources();
+    hr = RunBatchRoute(rp, n, srcs, dsts, rtPitch);
+    m_stream = ctx;
+    UseContextResources();
+    if (bl) NoteLaneBatch(bl, n, dsts);
+    return hr;
+}
+
+// The route of a batch, from the plan and the frames' pointers alone: nothing is launched, allocated or written here.  The pointers of
+// buffers RunBatchRoute may still (re)allocate are left null in the parameters (their checks do not read them).
+CHipVideoProcessor::BatchRoutePlan CHipVideoProcessor::ClassifyBatch(int n, const void *const *srcs, void *const *dsts, int rtPitch) const
+{
+    BatchRoutePlan rp;
+    const bool v210 = m_srcParams->cformat == MPCVR_CF_V210, rgb = m_srcParams->layout == LAY_RGB;
+    const bool fast = !(m_cfg.flags & (MPCVR_FLAG_NO_FUSED | MPCVR_FLAG_NO_FAST_CONVERT)), fastStrip = fast && !(m_cfg.flags & MPCVR_FLAG_NO_STRIP);
     // v210 samples are repacked into m_TexSrcVideo's layout first (CopyFrameV210, Helper.cpp:709-748): a batch gets one repack launch
-    // per 32 frames into the slots of a batch texture, and the whole-batch launches below read the slots as if they were the samples
-    std::vector<const void *> slots;
-    m_batchRepacked = false;
-    if (m_srcParams->cformat == MPCVR_CF_V210 && n > 1 && !(m_cfg.flags & (MPCVR_FLAG_NO_FUSED | MPCVR_FLAG_NO_FAST_CONVERT))) {
-        const int tp = TexPitch();
-        const size_t texBytes = ((size_t)tp * m_srcHeight + 255) & ~(size_t)255;
-        if (texBytes * (size_t)n <= ((size_t)1 << 30)) {
-            if ((hr = CheckHip(m_batchTex.CheckCreate(texBytes * n), "batch source texture"))) return hr;
-            slots.resize(n);
-            if (!m_startRecorded) (void)hipEventRecord(m_evStart, m_stream);      // the repack is part of the batch's process time, as on the other branches
-            m_startRecorded = true;
-            if ((hr = CheckHip(LaunchRepackV210(nullptr, m_srcPitch, (uint8_t *)m_batchTex.ptr, tp, m_srcHeight, m_stream, srcs, n, texBytes), "k_repack_v210"))) return hr;
-            m_batchTexZeroed = false;                       // (the RGB batches' zeroed remainder columns are gone)
-            for (int i = 0; i < n; i++) slots[i] = (uint8_t *)m_batchTex.ptr + (size_t)i * texBytes;
-            srcs = slots.data();
-            m_batchRepacked = true;
-        }
-    }
-    bool aligned = true, src4 = true;
-    m_batchSrc16 = true;
+    // per 32 frames into the slots of a batch texture, and the launches read the slots as if they were the samples
+    const size_t slot = ((size_t)TexPitch() * m_srcHeight + 255) & ~(size_t)255;
+    if (v210 && n > 1 && fast && slot * (size_t)n <= ((size_t)1 << 30)) rp.repackSlot = slot;
     for (int i = 0; i < n; i++) {
-        if (((uintptr_t)srcs[i] & 15) != 0) m_batchSrc16 = false;
-        if (((uintptr_t)srcs[i] & 3) != 0) src4 = false;
-        if (((uintptr_t)dsts[i] & 15) != 0) aligned = false;
+        if (!rp.repackSlot && ((uintptr_t)srcs[i] & 15) != 0) rp.src16 = false;
+        if (!rp.repackSlot && ((uintptr_t)srcs[i] & 3) != 0) rp.src4 = false;
+        if (((uintptr_t)dsts[i] & 15) != 0) rp.aligned = false;
+        if (((uintptr_t)dsts[i] & 7) != 0) rp.aligned8 = false;
     }
-    // samples that are repacked into m_TexSrcVideo first (v210, interleaved RGB) cannot be read in place by a whole-batch launch:
-    // they take the frame-by-frame branch below like samples that do not start on a dword (v210 became a fused-2x / strip
-    // candidate when packed 4:2:2 joined the block convert)
-    if ((m_srcParams->cformat == MPCVR_CF_V210 && !m_batchRepacked) || m_srcParams->layout == LAY_RGB) src4 = false;
-    // pass-per-kernel path, whole batch per launch: possible when every stage has a kernel with a frame dimension
+    // samples that are repacked into m_TexSrcVideo one by one (v210 past the batch texture, interleaved RGB) cannot be read in place by a
+    // whole-batch launch: they go frame by frame like samples that do not start on a dword
+    if ((v210 && !rp.repackSlot) || rgb) rp.src4 = false;
+    // (the launches take every sample from the frame table: the planners see the first one's alignment — slot 0 of m_batchTex when repacked)
+    const uint8_t *const sample0 = rp.repackSlot ? nullptr : (const uint8_t *)srcs[0];
+    const StoreParams target = MakeStore(dsts[0], rtPitch, m_plan.swap_fmt, true);
     // the arbitrary-ratio fused kernel takes the whole batch in one launch, like the 2x kernel
-    FusedStripParams strip_sp{};
-    const bool strip = m_strip && !m_plan.fused_up2x && !m_plan.hdr_tonemap && src4 && !m_dvFrames &&
-                       FillStripParams((const uint8_t *)srcs[0], dsts[0], rtPitch, MakeStore(dsts[0], rtPitch, m_plan.swap_fmt, true), &strip_sp);
-    bool batchable = false;
-    if (!m_plan.fused_up2x && !strip && n > 1 && src4 && !(m_cfg.flags & (MPCVR_FLAG_NO_FUSED | MPCVR_FLAG_NO_FAST_CONVERT))) {
-        FusedParams a{}, b{};
-        batchable = BatchPlan((const uint8_t *)srcs[0], dsts[0], rtPitch, aligned, &a, &b);
-        // one RPU per frame (ProcessBatchDovi): the block convert's Dolby Vision variants index the run's tables by the frame; the HDR10
-        // tone-mapping step takes its level-1 constants by value, so such a run goes frame by frame
-        if (m_dvFrames && (!m_dvTabReady || m_plan.hdr_tonemap)) batchable = false;
-        if (batchable && m_dvFrames) { m_dvTabDev = m_dvTabReady; m_dvCmDev = m_dvCmReady; }
+    FusedStripParams sp{};
+    const bool strip = m_strip && !m_plan.fused_up2x && !m_plan.hdr_tonemap && rp.src4 && !m_dvFrames && FillStripParams(sample0, dsts[0], rtPitch, target, &sp);
+    // pass-per-kernel path, whole batch per launch: possible when every stage has a kernel with a frame dimension.  One RPU per frame
+    // (ProcessBatchDovi): the block convert's Dolby Vision variants index the run's tables by the frame; the HDR10 tone-mapping step takes
+    // its level-1 constants by value, so such a run goes frame by frame
+    const bool batchable = !m_plan.fused_up2x && !strip && n > 1 && rp.src4 && fast && !(m_dvFrames && (!m_dvTabReady || m_plan.hdr_tonemap)) &&
+                           BatchPlan(sample0, dsts[0], rtPitch, rp.aligned, rp.repackSlot != 0, rp.src16, &rp.conv, &rp.direct);
+    auto take = [&rp](BatchRoute r) { rp.route = r; return rp; };
+    if (batchable && m_plan.direct_convert) return take(BatchRoute::DirectConvert);
+    if (rgb && !m_plan.convert && m_stripSurf && m_plan.two_pass && !m_plan.hdr_tonemap && n > 1 && fastStrip &&
+        FillStripSurfParams(Surface{nullptr, TexPitch(), m_srcWidth, m_srcHeight, RgbTexFmt(*m_srcParams)}, target, &sp)) {
+        rp.strip = sp;
+        return take(BatchRoute::RgbSurfaceStrip);
     }
-    if (batchable && m_plan.direct_convert && n <= kHostTableMax) {
-        // same-size frames: one convert launch with the frame table in its kernel arguments (32 frames for the block convert, 128 where the
-        // streaming kernel takes the launch — it answers hipErrorInvalidValue otherwise and the table is uploaded below)
-        FusedParams conv{}, direct{};
-        if (!BatchPlan((const uint8_t *)srcs[0], dsts[0], rtPitch, aligned, &conv, &direct)) return Fail(MPCVR_E_UNEXPECTED, "batch plan changed");
-        FusedFrame tab[kHostTableMax];
-        for (int i = 0; i < n; i++) tab[i] = FusedFrame{(const uint8_t *)srcs[i], dsts[i]};
-        if (!m_startRecorded) { (void)hipEventRecord(m_evStart, m_stream); m_startRecorded = true; }
-        const hipError_t e = LaunchConvertBlocks(direct, nullptr, FusedFrame{nullptr, nullptr}, n, m_stream, 0, tab);
-        if (e != hipErrorInvalidValue || n <= 32) {
-            hr = CheckHip(e, "k_convert_blocks");
-            (void)hipEventRecord(m_evStop, m_stream);
-            m_timed = true;
-            return hr;
+    if (m_plan.hdr_tonemap && m_strip && !m_plan.fused_up2x && rp.src4 && n > 1 && fastStrip) {
+        const int postPitch = (int)(m_videoRect.Width() * SurfBytesPerPixel(m_plan.internal_fmt));
+        if (FillStripParams(sample0, nullptr, postPitch, MakeStore(nullptr, postPitch, m_plan.internal_fmt, false), &sp)) {
+            rp.strip = sp;
+            return take(BatchRoute::StripToneMap);
         }
     }
-    // Interleaved RGB without a convert draw (m_PSConvColorData.bEnable false, :849-853): every frame is repacked into its own slot of a
-    // batch texture (the reference's CopyFrame* upload: one repack launch per 32 frames, the sample pointers in its arguments) and ONE
-    // k_fused_strip:surface launch resizes the whole chunk from there, instead of a repack + a resize launch per frame
-    if (m_srcParams->layout == LAY_RGB && !m_plan.convert && m_stripSurf && m_plan.two_pass && !m_plan.hdr_tonemap && n > 1 &&
-        !(m_cfg.flags & (MPCVR_FLAG_NO_FUSED | MPCVR_FLAG_NO_FAST_CONVERT | MPCVR_FLAG_NO_STRIP))) {
+    // (a batch of one needs no frame table: the frame travels in the kernel arguments, like mpcvr_process)
+    if ((!m_plan.fused_up2x && !strip && !batchable) || !rp.src4 || n == 1) return take(BatchRoute::FrameByFrame);
+    if (batchable) return take(BatchRoute::WholeBatchLaunches);
+    if (strip) {
+        rp.strip = sp;
+        return take(BatchRoute::Strip);
+    }
+    return take(BatchRoute::FusedUp2x);
+}
+
+// the launches of a classified batch on m_stream (the context stream or a lane's)
+HRESULT CHipVideoProcessor::RunBatchRoute(BatchRoutePlan &rp, int n, const void *const *srcs, void *const *dsts, int rtPitch)
+{
+    HRESULT hr = MPCVR_S_OK;
+    bool started = m_keepStart;                         // m_evStart sits in front of the batch's first launch (the repack's, if any)
+    auto start = [&] { if (!started) (void)hipEventRecord(m_evStart, m_stream); started = true; };
+    std::vector<const void *> slots;
+    if (rp.repackSlot) {
+        if ((hr = CheckHip(m_batchTex.CheckCreate(rp.repackSlot * n), "batch source texture"))) return hr;
+        start();                                        // the repack is part of the batch's process time
+        if ((hr = CheckHip(LaunchRepackV210(nullptr, m_srcPitch, (uint8_t *)m_batchTex.ptr, TexPitch(), m_srcHeight, m_stream, srcs, n, rp.repackSlot), "k_repack_v210"))) return hr;
+        m_batchTexZeroed = false;                       // (the RGB batches' zeroed remainder columns are gone)
+        slots.resize(n);
+        for (int i = 0; i < n; i++) slots[i] = (uint8_t *)m_batchTex.ptr + (size_t)i * rp.repackSlot;
+        srcs = slots.data();
+    }
+    if (m_dvFrames && (rp.route == BatchRoute::DirectConvert || rp.route == BatchRoute::WholeBatchLaunches)) {
+        // one RPU per frame: the block convert reads the run's tables (what FillConvertParams / FillFusedParams point the kernels at from here on)
+        m_dvTabDev = m_dvTabReady; m_dvCmDev = m_dvCmReady;
+        if (m_doviValid) { rp.direct.conv.dovi = rp.conv.conv.dovi = m_dvTabDev; rp.direct.dovi_cm = rp.conv.dovi_cm = m_dvCmDev; }
+    }
+    // The frame table travels through a small ring of pinned/device slots so the host can queue several batches ahead; a slot is reused
+    // only after the launches that read it have completed (`done`, recorded behind them).
+    const FusedFrame *table = nullptr;
+    hipEvent_t done = nullptr;
+    switch (rp.route) {
+    case BatchRoute::DirectConvert:
+        if (n <= kHostTableMax) {
+            // same-size frames: one convert launch with the frame table in its kernel arguments (32 frames for the block convert, 128 where the
+            // streaming kernel takes the launch — it answers hipErrorInvalidValue otherwise and the table is uploaded below)
+            FusedFrame tab[kHostTableMax];
+            for (int i = 0; i < n; i++) tab[i] = FusedFrame{(const uint8_t *)srcs[i], dsts[i]};
+            start();
+            const hipError_t e = LaunchConvertBlocks(rp.direct, nullptr, FusedFrame{nullptr, nullptr}, n, m_stream, 0, tab);
+            if (e != hipErrorInvalidValue || n <= 32) { hr = CheckHip(e, "k_convert_blocks"); break; }
+        }
+        if ((hr = UploadFrameTable(n, srcs, dsts, nullptr, 0, &table, &done))) break;
+        start();
+        hr = CheckHip(LaunchConvertBlocks(rp.direct, table, FusedFrame{nullptr, nullptr}, n, m_stream), "k_convert_blocks");
+        break;
+    case BatchRoute::RgbSurfaceStrip: {
+        // Interleaved RGB without a convert draw (m_PSConvColorData.bEnable false, :849-853): every frame is repacked into its own slot of a
+        // batch texture (the reference's CopyFrame* upload: one repack launch per 32 frames, the sample pointers in its arguments) and ONE
+        // k_fused_strip:surface launch resizes the whole chunk from there, instead of a repack + a resize launch per frame
         const int tp = TexPitch();
         const size_t texBytes = (size_t)tp * m_srcHeight;
         const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, ((size_t)1 << 30) / std::max<size_t>(texBytes, 1)));
         const bool fresh = m_batchTex.size < texBytes * chunk || !m_batchTex.ptr || !m_batchTexZeroed;     // (not by size alone: a v210 batch or another media type may have used it since)
-        if ((hr = CheckHip(m_batchTex.CheckCreate(texBytes * chunk), "batch source texture"))) return hr;
-        const Surface cs{m_batchTex.ptr, tp, m_srcWidth, m_srcHeight, RgbTexFmt(*m_srcParams)};
-        FusedStripParams ssp{};
-        if (FillStripSurfParams(cs, MakeStore(dsts[0], rtPitch, m_plan.swap_fmt, true), &ssp)) {
-            // texels the reference's copy loop never writes (RGB48 remainder) stay zero, as in PrepareSample
-            if (fresh && (hr = CheckHip(hipMemsetAsync(m_batchTex.ptr, 0, texBytes * chunk, m_stream), "clear batch texture"))) return hr;
-            m_batchTexZeroed = true;
-            FrameSlot &slot = m_slots[m_slotNext];
-            m_slotNext = (m_slotNext + 1) % kFrameSlots;
-            if (!slot.done && (hr = CheckHip(hipEventCreateWithFlags(&slot.done, hipEventDisableTiming), "slot event"))) return hr;
-            if (slot.used && (hr = CheckHip(hipEventSynchronize(slot.done), "slot wait"))) return hr;
-            if ((size_t)n > slot.cap) {
-                if (slot.pinned) (void)hipHostFree(slot.pinned);
-                slot.pinned = nullptr; slot.cap = 0;
-                const size_t cap = n < 64 ? 64 : (size_t)n;
-                if ((hr = CheckHip(hipHostMalloc(&slot.pinned, sizeof(FusedFrame) * cap, hipHostMallocDefault), "frames pinned"))) return hr;
-                if ((hr = CheckHip(slot.dev.CheckCreate(sizeof(FusedFrame) * cap), "frames"))) return hr;
-                slot.cap = cap;
-            }
-            FusedFrame *fr = (FusedFrame *)slot.pinned;
-            for (int i = 0; i < n; i++) { fr[i].src = (const uint8_t *)srcs[i]; fr[i].dst = dsts[i]; }
-            if ((hr = CheckHip(hipMemcpyAsync(slot.dev.ptr, fr, sizeof(FusedFrame) * n, hipMemcpyHostToDevice, m_stream), "frame table"))) return hr;
-            bool aligned8 = true;
-            for (int i = 0; i < n; i++)
-                if (((uintptr_t)dsts[i] & 7) != 0) aligned8 = false;
-            ssp.surf_stride = texBytes;
-            ssp.fp.dst_aligned16 = aligned8 ? 1 : 0;
-            if (!m_startRecorded) (void)hipEventRecord(m_evStart, m_stream);
-            for (int at = 0; at < n && !hr; at += chunk) {
-                const int m = std::min(chunk, n - at);
-                hr = CheckHip(LaunchRepackRgb(m_srcParams->repack, nullptr, m_srcBottomUp ? -m_srcPitch : m_srcPitch, (uint8_t *)m_batchTex.ptr, tp,
-                                              m_srcWidth, m_srcHeight, m_stream, srcs + at, m, texBytes), "k_repack_rgb");
-                if (!hr) hr = CheckHip(LaunchFusedStrip(ssp, (const FusedFrame *)slot.dev.ptr + at, FusedFrame{nullptr, nullptr}, m, m_stream), "k_fused_strip<surface>");
-            }
-            (void)hipEventRecord(m_evStop, m_stream);
-            (void)hipEventRecord(slot.done, m_stream);
-            slot.used = true;
-            m_timed = true;
-            return hr;
+        if ((hr = CheckHip(m_batchTex.CheckCreate(texBytes * chunk), "batch source texture"))) break;
+        // texels the reference's copy loop never writes (RGB48 remainder) stay zero, as in PrepareSample
+        if (fresh && (hr = CheckHip(hipMemsetAsync(m_batchTex.ptr, 0, texBytes * chunk, m_stream), "clear batch texture"))) break;
+        m_batchTexZeroed = true;
+        if ((hr = UploadFrameTable(n, srcs, dsts, nullptr, 0, &table, &done))) break;
+        rp.strip.surf.ptr = m_batchTex.ptr;
+        rp.strip.surf_stride = texBytes;
+        rp.strip.fp.dst_aligned16 = rp.aligned8 ? 1 : 0;
+        start();
+        for (int at = 0; at < n && !hr; at += chunk) {
+            const int m = std::min(chunk, n - at);
+            hr = CheckHip(LaunchRepackRgb(m_srcParams->repack, nullptr, m_srcBottomUp ? -m_srcPitch : m_srcPitch, (uint8_t *)m_batchTex.ptr, tp,
+                                          m_srcWidth, m_srcHeight, m_stream, srcs + at, m, texBytes), "k_repack_rgb");
+            if (!hr) hr = CheckHip(LaunchFusedStrip(rp.strip, table + at, FusedFrame{nullptr, nullptr}, m, m_stream), "k_fused_strip<surface>");
         }
+        break;
     }
-    // HDR10 tone-mapping step behind the one-kernel strip path (what a single frame of this plan runs, ProcessOne): the strip kernel draws
-    // every frame of a chunk into its slot of m_batchPost (a second frame table: same samples, the slots as targets) and ONE
-    // k_hdr10_tonemap launch writes the render targets (:3359-3367)
-    if (m_plan.hdr_tonemap && m_strip && !m_plan.fused_up2x && src4 && n > 1 && !(m_cfg.flags & (MPCVR_FLAG_NO_FUSED | MPCVR_FLAG_NO_FAST_CONVERT | MPCVR_FLAG_NO_STRIP))) {
+    case BatchRoute::StripToneMap: {
+        // HDR10 tone-mapping step behind the one-kernel strip path (what a single frame of this plan runs, ProcessOne): the strip kernel draws
+        // every frame of a chunk into its slot of m_batchPost (a second frame table: same samples, the slots as targets) and ONE
+        // k_hdr10_tonemap launch writes the render targets (:3359-3367)
         const int w2 = m_videoRect.Width(), h2 = m_videoRect.Height();
         const size_t postStride = PostStride();
         const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, ((size_t)4 << 30) / std::max<size_t>(postStride, 1)));
-        if ((hr = CheckHip(m_batchPost.CheckCreate(postStride * chunk), "batch post-scale textures"))) return hr;
+        if ((hr = CheckHip(m_batchPost.CheckCreate(postStride * chunk), "batch post-scale textures"))) break;
         const Surface post{m_batchPost.ptr, (int)(w2 * SurfBytesPerPixel(m_plan.internal_fmt)), w2, h2, m_plan.internal_fmt};
-        const StoreParams last = MakeStore(post.ptr, post.pitch, m_plan.internal_fmt, false);
-        FusedStripParams sp{};
-        if (FillStripParams((const uint8_t *)srcs[0], post.ptr, post.pitch, last, &sp)) {
-            sp.fp.dst_aligned16 = 1;                         // the slots start on 256-byte boundaries
-            if (!m_startRecorded) (void)hipEventRecord(m_evStart, m_stream);
-            for (int at = 0; at < n; at += chunk) {
-                const int m = std::min(chunk, n - at);
-                const FusedFrame *drawTab = nullptr, *realTab = nullptr;
-                hipEvent_t d1 = nullptr, d2 = nullptr;
-                if ((hr = UploadFrameTable(m, srcs + at, nullptr, (uint8_t *)m_batchPost.ptr, postStride, &drawTab, &d1))) return hr;
-                if ((hr = UploadFrameTable(m, srcs + at, dsts + at, nullptr, 0, &realTab, &d2))) return hr;
-                if ((hr = CheckHip(LaunchFusedStrip(sp, drawTab, FusedFrame{nullptr, nullptr}, m, m_stream), "k_fused_strip"))) return hr;
-                ResizeBatch tb; tb.n = m; tb.in_stride = postStride; tb.frames = realTab;
-                if ((hr = CheckHip(LaunchHdr10ToneMap(post, m_hdrTm, w2, h2, MakeStore(dsts[at], rtPitch, m_plan.swap_fmt, true), m_stream, &tb), "k_hdr10_tonemap"))) return hr;
-                (void)hipEventRecord(d1, m_stream);
-                (void)hipEventRecord(d2, m_stream);
-            }
-            (void)hipEventRecord(m_evStop, m_stream);
-            m_timed = true;
-            return MPCVR_S_OK;
+        rp.strip.fp.store.dst = post.ptr;
+        rp.strip.fp.dst_aligned16 = 1;                         // the slots start on 256-byte boundaries
+        start();
+        for (int at = 0; at < n && !hr; at += chunk) {
+            const int m = std::min(chunk, n - at);
+            const FusedFrame *drawTab = nullptr, *realTab = nullptr;
+            hipEvent_t d1 = nullptr, d2 = nullptr;
+            if ((hr = UploadFrameTable(m, srcs + at, nullptr, (uint8_t *)m_batchPost.ptr, postStride, &drawTab, &d1))) break;
+            if ((hr = UploadFrameTable(m, srcs + at, dsts + at, nullptr, 0, &realTab, &d2))) break;
+            ResizeBatch tb; tb.n = m; tb.in_stride = postStride; tb.frames = realTab;
+            if (!(hr = CheckHip(LaunchFusedStrip(rp.strip, drawTab, FusedFrame{nullptr, nullptr}, m, m_stream), "k_fused_strip")))
+                hr = CheckHip(LaunchHdr10ToneMap(post, m_hdrTm, w2, h2, MakeStore(dsts[at], rtPitch, m_plan.swap_fmt, true), m_stream, &tb), "k_hdr10_tonemap");
+            (void)hipEventRecord(d1, m_stream);
+            (void)hipEventRecord(d2, m_stream);
         }
+        break;
     }
-    // (a batch of one needs no frame table: the frame travels in the kernel arguments, like mpcvr_process)
-    if ((!m_plan.fused_up2x && !strip && !batchable) || !src4 || n == 1) {
-        // samples that are repacked (or, not starting on a dword, copied) first share m_TexSrcVideo: those batches stay on the
-        // context stream, frame by frame
-        const bool repack = (m_srcParams->cformat == MPCVR_CF_V210 && !m_batchRepacked) || m_srcParams->layout == LAY_RGB || !src4;
-        // MPCVR_BATCH_LANES=2..4 deals the frames to that many streams with private intermediates.  Measured on MI355X:
-        // +5..10 % on the two-pass resize geometries, -15 % on 1080p same-size (fork/join events cost more than the
-        // overlap returns), so one lane is the default.
-        static const int want = [] { const char *e = std::getenv("MPCVR_BATCH_LANES"); return e ? std::atoi(e) : 1; }();
-        const int lanes = (repack || n < 2 || want < 2 || m_dvFrames) ? 1 : std::min(std::min(n, want), (int)kLanes);
-        if (lanes > 1 && (hr = PrepareLanes(lanes))) return hr;
-        if (!m_startRecorded) (void)hipEventRecord(m_evStart, m_stream);
-        if (lanes > 1) {
-            if ((hr = CheckHip(hipEventRecord(m_fork, m_stream), "fork"))) return hr;
-            for (int l = 1; l < lanes; l++)
-                if ((hr = CheckHip(hipStreamWaitEvent(m_lanes[l].stream, m_fork, 0), "lane fork"))) return hr;
-        }
+    case BatchRoute::FrameByFrame:
+        // samples that are repacked (or, not starting on a dword, copied) into m_TexSrcVideo one by one share it: frame by frame
+        start();
         for (int i = 0; i < n && !hr; i++) {
-            const uint8_t *tex;
-            UseLane(i % lanes);
-            if (m_batchRepacked) tex = (const uint8_t *)srcs[i];           // (already in m_TexSrcVideo's layout: a slot of the batch texture)
-            else if ((hr = PrepareSample((const uint8_t *)srcs[i], &tex))) break;
+            const uint8_t *tex = (const uint8_t *)srcs[i];           // (repacked: already in m_TexSrcVideo's layout, a slot of the batch texture)
+            if (!rp.repackSlot && (hr = PrepareSample((const uint8_t *)srcs[i], &tex))) break;
             if (m_dvFrames && (hr = ApplyDoviFrame(m_dvFrames[i]))) break;          // this frame's RPU: constants, matrix, tone-mapping metadata
             hr = ProcessOne(tex, dsts[i], rtPitch);
         }
-        UseLane(0);
-        for (int l = 1; l < lanes; l++) {        // join, also on the error path: the context stream stays the only handle
-            (void)hipEventRecord(m_lanes[l].done, m_lanes[l].stream);
-            (void)hipStreamWaitEvent(m_stream, m_lanes[l].done, 0);
-        }
-        if (hr) return hr;
-        (void)hipEventRecord(m_evStop, m_stream);
-        m_timed = true;
-        return MPCVR_S_OK;
+        break;
+    case BatchRoute::WholeBatchLaunches:
+        if ((hr = UploadFrameTable(n, srcs, dsts, nullptr, 0, &table, &done))) break;
+        start();
+        hr = ProcessBatchLaunches(n, table, dsts[0], rtPitch, rp.aligned, rp.conv);
+        break;
+    case BatchRoute::Strip:
+        if ((hr = UploadFrameTable(n, srcs, dsts, nullptr, 0, &table, &done))) break;
+        rp.strip.fp.dst_aligned16 = rp.aligned8 ? 1 : 0;
+        start();
+        hr = CheckHip(LaunchFusedStrip(rp.strip, table, FusedFrame{nullptr, nullptr}, n, m_stream), "k_fused_strip");
+        break;
+    case BatchRoute::FusedUp2x: {
+        if ((hr = UploadFrameTable(n, srcs, dsts, nullptr, 0, &table, &done))) break;
+        FusedParams fp{};
+        FillFusedParams((const uint8_t *)srcs[0], nullptr, rtPitch, &fp);
+        fp.dst_aligned16 = rp.aligned ? 1 : 0;
+        start();
+        hr = CheckHip(LaunchFusedUp2x(fp, table, FusedFrame{nullptr, nullptr}, n, m_stream), "k_fused_up2x");
+        break;
     }
-    // one launch for the whole batch
-    // The frame table travels through a small ring of pinned/device slots so the host can queue several
-    // batches ahead; a slot is reused only after the launch that read it has completed (its event).
-    FrameSlot &slot = m_slots[m_slotNext];
-    m_slotNext = (m_slotNext + 1) % kFrameSlots;
-    if (!slot.done && (hr = CheckHip(hipEventCreateWithFlags(&slot.done, hipEventDisableTiming), "slot event"))) return hr;
-    if (slot.used && (hr = CheckHip(hipEventSynchronize(slot.done), "slot wait"))) return hr;
-    if ((size_t)n > slot.cap) {
-        if (slot.pinned) (void)hipHostFree(slot.pinned);
-        slot.pinned = nullptr; slot.cap = 0;
-        const size_t cap = n < 64 ? 64 : (size_t)n;
-        if ((hr = CheckHip(hipHostMalloc(&slot.pinned, sizeof(FusedFrame) * cap, hipHostMallocDefault), "frames pinned"))) return hr;
-        if ((hr = CheckHip(slot.dev.CheckCreate(sizeof(FusedFrame) * cap), "frames"))) return hr;
-        slot.cap = cap;
     }
-    FusedFrame *fr = (FusedFrame *)slot.pinned;
-    for (int i = 0; i < n; i++) { fr[i].src = (const uint8_t *)srcs[i]; fr[i].dst = dsts[i]; }
-    if ((hr = CheckHip(hipMemcpyAsync(slot.dev.ptr, fr, sizeof(FusedFrame) * n, hipMemcpyHostToDevice, m_stream), "frame table"))) return hr;
-    if (batchable) {
-        if (!m_startRecorded) (void)hipEventRecord(m_evStart, m_stream);
-        hr = ProcessBatchLaunches(n, (const FusedFrame *)slot.dev.ptr, (const uint8_t *)srcs[0], dsts[0], rtPitch, aligned);
-        (void)hipEventRecord(m_evStop, m_stream);
-        (void)hipEventRecord(slot.done, m_stream);
-        slot.used = true;
-        m_timed = true;
-        return hr;
-    }
-    if (strip) {
-        bool aligned8 = true;
-        for (int i = 0; i < n; i++)
-            if (((uintptr_t)dsts[i] & 7) != 0) aligned8 = false;
-        strip_sp.fp.dst_aligned16 = aligned8 ? 1 : 0;
-        if (!m_startRecorded) (void)hipEventRecord(m_evStart, m_stream);
-        hr = CheckHip(LaunchFusedStrip(strip_sp, (const FusedFrame *)slot.dev.ptr, FusedFrame{nullptr, nullptr}, n, m_stream), "k_fused_strip");
-        (void)hipEventRecord(m_evStop, m_stream);
-        (void)hipEventRecord(slot.done, m_stream);
-        slot.used = true;
-        m_timed = true;
-        return hr;
-    }
-    FusedParams fp{};
-    FillFusedParams((const uint8_t *)srcs[0], nullptr, rtPitch, &fp);
-    fp.dst_aligned16 = aligned ? 1 : 0;
-    if (!m_startRecorded) (void)hipEventRecord(m_evStart, m_stream);
-    hr = CheckHip(LaunchFusedUp2x(fp, (const FusedFrame *)slot.dev.ptr, FusedFrame{nullptr, nullptr}, n, m_stream), "k_fused_up2x");
     (void)hipEventRecord(m_evStop, m_stream);
-    (void)hipEventRecord(slot.done, m_stream);
-    slot.used = true;
+    if (done) (void)hipEventRecord(done, m_stream);
     m_timed = true;
     return hr;
 }
@@ -1741,7 +1644,7 @@ HRESULT CHipVideoProcessor::ProcessBatchErrDiff(int n, const void *const *srcs, 
     // the batch's process time runs from in front of the first chunk to behind the last chunk's pass
     (void)JoinFrameLanes(false);
     (void)hipEventRecord(m_evStart, m_stream);
-    m_startRecorded = true; m_keepStart = true;
+    m_keepStart = true;
     struct KeepStartGuard { bool &f; ~KeepStartGuard() { f = false; } } keepGuard{m_keepStart};
     for (int at = 0; at < n; at += chunk) {
         const int m = std::min(chunk, n - at);
@@ -1794,49 +1697,38 @@ HRESULT CHipVideoProcessor::UploadFrameTable(int n, const void *const *srcs, voi
     return MPCVR_S_OK;
 }
 
-// Can this plan run as whole-batch launches?  *conv: the block convert into the (batched) convert output; *direct: the block
-// convert straight into the render targets (same-size frames).  Exactly one of them is used.
-bool CHipVideoProcessor::BatchPlan(const uint8_t *sample0, void *rt0, int rtPitch, bool aligned, FusedParams *conv, FusedParams *direct) const
+// Can this plan run as whole-batch launches?  *conv: the block convert into the (batched) convert output, its target set per chunk by
+// ProcessBatchLaunches; *direct: the block convert straight into the render targets (same-size frames).  Exactly one of them is filled.
+// repacked: the samples are v210 slots of m_batchTex; src16: every sample starts on a 16-byte boundary.
+bool CHipVideoProcessor::BatchPlan(const uint8_t *sample0, void *rt0, int rtPitch, bool aligned, bool repacked, bool src16, FusedParams *conv, FusedParams *direct) const
 {
     // every draw kernel has a frame dimension (round 4: the one-kernel-fits-all k_resize / k_jinc2 too — quarter turns, flips outside the
     // strip kernels' reach, the two-draw Jinc2m), so what decides is the convert stage: the 2x2-block kernel must take the sample
     if (!m_plan.convert) return false;
-    if ((m_srcParams->cformat == MPCVR_CF_V210 && !m_batchRepacked) || m_srcParams->layout == LAY_RGB) return false;
-    const int w1 = m_srcRectWidth, h1 = m_srcRectHeight, w2 = m_videoRect.Width();
+    if ((m_srcParams->cformat == MPCVR_CF_V210 && !repacked) || m_srcParams->layout == LAY_RGB) return false;
     if (m_plan.direct_convert) {
         FillFusedParams(sample0, rt0, rtPitch, direct);
         direct->dst_aligned16 = aligned ? 1 : 0;
-        direct->src_aligned16 = m_batchSrc16 ? 1 : 0;
+        direct->src_aligned16 = src16 ? 1 : 0;
         return ConvertBlocksSupported(*direct, true);
     }
     // with the HDR10 tone-mapping step (:3359-3367) the draws go into the frames' post-scale textures (m_batchPost, internal format)
     // and one tone-mapping launch writes the render targets; without a resize the step reads the convert outputs
-    const bool hdr = m_plan.hdr_tonemap;
-    if (!m_plan.two_pass && !m_plan.one_pass && !hdr) return false;
-    const int convPitch = (int)(w1 * SurfBytesPerPixel(m_plan.internal_fmt));
-    FillFusedParams(sample0, m_batchConv.ptr, convPitch, conv);
-    conv->store = MakeStore(m_batchConv.ptr, convPitch, m_plan.internal_fmt, false);
+    if (!m_plan.two_pass && !m_plan.one_pass && !m_plan.hdr_tonemap) return false;
+    const int convPitch = (int)(m_srcRectWidth * SurfBytesPerPixel(m_plan.internal_fmt));
+    FillFusedParams(sample0, nullptr, convPitch, conv);
+    conv->store = MakeStore(nullptr, convPitch, m_plan.internal_fmt, false);
     conv->dst_aligned16 = 1;
-    conv->src_aligned16 = m_batchSrc16 ? 1 : 0;
+    conv->src_aligned16 = src16 ? 1 : 0;
     conv->exact_convert = 1;
-    if (!ConvertBlocksSupported(*conv, false)) return false;
-    const Surface cs{nullptr, convPitch, w1, h1, m_plan.internal_fmt};
-    const StoreParams final = hdr ? MakeStore((void *)(uintptr_t)4096, (int)(w2 * SurfBytesPerPixel(m_plan.internal_fmt)), m_plan.internal_fmt, false)
-                                  : MakeStore(rt0, rtPitch, m_plan.swap_fmt, true);
-    (void)cs; (void)final; (void)w2;
-    return true;            // the draws: ProcessBatchLaunches picks the kernel per chunk exactly as ResizeShaderPass does per frame
+    return ConvertBlocksSupported(*conv, false);     // the draws: ProcessBatchLaunches picks the kernel per chunk exactly as ResizeShaderPass does per frame
 }
 
 // convert all -> first draw all -> second draw all, a frame dimension in every grid; the intermediates hold `chunk` frames
-HRESULT CHipVideoProcessor::ProcessBatchLaunches(int n, const FusedFrame *table, const uint8_t *sample0, void *rt0, int rtPitch, bool aligned)
+HRESULT CHipVideoProcessor::ProcessBatchLaunches(int n, const FusedFrame *table, void *rt0, int rtPitch, bool aligned, FusedParams conv)
 {
     HRESULT hr;
     const int w1 = m_srcRectWidth, h1 = m_srcRectHeight, w2 = m_videoRect.Width(), h2 = m_videoRect.Height();
-    FusedParams conv{}, direct{};
-    if (m_plan.direct_convert) {
-        if (!BatchPlan(sample0, rt0, rtPitch, aligned, &conv, &direct)) return Fail(MPCVR_E_UNEXPECTED, "batch plan changed");
-        return CheckHip(LaunchConvertBlocks(direct, table, FusedFrame{nullptr, nullptr}, n, m_stream), "k_convert_blocks");
-    }
     // intermediates for up to `chunk` frames (at most ~4 GiB)
     const bool hdr = m_plan.hdr_tonemap;
     const size_t postStride = hdr ? PostStride() : 0;
@@ -1845,7 +1737,6 @@ HRESULT CHipVideoProcessor::ProcessBatchLaunches(int n, const FusedFrame *table,
     if ((hr = CheckHip(m_batchConv.CheckCreate(m_convBytes * chunk), "batch convert output"))) return hr;
     if (m_midBytes && (hr = CheckHip(m_batchMid.CheckCreate(m_midBytes * chunk), "batch resize texture"))) return hr;
     if (hdr && (hr = CheckHip(m_batchPost.CheckCreate(postStride * chunk), "batch post-scale textures"))) return hr;
-    if (!BatchPlan(sample0, rt0, rtPitch, aligned, &conv, &direct)) return Fail(MPCVR_E_UNEXPECTED, "batch plan changed");
     const int convPitch = (int)(w1 * SurfBytesPerPixel(m_plan.internal_fmt));
     const Surface cs{m_batchConv.ptr, convPitch, w1, h1, m_plan.internal_fmt};
     const StoreParams target = MakeStore(rt0, rtPitch, m_plan.swap_fmt, true);

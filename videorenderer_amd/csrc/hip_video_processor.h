@@ -237,13 +237,6 @@ private:
     FrameSlot m_slots[kFrameSlots];
     int m_slotNext = 0;
     uint16_t m_ditherHost[1024];
-    // mpcvr_process_batch on the pass-per-kernel path: the frames of a batch are independent, so they can be dealt to a
-    // few lanes (stream + private intermediates) whose kernels overlap (opt-in, MPCVR_BATCH_LANES; see ProcessBatch).
-    // Lane 0 is the context stream with m_TexConvertOutput / m_TexResize / m_TexPost.
-    static constexpr int kLanes = 4;
-    struct Lane { hipStream_t stream = nullptr; DevBuffer conv, mid, post; hipEvent_t done = nullptr; };
-    Lane m_lanes[kLanes];
-    hipEvent_t m_fork = nullptr;
     // mpcvr_process frame after frame (the reference's own call pattern, Render -> Process, DX11VideoProcessor.cpp:2730): a single 4K
     // frame is one round of waves on this part, so a kernel's ramp-up and drain cost a third of its time when frames run strictly one
     // after the other.  Frames are independent (a D3D11 driver overlaps draws into different render targets as well): a context that
@@ -264,11 +257,8 @@ private:
                        std::vector<const void *> batchRts; hipEvent_t batchDone = nullptr; bool batchPending = false; };
     static constexpr int kBatchLanes = 2;
     int m_blaneNext = 0;
-    bool m_batchOnLane = false;               // ProcessBatchRoutesOn runs with m_stream = a lane's stream
-    bool BatchLanesUsable(int n, const void *const *srcs, void *const *dsts, int rtPitch);
     FrameLane *PickBatchLane(int n, void *const *dsts);
     void NoteLaneBatch(FrameLane *fl, int n, void *const *dsts);
-    HRESULT ProcessBatchRoutesOn(int n, const void *const *srcs, void *const *dsts, int rtPitch);
     // work queued on the CONTEXT stream (a batch, a frame that ran off the lanes, a sample copy / repack, a read-back) since a lane last
     // waited for it: every such call bumps m_streamGen; a lane whose seenGen is behind waits for an event recorded on the context stream
     // (m_evStreamMark, recorded once per generation) before its next frame — a lane frame into the render target, or out of the sample, that
@@ -288,10 +278,10 @@ private:
     HRESULT JoinFrameLanes(bool host_wait);
     void NoteLaneFrame(FrameLane *fl, const void *rt);
     size_t m_convBytes = 0, m_midBytes = 0, m_postBytes = 0;
-    // resources of the frame being processed (lane 0 outside ProcessBatch)
+    // resources of the frame being processed: the context stream's, or (Process) a frame lane's stream with the context's surfaces
     hipStream_t m_run = nullptr;
     void *m_runConv = nullptr, *m_runMid = nullptr, *m_runPost = nullptr;
-    void UseLane(int lane);
+    void UseContextResources();
     // whole-batch launches of the pass-per-kernel path (block convert + folded resize kernels with a frame dimension)
     DevBuffer m_batchConv, m_batchMid;
     DevBuffer m_batchPost;         // HDR10 tone-mapping step of a batch: the frames' m_TexsPostScale copies side by side
@@ -317,10 +307,7 @@ private:
     HRESULT UploadFrameTable(int n, const void *const *srcs, void *const *dsts, uint8_t *dst_base, size_t dst_stride, const FusedFrame **dev, hipEvent_t *done);
     DevBuffer m_batchTex;          // interleaved RGB / v210 batches: the frames' m_TexSrcVideo copies side by side (ProcessBatch)
     bool m_texSrcZeroed = false, m_batchTexZeroed = false;     // the texels the RGB copy loops never write have been cleared for the current media type
-    bool m_startRecorded = false;  // ProcessBatch: m_evStart already sits in front of a repack launch
     bool m_keepStart = false;      // ProcessBatchErrDiff: m_evStart sits in front of the FIRST chunk; the chunks' ProcessBatchRoutes calls leave it there
-    bool m_batchRepacked = false;  // the batch at hand reads v210 samples already repacked into m_batchTex
-    bool m_batchSrc16 = false;     // every sample of the batch being planned starts on a 16-byte boundary
     // Jinc2m phase tables of the first / second draw (null: weights per pixel)
     DevBuffer m_jincFirst, m_jincSecond, m_jincFused;
     const float *m_jincFusedTab = nullptr;                                  // the fused Jinc2m kernel's weight table (BuildFusedJincTable), PassPlan::fused_jinc
@@ -342,9 +329,19 @@ private:
                                    // probe uses a null, aligned target — a real target with an odd pitch or offset sends the launch to k_fused_strip (GetPathInfo reports what ran)
     size_t m_periodOff[4] = {0, 0, 0, 0};     // xi_t | xw_t | yw | xstrip
     bool m_period = false;         // the planned launch (window-sized target) takes the periodic kernel: what GetVPInfo reports
-    bool BatchPlan(const uint8_t *sample0, void *rt0, int rtPitch, bool aligned, FusedParams *conv, FusedParams *direct) const;
-    HRESULT ProcessBatchLaunches(int n, const FusedFrame *table, const uint8_t *sample0, void *rt0, int rtPitch, bool aligned);
-    HRESULT PrepareLanes(int lanes);
+    // the route of a mpcvr_process_batch call, in order of precedence (ClassifyBatch), and what its launches need
+    enum class BatchRoute { DirectConvert, RgbSurfaceStrip, StripToneMap, FrameByFrame, WholeBatchLaunches, Strip, FusedUp2x };
+    struct BatchRoutePlan {
+        BatchRoute route = BatchRoute::FrameByFrame;
+        size_t repackSlot = 0;         // v210: the samples are repacked first, into slots of m_batchTex of this many bytes (256-byte aligned); 0: not
+        bool aligned = true, aligned8 = true, src16 = true, src4 = true;   // every render target on a 16- / 8-byte boundary; every sample the launches read on a 16- / 4-byte one
+        FusedStripParams strip{};      // RgbSurfaceStrip / StripToneMap / Strip (surface / post-scale pointers: set by RunBatchRoute)
+        FusedParams conv{}, direct{};  // WholeBatchLaunches / DirectConvert (BatchPlan)
+    };
+    BatchRoutePlan ClassifyBatch(int n, const void *const *srcs, void *const *dsts, int rtPitch) const;
+    HRESULT RunBatchRoute(BatchRoutePlan &rp, int n, const void *const *srcs, void *const *dsts, int rtPitch);
+    bool BatchPlan(const uint8_t *sample0, void *rt0, int rtPitch, bool aligned, bool repacked, bool src16, FusedParams *conv, FusedParams *direct) const;
+    HRESULT ProcessBatchLaunches(int n, const FusedFrame *table, void *rt0, int rtPitch, bool aligned, FusedParams conv);
 };
 
 }  // namespace mpcvr
