@@ -1132,6 +1132,18 @@ void CHipVideoProcessor::MarkConsumed()
     if (u.consumed && hipEventRecord(u.consumed, m_lastRun ? m_lastRun : m_stream) == hipSuccess) u.consumedRecorded = true;
 }
 
+// the block convert into m_TexConvertOutput (`out`; a batch's chunks set it to theirs) in front of a draw
+FusedParams CHipVideoProcessor::ConvertOutputParams(const uint8_t *sample, void *out) const
+{
+    const int pitch = (int)(m_srcRectWidth * SurfBytesPerPixel(m_plan.internal_fmt));
+    FusedParams fp{};
+    FillFusedParams(sample, out, pitch, &fp);
+    fp.store = MakeStore(out, pitch, m_plan.internal_fmt, false);
+    fp.dst_aligned16 = 1;
+    fp.exact_convert = 1;
+    return fp;
+}
+
 HRESULT CHipVideoProcessor::ConvertColorPass(const uint8_t *sample)
 {
     ConvertParams P;
@@ -1139,29 +1151,30 @@ HRESULT CHipVideoProcessor::ConvertColorPass(const uint8_t *sample)
     Surface out{m_runConv, (int)(m_srcRectWidth * SurfBytesPerPixel(m_plan.internal_fmt)),
                 m_srcRectWidth, m_srcRectHeight, m_plan.internal_fmt};
     if (!(m_cfg.flags & MPCVR_FLAG_NO_FUSED)) {           // the fused kernel's block convert, when the source qualifies
-        FusedParams fp{};
-        FillFusedParams(sample, out.ptr, out.pitch, &fp);
-        fp.store = MakeStore(out.ptr, out.pitch, out.fmt, false);
-        fp.dst_aligned16 = 1;
-        fp.exact_convert = 1;            // m_TexConvertOutput in front of a draw
+        const FusedParams fp = ConvertOutputParams(sample, out.ptr);
         if (ConvertBlocksSupported(fp, false))
             return CheckHip(LaunchConvertBlocks(fp, nullptr, FusedFrame{sample, out.ptr}, 1, m_run), "k_convert_blocks");
     }
     return CheckHip(LaunchConvert(P, out, m_run, (m_cfg.flags & MPCVR_FLAG_NO_FUSED) != 0), "k_convert");
 }
 
-// ResizeShaderPass (:3103-3187) with FinalPass (:3189-3233) folded into the epilogue of the last draw
-HRESULT CHipVideoProcessor::ResizeShaderPass(void *rt, int rtPitch, const uint8_t *sample)
+// ResizeShaderPass (:3103-3187) with FinalPass (:3189-3233) folded into the epilogue of the last draw: one frame, or a chunk of a batch
+// with the chunk as every launch's frame dimension (DrawFrames)
+HRESULT CHipVideoProcessor::ResizeShaderPass(const uint8_t *sample, void *rt, int rtPitch, const DrawFrames &df)
 {
     const int w1 = m_srcRectWidth, h1 = m_srcRectHeight, w2 = m_videoRect.Width(), h2 = m_videoRect.Height();
-    Surface conv{m_runConv, (int)(w1 * SurfBytesPerPixel(m_plan.internal_fmt)), w1, h1, m_plan.internal_fmt};
+    Surface conv{df.conv, (int)(w1 * SurfBytesPerPixel(m_plan.internal_fmt)), w1, h1, m_plan.internal_fmt};
+    // (a batch reaches neither the source texture nor the copy below: BatchPlan refuses a plan without the convert draw, or with neither
+    // a draw nor the HDR10 step)
     if (!m_plan.convert)      // pInputTexture = &m_TexSrcVideo (:3321-3323)
         conv = Surface{(void *)sample, TexPitch(), m_srcWidth, m_srcHeight, RgbTexFmt(*m_srcParams)};
     const StoreParams final = MakeStore(rt, rtPitch, m_plan.swap_fmt, true);
     // with the HDR10 tone-mapping step the resize draws into a post-scale texture (internal format, video-rect sized)
     // and the step itself writes the render target / runs the final pass (:3359-3367)
-    Surface post{m_runPost, (int)(w2 * SurfBytesPerPixel(m_plan.internal_fmt)), w2, h2, m_plan.internal_fmt};
+    Surface post{df.post, (int)(w2 * SurfBytesPerPixel(m_plan.internal_fmt)), w2, h2, m_plan.internal_fmt};
     const StoreParams last = m_plan.hdr_tonemap ? MakeStore(post.ptr, post.pitch, m_plan.internal_fmt, false) : final;
+    // a draw from the convert output into the last draw's targets
+    ResizeBatch b; b.n = df.n; b.in_stride = df.convStride; b.frames = df.lastTab; b.dst_aligned8 = df.aligned;
     HRESULT hr = MPCVR_S_OK;
     bool drawn = true;
     const bool plain = (m_cfg.flags & MPCVR_FLAG_NO_FUSED) != 0;      // keep the whole path on the one-kernel-fits-all versions
@@ -1169,22 +1182,27 @@ HRESULT CHipVideoProcessor::ResizeShaderPass(void *rt, int rtPitch, const uint8_
     FusedStripParams ssp{};
     if (m_stripSurf && FillStripSurfParams(conv, last, &ssp)) {
         // convert output (or RGB source texture) -> both draws -> final pass in the arbitrary-ratio fused kernel, no convert stage
-        hr = CheckHip(LaunchFusedStrip(ssp, nullptr, FusedFrame{(const uint8_t *)conv.ptr, last.dst}, 1, m_run), "k_fused_strip<surface>");
+        ssp.surf_stride = df.convStride;
+        if (df.lastTab) ssp.fp.dst_aligned16 = df.aligned;
+        const FusedFrame one = df.lastTab ? FusedFrame{nullptr, nullptr} : FusedFrame{(const uint8_t *)conv.ptr, last.dst};
+        hr = CheckHip(LaunchFusedStrip(ssp, df.lastTab, one, df.n, m_run), "k_fused_strip<surface>");
     } else if (m_plan.two_pass && !plain && !m_firstJinc && !m_secondJinc && m_firstAxis == 0 && !m_firstSwap &&
         Resize2DSupported(conv, m_tapsX, m_tapsY, last)) {
         // both draws in one LDS-tiled kernel: m_TexResize stays on chip
-        hr = CheckHip(LaunchResize2D(conv, m_tapsX, m_tapsY, (const int32_t *)m_otherX.ptr, m_plan.mid_h, w2, h2, last, m_run), "k_resize_2d");
+        hr = CheckHip(LaunchResize2D(conv, m_tapsX, m_tapsY, (const int32_t *)m_otherX.ptr, m_plan.mid_h, w2, h2, last, m_run, &b), "k_resize_2d");
     } else if (m_plan.two_pass) {
-        Surface mid{m_runMid, w2 * 8, w2, m_plan.mid_h, SF_RGBA16F};
+        Surface mid{df.mid, w2 * 8, w2, m_plan.mid_h, SF_RGBA16F};
         StoreParams st = MakeStore(mid.ptr, mid.pitch, SF_RGBA16F, false);
-        if (m_firstJinc) hr = CheckHip(LaunchJinc2(conv, m_firstCoords, w2, m_plan.mid_h, st, m_run, m_jincFirstTab, jfast, nullptr, m_jincFirstCtr), "k_jinc2");
-        else hr = CheckHip(LaunchResize(m_firstAxis, m_firstSwap, conv, m_tapsX, (const int32_t *)m_otherX.ptr, w2, m_plan.mid_h, st, m_run, plain), "k_resize<first>");
+        ResizeBatch b1; b1.n = df.n; b1.in_stride = df.convStride; b1.dst_stride = df.midStride;
+        if (m_firstJinc) hr = CheckHip(LaunchJinc2(conv, m_firstCoords, w2, m_plan.mid_h, st, m_run, m_jincFirstTab, jfast, &b1, m_jincFirstCtr), "k_jinc2");
+        else hr = CheckHip(LaunchResize(m_firstAxis, m_firstSwap, conv, m_tapsX, (const int32_t *)m_otherX.ptr, w2, m_plan.mid_h, st, m_run, plain, &b1), "k_resize<first>");
         if (hr) return hr;
-        if (m_secondJinc) hr = CheckHip(LaunchJinc2(mid, m_secondCoords, w2, h2, last, m_run, m_jincSecondTab, jfast, nullptr, m_jincSecondCtr), "k_jinc2");
-        else hr = CheckHip(LaunchResize(1, false, mid, m_tapsY, (const int32_t *)m_otherY.ptr, w2, h2, last, m_run, plain), "k_resize<Y>");
+        ResizeBatch b2 = b; b2.in_stride = df.midStride;
+        if (m_secondJinc) hr = CheckHip(LaunchJinc2(mid, m_secondCoords, w2, h2, last, m_run, m_jincSecondTab, jfast, &b2, m_jincSecondCtr), "k_jinc2");
+        else hr = CheckHip(LaunchResize(1, false, mid, m_tapsY, (const int32_t *)m_otherY.ptr, w2, h2, last, m_run, plain, &b2), "k_resize<Y>");
     } else if (m_plan.one_pass) {
-        if (m_firstJinc) hr = CheckHip(LaunchJinc2(conv, m_firstCoords, w2, h2, last, m_run, m_jincFirstTab, jfast, nullptr, m_jincFirstCtr), "k_jinc2");
-        else hr = CheckHip(LaunchResize(m_firstAxis, m_firstSwap, conv, m_tapsX, (const int32_t *)m_otherX.ptr, w2, h2, last, m_run, plain), "k_resize<one>");
+        if (m_firstJinc) hr = CheckHip(LaunchJinc2(conv, m_firstCoords, w2, h2, last, m_run, m_jincFirstTab, jfast, &b, m_jincFirstCtr), "k_jinc2");
+        else hr = CheckHip(LaunchResize(m_firstAxis, m_firstSwap, conv, m_tapsX, (const int32_t *)m_otherX.ptr, w2, h2, last, m_run, plain, &b), "k_resize<one>");
     } else {
         drawn = false;
         if (!m_plan.convert) {    // the next step reads the source rect of the texture (pTex = pInputTexture, :3352)
@@ -1199,13 +1217,14 @@ HRESULT CHipVideoProcessor::ResizeShaderPass(void *rt, int rtPitch, const uint8_
         }
     }
     if (hr || !m_plan.hdr_tonemap) return hr;
-    return CheckHip(LaunchHdr10ToneMap(drawn ? post : conv, m_hdrTm, w2, h2, final, m_run), "k_hdr10_tonemap");
+    ResizeBatch tb; tb.n = df.n; tb.in_stride = drawn ? df.postStride : df.convStride; tb.frames = df.rtTab;
+    return CheckHip(LaunchHdr10ToneMap(drawn ? post : conv, m_hdrTm, w2, h2, final, m_run, &tb), "k_hdr10_tonemap");
 }
 
-// parameters of the arbitrary-ratio fused kernel for one launch; false: this launch cannot take it (alignment, sizes)
-bool CHipVideoProcessor::FillStripParams(const uint8_t *sample, void *dst, int dstPitch, const StoreParams &store, FusedStripParams *sp) const
+// what both forms of the arbitrary-ratio fused kernel take from the plan: the target, the strip tables and, for a periodic vertical ratio,
+// the register-window kernel's (per_force: FusedStripParams::per_force); false: this launch cannot take it (alignment, sizes)
+bool CHipVideoProcessor::FillStripTables(const StoreParams &store, int perForce, FusedStripParams *sp) const
 {
-    FillFusedParams(sample, dst, dstPitch, &sp->fp);
     sp->fp.store = store;
     sp->ran_period = &m_stripRan;
     const int32_t *tab = (const int32_t *)m_stripTab.ptr;
@@ -1216,36 +1235,29 @@ bool CHipVideoProcessor::FillStripParams(const uint8_t *sample, void *dst, int d
     sp->nt = m_stripPlan.nt; sp->pxl = m_stripPlan.pxl; sp->strip_w = m_stripPlan.strip_w; sp->ring = m_stripPlan.ring; sp->acols = m_stripPlan.acols;
     sp->per_P = 0;
     if (m_periodPlan.P && !(m_cfg.flags & MPCVR_FLAG_NO_PERIOD)) {
-        sp->per_P = m_periodPlan.P; sp->per_Q = m_periodPlan.Q; sp->per_nt = m_periodPlan.nt; sp->per_acols = m_periodPlan.acols; sp->per_strip_w = m_periodPlan.strip_w; sp->per_own = m_periodPlan.own; sp->per_force = (m_cfg.flags & MPCVR_FLAG_FORCE_PERIOD) ? 1 : 0;
+        sp->per_P = m_periodPlan.P; sp->per_Q = m_periodPlan.Q; sp->per_nt = m_periodPlan.nt; sp->per_acols = m_periodPlan.acols; sp->per_strip_w = m_periodPlan.strip_w; sp->per_own = m_periodPlan.own; sp->per_force = perForce;
         sp->per_xi_t = tab + m_periodOff[0]; sp->per_xw_t = tab + m_periodOff[1]; sp->per_yw = tab + m_periodOff[2]; sp->per_xstrip = tab + m_periodOff[3];
     }
     return FusedStripSupported(*sp) && FusedStripLdsBytes(*sp) <= DeviceLdsLimit();
+}
+
+// parameters of the arbitrary-ratio fused kernel for one launch; false: this launch cannot take it (alignment, sizes)
+bool CHipVideoProcessor::FillStripParams(const uint8_t *sample, void *dst, int dstPitch, const StoreParams &store, FusedStripParams *sp) const
+{
+    FillFusedParams(sample, dst, dstPitch, &sp->fp);
+    return FillStripTables(store, (m_cfg.flags & MPCVR_FLAG_FORCE_PERIOD) ? 1 : 0, sp);
 }
 
 // the same kernel without its convert stage: `src` = m_TexConvertOutput (any convert kernel wrote it) or the RGB source texture
 bool CHipVideoProcessor::FillStripSurfParams(const Surface &src, const StoreParams &store, FusedStripParams *sp) const
 {
     *sp = FusedStripParams{};
-    sp->fp.store = store;
-    sp->ran_period = &m_stripRan;
     sp->fp.dst_aligned16 = (((uintptr_t)store.dst) & 15) == 0;      // (batches: the caller knows every target of the table and overrides it)
-    const int32_t *tab = (const int32_t *)m_stripTab.ptr;
-    sp->yrange = tab + m_stripOff[0]; sp->xstrip = tab + m_stripOff[1];
-    sp->xi_t = tab + m_stripOff[2]; sp->xw_t = tab + m_stripOff[3];
-    sp->yi = tab + m_stripOff[4]; sp->yw = tab + m_stripOff[5];
-    sp->out_w = m_videoRect.Width(); sp->out_h = m_videoRect.Height();
-    sp->nt = m_stripPlan.nt; sp->pxl = m_stripPlan.pxl;
-    sp->strip_w = m_stripPlan.strip_w; sp->ring = m_stripPlan.ring; sp->acols = m_stripPlan.acols;
     sp->surface_mode = 1;
     sp->surf = src;
     sp->other = m_otherX.ptr && !m_tapsX.other_identity ? (const int32_t *)m_otherX.ptr : nullptr;
     sp->mid_h = m_plan.mid_h;
-    sp->per_P = 0;
-    if (m_periodPlan.P && !(m_cfg.flags & MPCVR_FLAG_NO_PERIOD)) {      // periodic vertical ratio: the register-window kernel reads the surface as well
-        sp->per_P = m_periodPlan.P; sp->per_Q = m_periodPlan.Q; sp->per_nt = m_periodPlan.nt; sp->per_acols = m_periodPlan.acols; sp->per_strip_w = m_periodPlan.strip_w; sp->per_own = m_periodPlan.own; sp->per_force = 1;
-        sp->per_xi_t = tab + m_periodOff[0]; sp->per_xw_t = tab + m_periodOff[1]; sp->per_yw = tab + m_periodOff[2]; sp->per_xstrip = tab + m_periodOff[3];
-    }
-    return FusedStripSupported(*sp) && FusedStripLdsBytes(*sp) <= DeviceLdsLimit();
+    return FillStripTables(store, 1, sp);      // (per_force: with a periodic vertical ratio the register-window kernel reads the surface as well)
 }
 
 HRESULT CHipVideoProcessor::ProcessOne(const uint8_t *sample, void *rt, int rtPitch)
@@ -1280,7 +1292,7 @@ HRESULT CHipVideoProcessor::ProcessOne(const uint8_t *sample, void *rt, int rtPi
         return CheckHip(LaunchConvertDirect(P, MakeStore(rt, rtPitch, m_plan.swap_fmt, true), m_run), "k_convert_direct");
     }
     if (m_plan.convert && (hr = ConvertColorPass(sample))) return hr;
-    return ResizeShaderPass(rt, rtPitch, sample);
+    return ResizeShaderPass(sample, rt, rtPitch, DrawFrames{m_runConv, m_runMid, m_runPost});
 }
 
 // Process — DX11VideoProcessor.cpp:3285-3424
@@ -1715,20 +1727,15 @@ bool CHipVideoProcessor::BatchPlan(const uint8_t *sample0, void *rt0, int rtPitc
     // with the HDR10 tone-mapping step (:3359-3367) the draws go into the frames' post-scale textures (m_batchPost, internal format)
     // and one tone-mapping launch writes the render targets; without a resize the step reads the convert outputs
     if (!m_plan.two_pass && !m_plan.one_pass && !m_plan.hdr_tonemap) return false;
-    const int convPitch = (int)(m_srcRectWidth * SurfBytesPerPixel(m_plan.internal_fmt));
-    FillFusedParams(sample0, nullptr, convPitch, conv);
-    conv->store = MakeStore(nullptr, convPitch, m_plan.internal_fmt, false);
-    conv->dst_aligned16 = 1;
+    *conv = ConvertOutputParams(sample0, nullptr);
     conv->src_aligned16 = src16 ? 1 : 0;
-    conv->exact_convert = 1;
-    return ConvertBlocksSupported(*conv, false);     // the draws: ProcessBatchLaunches picks the kernel per chunk exactly as ResizeShaderPass does per frame
+    return ConvertBlocksSupported(*conv, false);
 }
 
 // convert all -> first draw all -> second draw all, a frame dimension in every grid; the intermediates hold `chunk` frames
 HRESULT CHipVideoProcessor::ProcessBatchLaunches(int n, const FusedFrame *table, void *rt0, int rtPitch, bool aligned, FusedParams conv)
 {
     HRESULT hr;
-    const int w1 = m_srcRectWidth, h1 = m_srcRectHeight, w2 = m_videoRect.Width(), h2 = m_videoRect.Height();
     // intermediates for up to `chunk` frames (at most ~4 GiB)
     const bool hdr = m_plan.hdr_tonemap;
     const size_t postStride = hdr ? PostStride() : 0;
@@ -1737,59 +1744,25 @@ HRESULT CHipVideoProcessor::ProcessBatchLaunches(int n, const FusedFrame *table,
     if ((hr = CheckHip(m_batchConv.CheckCreate(m_convBytes * chunk), "batch convert output"))) return hr;
     if (m_midBytes && (hr = CheckHip(m_batchMid.CheckCreate(m_midBytes * chunk), "batch resize texture"))) return hr;
     if (hdr && (hr = CheckHip(m_batchPost.CheckCreate(postStride * chunk), "batch post-scale textures"))) return hr;
-    const int convPitch = (int)(w1 * SurfBytesPerPixel(m_plan.internal_fmt));
-    const Surface cs{m_batchConv.ptr, convPitch, w1, h1, m_plan.internal_fmt};
-    const StoreParams target = MakeStore(rt0, rtPitch, m_plan.swap_fmt, true);
+    DrawFrames df{m_batchConv.ptr, m_batchMid.ptr, m_batchPost.ptr, m_convBytes, m_midBytes, postStride};
     // HDR10 tone-mapping step: the draws write frame z's post-scale texture (a second frame table whose targets are the slots of
     // m_batchPost), then ONE k_hdr10_tonemap launch per chunk writes the render targets (:3359-3367)
-    const Surface post{m_batchPost.ptr, (int)(w2 * SurfBytesPerPixel(m_plan.internal_fmt)), w2, h2, m_plan.internal_fmt};
-    const StoreParams final = hdr ? MakeStore(post.ptr, post.pitch, m_plan.internal_fmt, false) : target;
-    const FusedFrame *postTab = nullptr;
     hipEvent_t postDone = nullptr;
     if (hdr) {
-        if ((hr = UploadFrameTable(chunk, nullptr, nullptr, (uint8_t *)m_batchPost.ptr, postStride, &postTab, &postDone))) return hr;
+        if ((hr = UploadFrameTable(chunk, nullptr, nullptr, (uint8_t *)m_batchPost.ptr, postStride, &df.lastTab, &postDone))) return hr;
         aligned = true;             // the slots of m_batchPost start on 256-byte boundaries
     }
-    const bool drawn = m_plan.two_pass || m_plan.one_pass;
+    df.aligned = aligned ? 1 : 0;
     for (int at = 0; at < n; at += chunk) {
         const int m = std::min(chunk, n - at);
-        const FusedFrame *tab = hdr ? postTab : table + at;
         // frame z of the chunk: sample from the table, output at m_batchConv + z * m_convBytes
         conv.store.dst = m_batchConv.ptr;
         if (m_dvTabDev) { conv.conv.dovi = m_dvTabDev + at; conv.dovi_cm = m_dvCmDev + (size_t)12 * at; }       // (the chunk's slice of the per-frame RPU tables)
         if ((hr = CheckHip(LaunchConvertBlocks(conv, table + at, FusedFrame{nullptr, nullptr}, m, m_stream, m_convBytes), "k_convert_blocks"))) return hr;
-        // the draws, kernel by kernel as ResizeShaderPass picks them for one frame (default tier), each with the chunk as its frame dimension
-        ResizeBatch b1; b1.n = m; b1.in_stride = m_convBytes;
-        FusedStripParams ssp{};
-        if (m_stripSurf && FillStripSurfParams(cs, final, &ssp)) {
-            ssp.surf_stride = m_convBytes;
-            ssp.fp.dst_aligned16 = aligned ? 1 : 0;
-            if ((hr = CheckHip(LaunchFusedStrip(ssp, tab, FusedFrame{nullptr, nullptr}, m, m_stream), "k_fused_strip<surface>"))) return hr;
-        } else if (m_plan.two_pass && !m_firstJinc && !m_secondJinc && m_firstAxis == 0 && !m_firstSwap && Resize2DSupported(cs, m_tapsX, m_tapsY, final)) {
-            b1.frames = tab;
-            if ((hr = CheckHip(LaunchResize2D(cs, m_tapsX, m_tapsY, (const int32_t *)m_otherX.ptr, m_plan.mid_h, w2, h2, final, m_stream, &b1), "k_resize_2d"))) return hr;
-        } else if (m_plan.two_pass) {
-            const Surface mid{m_batchMid.ptr, w2 * 8, w2, m_plan.mid_h, SF_RGBA16F};
-            b1.dst_stride = m_midBytes;
-            const StoreParams st = MakeStore(mid.ptr, mid.pitch, SF_RGBA16F, false);
-            if (m_firstJinc) hr = CheckHip(LaunchJinc2(cs, m_firstCoords, w2, m_plan.mid_h, st, m_stream, m_jincFirstTab, true, &b1, m_jincFirstCtr), "k_jinc2");
-            else hr = CheckHip(LaunchResize(m_firstAxis, m_firstSwap, cs, m_tapsX, (const int32_t *)m_otherX.ptr, w2, m_plan.mid_h, st, m_stream, false, &b1), "k_resize<first>");
-            if (hr) return hr;
-            ResizeBatch b2; b2.n = m; b2.in_stride = m_midBytes; b2.frames = tab; b2.dst_aligned8 = aligned ? 1 : 0;
-            if (m_secondJinc) hr = CheckHip(LaunchJinc2(mid, m_secondCoords, w2, h2, final, m_stream, m_jincSecondTab, true, &b2, m_jincSecondCtr), "k_jinc2");
-            else hr = CheckHip(LaunchResize(1, false, mid, m_tapsY, (const int32_t *)m_otherY.ptr, w2, h2, final, m_stream, false, &b2), "k_resize<Y>");
-            if (hr) return hr;
-        } else if (m_firstJinc) {
-            b1.frames = tab; b1.dst_aligned8 = aligned ? 1 : 0;
-            if ((hr = CheckHip(LaunchJinc2(cs, m_firstCoords, w2, h2, final, m_stream, m_jincFirstTab, true, &b1, m_jincFirstCtr), "k_jinc2"))) return hr;
-        } else if (drawn) {
-            b1.frames = tab;
-            if ((hr = CheckHip(LaunchResize(m_firstAxis, m_firstSwap, cs, m_tapsX, (const int32_t *)m_otherX.ptr, w2, h2, final, m_stream, false, &b1), "k_resize<one>"))) return hr;
-        }
-        if (hdr) {
-            ResizeBatch tb; tb.n = m; tb.in_stride = drawn ? postStride : m_convBytes; tb.frames = table + at;
-            if ((hr = CheckHip(LaunchHdr10ToneMap(drawn ? post : cs, m_hdrTm, w2, h2, target, m_stream, &tb), "k_hdr10_tonemap"))) return hr;
-        }
+        df.n = m;
+        df.rtTab = table + at;
+        if (!hdr) df.lastTab = df.rtTab;
+        if ((hr = ResizeShaderPass(nullptr, rt0, rtPitch, df))) return hr;
     }
     if (postDone) (void)hipEventRecord(postDone, m_stream);
     return MPCVR_S_OK;

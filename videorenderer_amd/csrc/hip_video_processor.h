@@ -97,7 +97,18 @@ private:
     void SetShaderLuminanceParams();                     // :889
     HRESULT UpdatePlan();                                // UpdateTexures/UpdatePostScaleTexures/Update*scalingShaders
     HRESULT ConvertColorPass(const uint8_t *sample);     // :3048
-    HRESULT ResizeShaderPass(void *rt, int rtPitch, const uint8_t *sample);     // :3103 (+ FinalPass :3189 fused into the last draw)
+    FusedParams ConvertOutputParams(const uint8_t *sample, void *out) const;          // the block convert into m_TexConvertOutput
+    // what ResizeShaderPass draws through, frame z of each surface at its pointer + z * its stride: one frame (the m_run* surfaces, no
+    // tables, zero strides — what every launcher takes a null ResizeBatch for) or a chunk of a batch (ProcessBatchLaunches)
+    struct DrawFrames {
+        void *conv = nullptr, *mid = nullptr, *post = nullptr;     // m_TexConvertOutput, m_TexResize, the post-scale texture
+        size_t convStride = 0, midStride = 0, postStride = 0;
+        int n = 1;
+        const FusedFrame *lastTab = nullptr;   // the last draw's targets: the render targets, or the post-scale slots with the HDR10 step
+        const FusedFrame *rtTab = nullptr;     // the HDR10 step's render targets
+        int aligned = 1;                       // with a table: every lastTab target on a 16-byte boundary (one frame: its target's address decides)
+    };
+    HRESULT ResizeShaderPass(const uint8_t *sample, void *rt, int rtPitch, const DrawFrames &df);     // :3103 (+ FinalPass :3189 fused into the last draw)
     HRESULT ProcessOne(const uint8_t *sample, void *rt, int rtPitch);
     HRESULT UploadTaps(const HostAxisTaps &h, DevBuffer &bi, DevBuffer &bw, DevBuffer &bs, DevBuffer &bb, const std::vector<int32_t> &other, AxisTaps *out);
     HRESULT UploadIndex(const std::vector<int32_t> &v, DevBuffer &b);
@@ -323,6 +334,7 @@ private:
     DevBuffer m_stripTab;          // yrange | xstrip | xi_t | xw_t | yi | yw, word offsets in m_stripOff
     size_t m_stripOff[6] = {0, 0, 0, 0, 0, 0};
     bool FillStripParams(const uint8_t *sample, void *dst, int dstPitch, const StoreParams &store, FusedStripParams *sp) const;
+    bool FillStripTables(const StoreParams &store, int perForce, FusedStripParams *sp) const;     // what the two above share
     // periodic-phase variant of the same launch (vp_fused_period.h): vertical ratio 4:3 / 3:2 / 2:3 / 1:2 / 3:1, tables behind the strip kernel's in m_stripTab
     PeriodPlan m_periodPlan;       // P == 0: not a periodic geometry
     mutable int m_stripRan = -1;   // which kernel the last strip launch of this plan really ran (1 = k_fused_period, 0 = k_fused_strip, -1 = none yet): the plan-time
