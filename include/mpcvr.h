@@ -267,14 +267,20 @@ int32_t mpcvr_copy_sample(mpcvr_ctx *ctx, const void *data, int32_t pitch, int32
 /* Process — DX11VideoProcessor.cpp:3285-3424.  dst: DEVICE pointer to a window_w x window_h render
  * target, 4 bytes per pixel (B8G8R8A8 or R10G10B10A2), dst_pitch bytes per row.  src_rect must be
  * NULL or the input's source rect (the reference overrides it with the convert texture, :3316-3319);
- * dst_rect NULL => the context's video rect.  Pixels outside dst_rect are not written. */
+ * dst_rect NULL => the context's video rect.  Pixels outside dst_rect are not written, and neither is any byte outside the
+ * window's pixels: the bytes between window_w * 4 and dst_pitch of a row, and everything in front of and behind the target.
+ * A render target is made of dwords: dst_dev and dst_pitch must be multiples of 4 (any multiple: a sub-allocated, pitch-padded
+ * surface is served; the 8- and 16-byte stores are taken where target and pitch allow them).  MPCVR_E_INVALIDARG otherwise, with
+ * nothing launched and the target untouched.  The same holds for every dsts[i] / dst_pitch of mpcvr_process_frames,
+ * mpcvr_process_batch and mpcvr_process_batch_dovi. */
 int32_t mpcvr_process(mpcvr_ctx *ctx, void *dst_dev, int32_t dst_pitch, const mpcvr_rect *src_rect,
                       const mpcvr_rect *dst_rect, int32_t second_field);
 
 /* n frames the reference's way — mpcvr_copy_sample(samples[i], pitch, mem_kind) then mpcvr_process(dsts_dev[i], dst_pitch, NULL, NULL, 0), frame
  * after frame (ProcessSample -> CopySample -> Render -> Process, DX11VideoProcessor.cpp:2143-2200, :2730) — behind one call, so that a caller
  * in a scripting language measures the path and not its own foreign-function calls.  Not a batch: every frame is its own launch (or lands
- * on the context's frame lanes); stops at the first failure and returns it. */
+ * on the context's frame lanes); stops at the first failure and returns it (a dsts_dev[i] or dst_pitch that is not a multiple of 4:
+ * MPCVR_E_INVALIDARG at that frame, the frames in front of it drawn). */
 int32_t mpcvr_process_frames(mpcvr_ctx *ctx, int32_t n, const void *const *samples, int32_t pitch, int32_t mem_kind, void *const *dsts_dev, int32_t dst_pitch);
 
 /* Render minus Present — DX11VideoProcessor.cpp:2599-2813: Process into the context-owned back buffer. */
@@ -300,7 +306,8 @@ int32_t mpcvr_reset(mpcvr_ctx *ctx);
 
 /* Extension (not in the reference): n frames in one launch sequence to escape the launch-bound
  * regime.  srcs[i]: DEVICE sample pointers (layout/pitch as declared by mpcvr_set_input);
- * dsts[i]: DEVICE render targets (dst_pitch each).
+ * dsts[i]: DEVICE render targets (dst_pitch each; every dsts[i] and dst_pitch a multiple of 4, else MPCVR_E_INVALIDARG and nothing is
+ * drawn — see mpcvr_process.  The targets of one batch may differ in alignment: every frame runs through the stores the worst-aligned allows).
  * The frames of a batch are independent of each other: on every path that can, the whole batch runs as one launch per
  * draw (fused 2x / strip / periodic kernel: one launch; same-size frames: one k_convert_stream launch; pass-per-kernel path:
  * block convert / X draw / Y draw with a frame dimension and batched intermediates, <= 4 GiB; Dolby Vision: the block convert's
@@ -308,15 +315,19 @@ int32_t mpcvr_reset(mpcvr_ctx *ctx);
  * batched post-scale textures; quarter turns, flips outside the strip kernels' reach and Jinc2m in its one- and two-draw forms: every
  * draw kernel has a frame dimension; bUseDither = 2: ONE error-diffusion launch behind the batch's 10-bit frames), otherwise frame by
  * frame (samples that do not start on a dword or need a repack of their own outside the v210 / interleaved-RGB batch textures).
- * mpcvr_get_last_batch_info reports the kernel launches a batch took.  The targets must therefore be distinct buffers; completion is
+ * mpcvr_get_last_batch_info reports the kernel launches a batch took.  The targets of one batch must therefore not overlap in memory; completion is
  * in stream order for the batch as a whole.
  * Round 6: on a context that OWNS its stream (no mpcvr_set_stream) consecutive batches whose plan is one launch with no intermediate
  * surface (exact 2x, the strip / periodic kernel reading the samples, the fused Jinc2m kernel, the same-size block convert; no Dolby Vision,
  * no repack) take turns on two internal lanes, so that two launches are in flight and fill each other's ramp-up and tail (4K -> 8K: +4 %,
  * 1080p -> 1440p: +16 %; MPCVR_NO_BATCH_LANES=1 in the environment turns it off).
- * Batches and single frames that write the same render target (same pointer) stay in the order they were queued; everything that can observe
+ * Batches and single frames that write overlapping memory stay in the order they were queued, whatever pointers they were given: a target
+ * counts as the bytes from its first pixel to the last pixel of its last row, dst_dev .. dst_dev + (window_h - 1) * dst_pitch + window_w * 4
+ * (a window further down in one surface, the same surface from another base; rows of two targets that interleave in one surface count as
+ * overlapping).  Targets that merely touch run side by side.  Everything that can observe
  * a result (mpcvr_synchronize, the snapshot, a plan change, mpcvr_set_stream) waits for the lanes.  MPCVR_FLAG_NO_FRAME_LANES (or a caller's
- * stream) keeps every batch in stream order; mpcvr_get_last_batch_info names the lane ("lane=0|1", -1 = the context stream). */
+ * stream) keeps every batch in stream order; mpcvr_get_last_batch_info names the lane ("lane=0|1", -1 = the context stream) and how many
+ * writers still in flight on other lanes the batch was ordered behind ("waits=<n>"). */
 int32_t mpcvr_process_batch(mpcvr_ctx *ctx, int32_t n, const void *const *srcs, void *const *dsts,
                             int32_t dst_pitch);
 /* mpcvr_process_batch for a Dolby Vision stream: rpus[i] is the RPU of frame i — the reference reads it from every sample in
@@ -327,7 +338,8 @@ int32_t mpcvr_process_batch(mpcvr_ctx *ctx, int32_t n, const void *const *srcs, 
  * run (same-size frames; convert + resize kernels): they read frame z's curves, LMS matrix, trims and ycc_to_rgb matrix from
  * device tables indexed by the frame.  A run behind the HDR10 tone-mapping step (its level-1 constants travel by value), and
  * whatever the per-pixel convert serves, goes frame by frame with each RPU's constants uploaded in stream order.
- * E_INVALIDARG, and nothing drawn, when any RPU of the batch fails the checks of mpcvr_set_dovi_metadata. */
+ * E_INVALIDARG, and nothing drawn, when any RPU of the batch fails the checks of mpcvr_set_dovi_metadata, or when a dsts[i] or
+ * dst_pitch is not a multiple of 4 (see mpcvr_process). */
 int32_t mpcvr_process_batch_dovi(mpcvr_ctx *ctx, int32_t n, const void *const *srcs, void *const *dsts,
                                  int32_t dst_pitch, const mpcvr_dovi_metadata *rpus);
 
@@ -353,7 +365,7 @@ int32_t mpcvr_get_color_matrix(mpcvr_ctx *ctx, float out12[12]);     /* cm_r, cm
 int32_t mpcvr_get_extfmt(mpcvr_ctx *ctx, uint32_t *extfmt);           /* after SpecifyExtendedFormat */
 int32_t mpcvr_get_frame_bytes(mpcvr_ctx *ctx, size_t *bytes, int32_t *pitch);
 int32_t mpcvr_get_path_info(mpcvr_ctx *ctx, char *buf, size_t buf_size); /* e.g. "fused_up2x" / "fused_jinc2x" / "passes:convert,resizeX,resizeY+final" */
-/* How the last mpcvr_process_batch / mpcvr_process_batch_dovi call ran: "frames=<n>;launches=<kernel launches>[;dovi_runs=<frames>:<tables|frames>,...]".
+/* How the last mpcvr_process_batch / mpcvr_process_batch_dovi call ran: "frames=<n>;launches=<kernel launches>;lane=<lane>;waits=<n>[;dovi_runs=<frames>:<tables|frames>,...]".
  * A batch on a whole-batch route launches a handful of kernels whatever n is (one per stage and <= 4 GiB chunk of intermediates); a
  * frame-by-frame one at least n.  dovi_runs: the runs mpcvr_process_batch_dovi cut the frames into and whether a run read its RPUs from the
  * per-frame tables or went frame by frame. */

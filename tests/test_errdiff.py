@@ -130,11 +130,15 @@ def region(c):
 
 
 def product_10bit_and_diffused(mpcvr, torch, c, flags=0):
-    """The product twice on the same sample: as the 10-bit swap chain (what the pass reads) and with bUseDither = 2."""
-    from tests.test_parity_gpu import run_product
+    """The product on the same sample: as the 10-bit swap chain (what the pass reads) and with bUseDither = 2 into every render-target layout
+    (tests.test_parity_gpu.run_layouts: a target carved out of a patterned buffer, every byte outside the window pixels checked) ->
+    (10-bit frame, {layout: diffused frame}, GetVPInfo of the two)."""
+    from tests.test_parity_gpu import run_layouts, run_product
     ten, info10 = run_product(mpcvr, torch, dict(c, bUseDither=2, output_format=1), flags)
-    out, info = run_product(mpcvr, torch, dict(c, bUseDither=2), flags)
-    return ten.view(np.uint32)[:, :, 0], out, info10, info
+    outs = run_layouts(mpcvr, torch, dict(c, bUseDither=2), flags, what="error diffusion")
+    infos = {v[1] for v in outs.values()}
+    assert len(infos) == 1, infos
+    return ten.view(np.uint32)[:, :, 0], {k: v[0] for k, v in outs.items()}, info10, infos.pop()
 
 
 ED_CASES = {
@@ -161,11 +165,14 @@ ED_CASES = {
 def test_kernel_equals_serial_model_on_the_products_10_bit_frame(mpcvr, oracle, name):
     import torch
     c = ED_CASES[name]
-    ten, out, info10, info = product_10bit_and_diffused(mpcvr, torch, c)
+    ten, outs, info10, info = product_10bit_and_diffused(mpcvr, torch, c)
     assert "errdiff" in info and "errdiff" not in info10, (info10, info)
     rect, (ww, wh) = region(c)
     want = oracle.error_diffusion(ten, rect, dst=np.full((wh, ww, 4), BG, dtype=np.uint8))
-    assert np.array_equal(out, want), f"{name} [{info}]: {(out != want).any(axis=2).sum()} pixels differ"
+    # the pass writes through dst_pitch: every render-target layout holds the serial model's frame, the background inside the window included
+    # (the bytes outside the window pixels: product_10bit_and_diffused)
+    for layout, out in outs.items():
+        assert np.array_equal(out, want), f"{name} <{layout}> [{info}]: {(out != want).any(axis=2).sum()} pixels differ"
 
 
 @pytest.mark.gpu
@@ -213,6 +220,11 @@ def test_batch_equals_single_frames_and_is_one_pass_launch(mpcvr, oracle):
         for i, d in enumerate(dsts):
             assert np.array_equal(d.cpu().numpy(), singles[i]), (name, i)
         assert binfo["frames"] == 5 and binfo["launches"] <= 4, (name, binfo)        # the 10-bit plan's whole-batch launches + ONE pass launch
+        # the targets as slices of one patterned buffer whose first bytes differ in alignment, at `off8`'s and `off4`'s pitch
+        from tests.test_parity_gpu import MIXED_BASES, batch_vs_singles_in_carved_targets, layout_of
+        for layout in ("off8", "off4"):
+            mixed = batch_vs_singles_in_carved_targets(torch, vp, frames, pitch, ww, wh, layout_of(layout, ww)[1], MIXED_BASES[:5], f"error diffusion {name} <{layout}>")
+            assert mixed["frames"] == 5 and mixed["launches"] <= 4, (name, layout, mixed)
         vp.close()
 
 
@@ -222,10 +234,12 @@ def test_full_size_4k_to_8k_equals_serial_model(mpcvr, oracle):
     extension rides the same kernel): 68 bands of 976 groups, one workgroup each."""
     import torch
     c = dict(FULL_SIZE_CASES["c4_mitchell"])
-    ten, out, info10, info = product_10bit_and_diffused(mpcvr, torch, c)
+    ten, outs, info10, info = product_10bit_and_diffused(mpcvr, torch, c)
     want = oracle.error_diffusion(ten, (0, 0, 7680, 4320))
     assert "errdiff" in info
-    assert np.array_equal(out, want), f"{(out != want).any(axis=2).sum()} pixels differ [{info}]"
+    for layout, out in outs.items():         # (every render-target layout: the last band and the right edge at a real width)
+        assert np.array_equal(out, want), f"<{layout}>: {(out != want).any(axis=2).sum()} pixels differ [{info}]"
+    out = outs["off4"]
     k = ((ten >> 0) & 0x3ff).astype(np.float64).mean() * 255 / 1023
     assert abs(out[..., 2].astype(np.float64).mean() - k) < 0.01
 

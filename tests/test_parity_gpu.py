@@ -86,6 +86,122 @@ def run_product(mpcvr, torch, c, extra_flags=0, host_upload=False):
     return out, info
 
 
+# ---- render-target layouts ----------------------------------------------------------------------------------------------------------
+# A host's back buffer is pitch-padded and sub-allocated more often than not.  Every layout draws into a target carved out of a larger device
+# buffer that holds a non-constant byte pattern; the bytes in front of the target, behind it and between window_w * 4 and dst_pitch of every
+# row must still hold the pattern afterwards, bit for bit (include/mpcvr.h: pixels outside dst_rect are not written).
+#   name       first byte (from a 256-byte boundary)   pitch                                              what it reaches
+#   tight      0                                       window_w * 4                                       the layout of a tensor of its own
+#   padded16   0                                       window_w * 4 rounded up to 16, plus 64             the aligned epilogues with other row addresses
+#   off4       4                                       window_w * 4 + 4                                   nothing aligned beyond a pixel: the per-pixel store paths
+#   off8       8                                       a multiple of 8, not of 16, >= window_w * 4 + 8    the 8-byte paths, the 16-byte ones declining
+LAYOUTS = ("tight", "padded16", "off4", "off8")
+
+
+def layout_of(layout, ww):
+    """(distance of the target's first byte from a 256-byte boundary, dst_pitch) of a layout for a window ww pixels wide."""
+    row = ww * 4
+    if layout == "tight":
+        return 0, row
+    if layout == "padded16":
+        return 0, ((row + 15) & ~15) + 64
+    if layout == "off4":
+        return 4, row + 4
+    if layout == "off8":
+        pitch = (row + 8 + 7) & ~7
+        return 8, pitch + 8 if pitch % 16 == 0 else pitch
+    raise KeyError(layout)
+
+
+def kernel_under(layout, expect):
+    """The GetVPInfo fragment a layout is expected to show where `tight` shows `expect`: k_fused_period stores 8 bytes per lane and steps
+    aside for a target or pitch that is not a multiple of 8 (`off4`) — the launch then goes to k_fused_strip, whose epilogue has a per-pixel
+    form; it must step aside, so `off4` is held to the strip kernel's name.  `off8` is all k_fused_period needs and is held to ITS name:
+    these layouts found single frames into an 8-byte-aligned target losing the kernel to a flag that asked for 16 bytes (batches never did)."""
+    if layout == "off4" and "fused_period" in expect:
+        return expect.split("(")[0].replace("fused_period", "fused_strip") + "("
+    return expect
+
+
+class CarvedTargets:
+    """n render targets of ww x wh pixels, `pitch` bytes per row, inside ONE patterned device buffer: target i starts bases[i] bytes behind a
+    256-byte boundary; a guard band of one row of `pitch` plus 4 KiB (a wave's worth of 16-byte stores is 1 KiB) lies in front of the first,
+    between any two and behind the last.  Window pixels start as BG."""
+
+    def __init__(self, torch, ww, wh, pitch, bases):
+        self.torch, self.ww, self.wh, self.pitch = torch, ww, wh, pitch
+        guard = pitch + 4096
+        self.starts = []
+        at = 0
+        for b in bases:
+            at = (at + guard + 255) // 256 * 256 + b
+            self.starts.append(at)
+            at += wh * pitch                      # (the last row's padding belongs to the target's rows: checked like every row's)
+        total = at + guard
+        i = torch.arange(total, dtype=torch.int32, device="cuda") & 255
+        self.pattern = ((i * 131 + 17) & 255).to(torch.uint8)
+        del i
+        self.buf = self.pattern.clone()
+        assert self.buf.data_ptr() % 256 == 0
+        for s in self.starts:
+            self._window(self.buf, s).fill_(BG)
+        self.ptrs = [self.buf.data_ptr() + s for s in self.starts]
+
+    def _window(self, t, start):
+        return t.as_strided((self.wh, self.ww * 4), (self.pitch, 1), start)
+
+    def window(self, i):
+        """the pixels of target i as a (wh, ww, 4) view of the buffer (device)"""
+        return self.buf.as_strided((self.wh, self.ww, 4), (self.pitch, 4, 1), self.starts[i])
+
+    def pixels(self, i=0):
+        return self.window(i).contiguous().cpu().numpy()
+
+    def assert_guards_intact(self, what):
+        """every byte that is not a window pixel equals the pattern (call after Synchronize; the pixels are read with pixels() / window())"""
+        torch = self.torch
+        rest = self.buf.clone()
+        for s in self.starts:
+            self._window(rest, s).copy_(self._window(self.pattern, s))
+        if torch.equal(rest, self.pattern):
+            return
+        off = int(torch.nonzero(rest != self.pattern)[0])
+        n_bad = int((rest != self.pattern).sum())
+        where = f"{self.starts[0] - off} bytes in front of target 0"
+        for k, s in enumerate(self.starts):
+            if off >= s:
+                r, x = divmod(off - s, self.pitch)
+                where = (f"target {k}: row {r}, byte {x} of the row (pixels end at {self.ww * 4}, pitch {self.pitch})" if r < self.wh
+                         else f"{off - s - self.wh * self.pitch} bytes behind the last row of target {k}")
+        raise AssertionError(f"{what}: {n_bad} byte(s) outside the window pixels were written; the first is {where}: "
+                             f"{int(rest[off])} where the pattern holds {int(self.pattern[off])}")
+
+
+def run_layouts(mpcvr, torch, c, extra_flags=0, layouts=LAYOUTS, what=""):
+    """One context, one sample, the case drawn once per layout: {layout: (pixels, GetVPInfo)}, the guard and padding bytes of every layout
+    checked.  `padded16` runs the kernel variant `tight` runs wherever window_w * 4 is a multiple of 16 (only the row addresses differ), so
+    it must then leave the same bytes."""
+    vp, (ww, wh) = make_vp(mpcvr, c, extra_flags)
+    frame, pitch = case_frame(c)
+    assert vp.GetFrameBytes() == (frame.size, abs(pitch))
+    dev = torch.from_numpy(frame).cuda()
+    outs = {}
+    for layout in layouts:
+        base, dst_pitch = layout_of(layout, ww)
+        t = CarvedTargets(torch, ww, wh, dst_pitch, [base])
+        vp.CopySample(dev, pitch)
+        vp.Process(t.ptrs[0], dst_pitch)
+        vp.Synchronize()
+        info = vp.GetVPInfo()
+        t.assert_guards_intact(f"{what or c.get('name', '')} layout {layout} (first byte at +{base}, pitch {dst_pitch}) [{info}]")
+        outs[layout] = (t.pixels(), info)
+    vp.close()
+    if "tight" in outs and "padded16" in outs and (ww * 4) % 16 == 0:
+        assert outs["tight"][1] == outs["padded16"][1], (what, outs["tight"][1], outs["padded16"][1])
+        assert np.array_equal(outs["tight"][0], outs["padded16"][0]), f"{what}: a padded pitch changed the pixels [{outs['tight'][1]}]"
+    return outs
+
+
 # whole frames (>= 0.4 M pixels): the smallest share of identical channels measured over every such comparison of the suite is 0.99922
 # (profiles/r03/parity_identical_channels.jsonl, MPCVR_PARITY_LOG); the floor is 1 - 2 x (1 - that): twice today's worst fails
 WHOLE_FRAME_FLOOR = 0.9984
@@ -234,14 +350,15 @@ def test_pass_per_kernel_path_vs_oracle(mpcvr, oracle, torch_cuda, name):
     from videorenderer_amd import api
     c = GOLDEN_CASES[name]
     want = run_case(oracle, name, background=BG)
-    got, info = run_product(mpcvr, torch_cuda, c, extra_flags=api.FLAG_NO_FUSED)
-    assert info.startswith("passes:"), info
-    # bit-exact, behind a PQ / HLG / gamma / Dolby Vision tail too (round 6: the tier evaluates the transcendentals as the oracle defines
-    # them — csrc/vp_crmath.h — where until round 5 v_log_f32 / v_exp_f32 left tails at "<= 1 LSB, >= 99.5 % identical")
-    if c.get("output_format", 0) == 1:
-        compare_rgb10(got, want, name, exact=True)
-    else:
-        compare(got, want, name, exact=True)
+    # (every render-target layout: the oracle's frame once, the product's once per layout, guard and padding bytes checked by run_layouts)
+    for layout, (got, info) in run_layouts(mpcvr, torch_cuda, c, extra_flags=api.FLAG_NO_FUSED, what=name).items():
+        assert info.startswith("passes:"), info
+        # bit-exact, behind a PQ / HLG / gamma / Dolby Vision tail too (round 6: the tier evaluates the transcendentals as the oracle defines
+        # them — csrc/vp_crmath.h — where until round 5 v_log_f32 / v_exp_f32 left tails at "<= 1 LSB, >= 99.5 % identical")
+        if c.get("output_format", 0) == 1:
+            compare_rgb10(got, want, f"{name} <{layout}>", exact=True)
+        else:
+            compare(got, want, f"{name} <{layout}>", exact=True)
 
 
 ADAPTER_DRIVER = os.path.join(os.path.dirname(HERE), "oracle", "_ref", "adapter_driver")
@@ -665,12 +782,12 @@ def test_default_path_vs_oracle(mpcvr, oracle, torch_cuda, name):
     everything that does not run the fused kernel or a transcendental tail stays bit-exact."""
     c = GOLDEN_CASES[name]
     want = run_case(oracle, name, background=BG)
-    got, info = run_product(mpcvr, torch_cuda, c)
-    # 4:2:0 sources may go through the fused kernel or its block convert (FMA contraction, scale folded into the matrix)
-    if c.get("output_format", 0) == 1:
-        compare_rgb10(got, want, name, tail=has_tail(c), internal8=internal_is_8bit(c))
-    else:
-        compare(got, want, f"{name} [{info}]", min_same=0.99)
+    for layout, (got, info) in run_layouts(mpcvr, torch_cuda, c, what=name).items():
+        # 4:2:0 sources may go through the fused kernel or its block convert (FMA contraction, scale folded into the matrix)
+        if c.get("output_format", 0) == 1:
+            compare_rgb10(got, want, f"{name} <{layout}>", tail=has_tail(c), internal8=internal_is_8bit(c))
+        else:
+            compare(got, want, f"{name} <{layout}> [{info}]", min_same=0.99)
 
 
 @pytest.mark.parametrize("name", sorted(GOLDEN_CASES))
@@ -872,20 +989,21 @@ def test_kernel_family_sweep_vs_oracle(mpcvr, oracle, torch_cuda, label):
     p = oracle_params(oracle, c)
     frame, pitch = case_frame(c)
     want = oracle.process(p, frame, pitch, dst=np.full((p.window_h, p.window_w, 4), BG, dtype=np.uint8))
-    got, info = run_product(mpcvr, torch_cuda, c, extra_flags=flags)
     # noise frames of a few thousand pixels: with an 8-bit internal format one code of the texture is four ten-bit codes of the target,
     # so the share of identical channels is held at 0.97 there (0.99 elsewhere); behind a PQ / HLG tail a channel beyond the bar needs
     # its witness (compare_behind_tail: inside the oracle's own +-4 ulp pow() interval), at most one per frame (round 6: what was measured)
     same_floor = 0.97 if internal_is_8bit(c) else 0.99
-    if has_tail(c):
-        ten = c["output_format"] == 1
-        compare_behind_tail(oracle, p, frame, pitch, got, want, f"{label} [{info}]", min_same=same_floor, ten_bit=ten,
-                            lim=(5 if internal_is_8bit(c) else 2) if ten else 1, cap=1)       # (measured, round 6: 1 on two of the 2,975 cases)
-    elif c["output_format"] == 1:
-        # (Jinc2m: a one-code difference of the block convert in the 10-bit texture may come out as two ten-bit codes = half an 8-bit code)
-        compare_rgb10(got, want, f"{label} [{info}]", tail=c.get("iUpscaling") == 5, internal8=internal_is_8bit(c), min_same=same_floor)
-    else:
-        compare(got, want, f"{label} [{info}]", min_same=same_floor)
+    # every render-target layout on every case (the oracle's frame once; run_layouts checks the bytes around the pixels)
+    for layout, (got, info) in run_layouts(mpcvr, torch_cuda, c, extra_flags=flags, what=label).items():
+        if has_tail(c):
+            ten = c["output_format"] == 1
+            compare_behind_tail(oracle, p, frame, pitch, got, want, f"{label} <{layout}> [{info}]", min_same=same_floor, ten_bit=ten,
+                                lim=(5 if internal_is_8bit(c) else 2) if ten else 1, cap=1)       # (measured, round 6: 1 on two of the 2,975 cases)
+        elif c["output_format"] == 1:
+            # (Jinc2m: a one-code difference of the block convert in the 10-bit texture may come out as two ten-bit codes = half an 8-bit code)
+            compare_rgb10(got, want, f"{label} <{layout}> [{info}]", tail=c.get("iUpscaling") == 5, internal8=internal_is_8bit(c), min_same=same_floor)
+        else:
+            compare(got, want, f"{label} <{layout}> [{info}]", min_same=same_floor)
 
 
 def _is_same_size(c):
@@ -999,6 +1117,40 @@ def test_get_current_image_and_render(mpcvr, oracle, torch_cuda):
 # batches that go frame by frame by design (everything else in test_process_batch_equals_single must take a whole-batch route)
 # — the fp16 internal format (a user-forced setting): its convert is the per-pixel kernel, which has no frame dimension
 BATCH_FRAME_BY_FRAME = ("hdrout_tm6_st2094_hlg_fp16",)
+# the first bytes of a batch's targets inside one buffer, from 256-byte boundaries: target 0 on the boundary, target 1 at +8, target 2 at +4, the rest alternate
+MIXED_BASES = (0, 8, 4, 8, 4, 8, 4, 8)
+
+
+def batch_vs_singles_in_carved_targets(torch, vp, frames, src_pitch, ww, wh, dst_pitch, bases, what):
+    """mpcvr_process_batch into targets that are slices of ONE patterned buffer (guard bytes in front, between and behind; first bytes at
+    `bases` from 256-byte boundaries, one pitch) against the same frames drawn one by one.  A whole-batch launch is planned from the batch's
+    first target and runs EVERY frame through the kernel and stores its worst-aligned target allows (a target at +4 sends the whole launch
+    from k_fused_period to k_fused_strip, say — two kernels that are held to one code of each other, not to the same bytes), so its frames
+    are compared with single frames drawn at that worst alignment.  A batch that declines to frame by frame (GetLastBatchInfo: a launch
+    per frame or more) draws every frame as a single one, with the kernel ITS target allows: those are compared with single frames
+    drawn into the same first bytes.  Either way each target must hold its single frame's bytes, and every byte outside the window pixels
+    the pattern.  Returns GetLastBatchInfo()."""
+    assert len(bases) == len(frames)
+    worst = min(bases, key=lambda b: (b & -b) if b else 256)
+    alone = {}
+    for how, at in (("worst", [worst] * len(frames)), ("own", list(bases))):
+        alone[how] = CarvedTargets(torch, ww, wh, dst_pitch, at)
+        for f, ptr in zip(frames, alone[how].ptrs):
+            vp.CopySample(f, src_pitch)
+            vp.Process(ptr, dst_pitch)
+        vp.Synchronize()
+        alone[how].assert_guards_intact(f"{what}: single frames at {at}, pitch {dst_pitch} [{vp.GetVPInfo()}]")
+    batch = CarvedTargets(torch, ww, wh, dst_pitch, list(bases))
+    vp.ProcessBatch(frames, batch.ptrs, dst_pitch)
+    vp.Synchronize()
+    info = vp.GetLastBatchInfo()
+    batch.assert_guards_intact(f"{what}: batch into targets at {list(bases)}, pitch {dst_pitch} [{vp.GetVPInfo()}; {info}]")
+    how = "own" if info["launches"] >= len(frames) else "worst"
+    for i in range(len(frames)):
+        assert torch.equal(batch.window(i), alone[how].window(i)), (f"{what}: frame {i} of the batch (target at +{bases[i]}, pitch {dst_pitch}) differs from the frame drawn "
+                                                                    f"alone at +{worst if how == 'worst' else bases[i]} [{vp.GetVPInfo()}; {info}]")
+    assert not bool((batch.window(0) == BG).all()), what
+    return info
 
 
 def test_process_batch_equals_single(mpcvr, torch_cuda):
@@ -1057,6 +1209,10 @@ def test_process_batch_equals_single(mpcvr, torch_cuda):
         vp.Synchronize()
         for i in range(3):
             assert torch.equal(singles[2 + i], dsts[i]), (name, flags, "second batch", i)
+        # the targets as slices of one patterned buffer with mixed first bytes: `off8`'s pitch, then `off4`'s (same route: the launch count stays)
+        for layout in ("off8", "off4"):
+            mixed = batch_vs_singles_in_carved_targets(torch, vp, frames, pitch, ww, wh, layout_of(layout, ww)[1], MIXED_BASES[:5], f"{name} flags={flags} <{layout}>")
+            assert mixed["frames"] == 5, (name, flags, layout, route, mixed)
         vp.close()
     assert sorted(n for n, _, _, _ in by_frame) == sorted(BATCH_FRAME_BY_FRAME), by_frame
 
@@ -1363,6 +1519,43 @@ def test_error_behaviour(mpcvr, torch_cuda):
     assert hr_of(lambda: vp.Configure(vp.settings.copy(iSDRDisplayNits=5))) == api.E_INVALIDARG
     assert hr_of(lambda: vp.Configure(vp.settings.copy(iUpscaling=7))) == api.E_INVALIDARG      # past UPSCALE_Jinc2
     vp.close()
+    # A render target is made of dwords (include/mpcvr.h): a first byte or a pitch that is not a multiple of 4 is refused by every entry point
+    # that takes a target, in front of any launch — the target, and every byte around it, stays as it was.  The plain context, and one whose
+    # batches end in the error-diffusion pass (a route of its own).
+    import ctypes as C
+    from videorenderer_amd import synth
+    for kw in (dict(), dict(bUseDither=api.DITHER_ErrorDiffusion_EXT)):
+        vp = api.VideoProcessor(api.default_settings(**kw))
+        vp.InitMediaType(2, 64, 64, extfmt=GOLDEN_CASES["dovi_poly_sdr"]["exfmt"])
+        vp.SetWindowRect((0, 0, 64, 64)); vp.SetVideoRect((0, 0, 64, 64))
+        sample = torch.from_numpy(synth.make_frame(2, 64, 64, "noise", seed=5)[0].copy()).cuda()
+        pitch = vp.GetFrameBytes()[1]
+        t = CarvedTargets(torch, 64, 64, 64 * 4 + 16, [0, 0])
+        before = t.buf.clone()
+        rpu = synth.dovi_metadata(kind="poly")
+        arr = C.c_void_p * 2
+        L = api.load_library()
+        for off, dp in ((1, 272), (2, 272), (3, 272), (0, 273), (0, 274), (0, 275), (2, 274)):
+            a, b = t.ptrs[0] + off, t.ptrs[1]
+            vp.CopySample(sample, pitch)
+            assert hr_of(lambda: vp.Process(a, dp)) == api.E_INVALIDARG, (kw, off, dp)
+            assert L.mpcvr_process_frames(vp._ctx, 2, arr(sample.data_ptr(), sample.data_ptr()), pitch, api.MEM_DEVICE, arr(b, a), dp) == api.E_INVALIDARG, (kw, off, dp)
+            assert hr_of(lambda: vp.ProcessBatch([sample, sample], [b, a], dp)) == api.E_INVALIDARG, (kw, off, dp)
+            assert hr_of(lambda: vp.ProcessBatchDovi([sample, sample], [b, a], dp, [rpu, rpu])) == api.E_INVALIDARG, (kw, off, dp)
+            vp.Synchronize()
+            if off and dp % 4 == 0:
+                # (mpcvr_process_frames stops at the first failure: with a sound pitch its first frame — the aligned target — is drawn)
+                assert not torch.equal(t.window(1), before.as_strided((64, 64, 4), (272, 4, 1), t.starts[1])), (kw, off, dp)
+                t.window(1).fill_(BG)
+            assert torch.equal(t.buf, before), (kw, off, dp, "a refused call wrote into the buffer")
+        # (the same calls with a sound target and pitch are served)
+        vp.CopySample(sample, pitch)
+        vp.Process(t.ptrs[0], 272)
+        vp.ProcessBatch([sample, sample], t.ptrs, 272)
+        vp.Synchronize()
+        t.assert_guards_intact(f"aligned calls {kw}")
+        assert torch.equal(t.window(0), t.window(1)) and not bool((t.window(0) == BG).all())
+        vp.close()
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1456,17 +1649,18 @@ def test_full_size_hip_vs_reference_shader_text(mpcvr, oracle, torch_cuda, name)
     want, live = reference_text_output(oracle, name)
     for flag, path, floor in FULL_SIZE_TIERS[name]:
         flags = getattr(api, flag) if flag else 0
-        got, info = run_product(mpcvr, torch, c, extra_flags=flags)
-        assert info.startswith(path) or (path in ("period", "strip", "period:surface", "strip:surface") and f"kernel=fused_{path}(" in info), (name, flag, info)
-        assert bool((got[..., 3] == 255).all())
-        if name in FULL_SIZE_BEHIND_A_TAIL and floor < 1.0:     # channels beyond 1 LSB must each lie inside the oracle's own +-4 ulp pow() interval, and be few
-            frame, pitch = case_frame(c)
-            same, n_ill = compare_behind_tail(oracle, oracle_params(oracle, c), frame, pitch, got, want, f"{name} flags={flag} [{info}]", min_same=floor,
-                                              cap=FULL_SIZE_BEHIND_A_TAIL[name])
-            print(f"FULLSIZE {name} {flag or 'default'}: {n_ill} ill-conditioned channel(s)")
-        else:
-            same = compare(got, want, f"{name} flags={flag} [{info}]", exact=(floor == 1.0), min_same=floor)
-        print(f"FULLSIZE {name} {flag or 'default'} [{info}] vs reference text ({'live' if live else 'recorded hash'}): identical channels {same:.6f}")
+        # (today's layout and `off4` — the per-pixel store paths at real widths, right edge and last strip included; the reference frame serves both)
+        for layout, (got, info) in run_layouts(mpcvr, torch, c, extra_flags=flags, layouts=("tight", "off4"), what=f"{name} flags={flag}").items():
+            assert info.startswith(path) or (path in ("period", "strip", "period:surface", "strip:surface") and kernel_under(layout, f"kernel=fused_{path}(") in info), (name, flag, layout, info)
+            assert bool((got[..., 3] == 255).all())
+            if name in FULL_SIZE_BEHIND_A_TAIL and floor < 1.0:     # channels beyond 1 LSB must each lie inside the oracle's own +-4 ulp pow() interval, and be few
+                frame, pitch = case_frame(c)
+                same, n_ill = compare_behind_tail(oracle, oracle_params(oracle, c), frame, pitch, got, want, f"{name} flags={flag} <{layout}> [{info}]", min_same=floor,
+                                                  cap=FULL_SIZE_BEHIND_A_TAIL[name])
+                print(f"FULLSIZE {name} {flag or 'default'} <{layout}>: {n_ill} ill-conditioned channel(s)")
+            else:
+                same = compare(got, want, f"{name} flags={flag} <{layout}> [{info}]", exact=(floor == 1.0), min_same=floor)
+            print(f"FULLSIZE {name} {flag or 'default'} <{layout}> [{info}] vs reference text ({'live' if live else 'recorded hash'}): identical channels {same:.6f}")
 
 
 @pytest.mark.parametrize("name", sorted(GOLDEN_CASES))
@@ -1545,13 +1739,16 @@ def test_strip_kernel_whole_frame_vs_oracle(mpcvr, oracle, torch_cuda, label, c)
     frame, pitch = case_frame(c)
     p = oracle_params(oracle, c)
     want = oracle.process(p, frame, pitch, dst=np.full((p.window_h, p.window_w, 4), BG, dtype=np.uint8))
-    got, info = run_product(mpcvr, torch, c, extra_flags=api.FLAG_NO_PERIOD)
-    assert "kernel=fused_strip" in info, info
-    same = compare(got, want, f"{label} [{info}]", min_same=WHOLE_FRAME_FLOOR)
-    alt, info_alt = run_product(mpcvr, torch, c, extra_flags=api.FLAG_NO_STRIP)
-    assert "kernel=fused_" not in info_alt and info_alt.startswith("passes:convert,resizeX,resizeY"), info_alt
-    same_alt = compare(alt, want, f"{label} [{info_alt}]", min_same=WHOLE_FRAME_FLOOR)
-    print(f"{label}: identical channels strip {same:.6f}, tiled {same_alt:.6f}  [{info}]")
+    # every render-target layout (run_layouts checks the bytes around the pixels): the right edge and the last strip at real widths
+    strips = run_layouts(mpcvr, torch, c, extra_flags=api.FLAG_NO_PERIOD, what=label)
+    tiled = run_layouts(mpcvr, torch, c, extra_flags=api.FLAG_NO_STRIP, what=label)
+    for layout in LAYOUTS:
+        (got, info), (alt, info_alt) = strips[layout], tiled[layout]
+        assert "kernel=fused_strip" in info, info
+        same = compare(got, want, f"{label} <{layout}> [{info}]", min_same=WHOLE_FRAME_FLOOR)
+        assert "kernel=fused_" not in info_alt and info_alt.startswith("passes:convert,resizeX,resizeY"), info_alt
+        same_alt = compare(alt, want, f"{label} <{layout}> [{info_alt}]", min_same=WHOLE_FRAME_FLOOR)
+        print(f"{label} <{layout}>: identical channels strip {same:.6f}, tiled {same_alt:.6f}  [{info}]")
 
 
 _SDR = GOLDEN_CASES["c1_nv12_bt709_passthrough"]["exfmt"]
@@ -1596,24 +1793,26 @@ def test_period_kernel_vs_oracle_and_strip_kernel(mpcvr, oracle, torch_cuda, lab
     frame, pitch = case_frame(c)
     p = oracle_params(oracle, c)
     want = oracle.process(p, frame, pitch, dst=np.full((p.window_h, p.window_w, 4), BG, dtype=np.uint8))
-    got, info = run_product(mpcvr, torch, c, extra_flags=api.FLAG_FORCE_PERIOD)       # (SDR + 4 taps: the planner's own choice is k_fused_strip)
+    periods = run_layouts(mpcvr, torch, c, extra_flags=api.FLAG_FORCE_PERIOD, what=label)       # (SDR + 4 taps: the planner's own choice is k_fused_strip)
+    strips = run_layouts(mpcvr, torch, c, extra_flags=api.FLAG_NO_PERIOD, what=label)
     P, Q, nt = pqn
-    if nt == 6 or (nt == 4 and not has_tail(c)):     # (round 5: six taps — MPCVR_FLAG_LANCZOS3_FIXED, the Spline36 extension — have no periodic variant any
-        # more; round 6: nor have four taps without a tail (SDR through Mitchell / Catmull-Rom / Lanczos2), where the strip kernel was the planner's choice anyway)
-        assert "kernel=fused_strip(" in info, info
-    else:
-        assert f"kernel=fused_period(rows={P}:{Q},taps={nt}," in info, info
-    alt, info_alt = run_product(mpcvr, torch, c, extra_flags=api.FLAG_NO_PERIOD)
-    assert "kernel=fused_strip(" in info_alt, info_alt
-    if c.get("output_format", 0) == 1:
-        compare_rgb10(got, want, f"{label} [{info}]", tail=has_tail(c), min_same=0.99)
-        compare_rgb10(alt, want, f"{label} [{info_alt}]", tail=has_tail(c), min_same=0.99)
-        return
-    floor = 0.99 if c["w"] < 100 else 0.998
-    same = compare(got, want, f"{label} [{info}]", min_same=floor)
-    same_alt = compare(alt, want, f"{label} [{info_alt}]", min_same=floor)
-    compare(got, alt, f"{label} period vs strip", min_same=floor)
-    print(f"PERIOD {label}: identical channels period {same:.6f}, strip {same_alt:.6f}  [{info}]")
+    for layout in LAYOUTS:             # (every render-target layout: `off8` is the 8-byte store of k_fused_period, `off4` its per-pixel one)
+        (got, info), (alt, info_alt) = periods[layout], strips[layout]
+        if nt == 6 or (nt == 4 and not has_tail(c)):     # (round 5: six taps — MPCVR_FLAG_LANCZOS3_FIXED, the Spline36 extension — have no periodic variant any
+            # more; round 6: nor have four taps without a tail (SDR through Mitchell / Catmull-Rom / Lanczos2), where the strip kernel was the planner's choice anyway)
+            assert "kernel=fused_strip(" in info, info
+        else:
+            assert kernel_under(layout, f"kernel=fused_period(rows={P}:{Q},taps={nt},") in info, (layout, info)
+        assert "kernel=fused_strip(" in info_alt, info_alt
+        if c.get("output_format", 0) == 1:
+            compare_rgb10(got, want, f"{label} <{layout}> [{info}]", tail=has_tail(c), min_same=0.99)
+            compare_rgb10(alt, want, f"{label} <{layout}> [{info_alt}]", tail=has_tail(c), min_same=0.99)
+            continue
+        floor = 0.99 if c["w"] < 100 else 0.998
+        same = compare(got, want, f"{label} <{layout}> [{info}]", min_same=floor)
+        same_alt = compare(alt, want, f"{label} <{layout}> [{info_alt}]", min_same=floor)
+        compare(got, alt, f"{label} <{layout}> period vs strip", min_same=floor)
+        print(f"PERIOD {label} <{layout}>: identical channels period {same:.6f}, strip {same_alt:.6f}  [{info}]")
 
 
 PERIOD_SURFACE_CASES = [
@@ -1732,9 +1931,66 @@ def test_period_kernel_batches_equal_single_frames(mpcvr, torch_cuda, over, kern
     outs = [torch.zeros((wh, ww, 4), dtype=torch.uint8, device="cuda") for _ in frames]
     vp.ProcessBatch(frames, outs, ww * 4)
     vp.Synchronize()
-    vp.close()
     for a, b in zip(singles, outs):
         assert torch.equal(a, b)
+    whole = vp.GetLastBatchInfo()
+    # the targets as slices of one patterned buffer with mixed first bytes: `off8`'s pitch, then `off4`'s
+    for layout in ("off8", "off4"):
+        mixed = batch_vs_singles_in_carved_targets(torch, vp, frames, pitch, ww, wh, layout_of(layout, ww)[1], MIXED_BASES[:5], f"{over} <{layout}>")
+        assert kernel_under("off4", kernel) in vp.GetVPInfo(), (layout, vp.GetVPInfo())        # (a target at +4: the 8-byte stores step aside)
+        # (still one launch per stage — except same-size frames: the block convert needs 16-byte targets, so such a batch declines to frame by frame)
+        assert mixed["frames"] == 5 and (mixed["launches"] == whole["launches"] or kernel == "direct:convert"), (layout, whole, mixed)
+    vp.close()
+
+
+# Same-size frames (DirectConvert) are the one route a misaligned target takes away: k_convert_blocks stores 16 bytes per lane and has no
+# per-pixel epilogue, so a batch with such a target goes frame by frame — its aligned frames through k_convert_blocks, the others through
+# the per-pixel convert kernel, each as the single frame into that target would.
+MIXED_ALIGNMENT_DECLINES = ("DirectConvert",)
+MIXED_ALIGNMENT_ROUTES = {
+    # route: (case, extra flags, the GetVPInfo fragment of an aligned batch)
+    "FusedUp2x": (GOLDEN_CASES["noise_p010_pq_lanczos3_2x"], 0, "fused_up2x"),
+    "Strip:k_fused_strip": (dict(cformat=2, w=960, h=540, kind="noise", seed=420, dst=(1300, 733), iUpscaling=4, exfmt=_PQ), 0, "kernel=fused_strip("),
+    "Strip:k_fused_period": (dict(cformat=2, w=960, h=540, kind="noise", seed=420, dst=(1280, 720), iUpscaling=4, exfmt=_PQ), 0, "kernel=fused_period("),
+    "DirectConvert": (GOLDEN_CASES["c1_nv12_bt709_passthrough"], 0, "direct:convert"),
+    "WholeBatchLaunches": (GOLDEN_CASES["down_lanczos_2p5x"], 64, "passes:"),                       # 64 = NO_STRIP: block convert + tiled two-draw kernel
+    "StripToneMap": (GOLDEN_CASES["hdrout_tm2_reinhard"], 0, "hdr10tonemap"),
+    "RgbSurfaceStrip": (dict(cformat=30, w=960, h=540, kind="noise", seed=420, dst=(1280, 720), iUpscaling=4), 0, "kernel=fused_period:surface("),
+    "ErrorDiffusion": (dict(GOLDEN_CASES["c3hdr_p010_pq_lanczos3_2x"], bUseDither=2), 0, "errdiff"),
+}
+
+
+@pytest.mark.parametrize("order", ["aligned_first_misaligned_later", "misaligned_first_aligned_later"])
+@pytest.mark.parametrize("route", sorted(MIXED_ALIGNMENT_ROUTES))
+def test_batch_whose_targets_differ_in_alignment(mpcvr, torch_cuda, route, order):
+    """The launch parameters of a batch are planned from its FIRST target; the epilogue has to be the one its worst-aligned target allows.
+    Per whole-batch route: a batch whose first target sits on a 256-byte boundary and whose later ones do not, and the other way round, at a
+    pitch that is a multiple of 16 (the aligned targets alone would take the 16-byte stores).  Every frame must equal the frame drawn alone,
+    the bytes around every target must keep their pattern, and the batch must stay on its whole-batch route (a handful of launches;
+    MIXED_ALIGNMENT_DECLINES names the one route that steps aside)."""
+    torch = torch_cuda
+    c, flags, fragment = MIXED_ALIGNMENT_ROUTES[route]
+    vp, (ww, wh) = make_vp(mpcvr, c, flags)
+    c = dict(c, kind="noise")
+    frames = [torch.from_numpy(case_frame(dict(c, seed=c["seed"] + 100 * i))[0]).cuda() for i in range(5)]
+    pitch = vp.GetFrameBytes()[1]
+    dst_pitch = layout_of("padded16", ww)[1]
+    # what an aligned batch of this case runs (the route under test), then the mixed one
+    aligned = CarvedTargets(torch, ww, wh, dst_pitch, [0] * 5)
+    vp.ProcessBatch(frames, aligned.ptrs, dst_pitch)
+    vp.Synchronize()
+    aligned.assert_guards_intact(f"{route}: aligned batch")
+    info, whole = vp.GetVPInfo(), vp.GetLastBatchInfo()
+    assert fragment in info and whole["frames"] == 5 and whole["launches"] <= 4, (route, info, whole)
+    bases = (0, 4, 0, 8, 4) if order.startswith("aligned") else (4, 0, 0, 8, 0)
+    mixed = batch_vs_singles_in_carved_targets(torch, vp, frames, pitch, ww, wh, dst_pitch, bases, f"{route} {order}")
+    info = vp.GetVPInfo()
+    vp.close()
+    assert kernel_under("off4", fragment) in info, (route, order, info)
+    if route in MIXED_ALIGNMENT_DECLINES:
+        assert mixed["frames"] == 5 and mixed["launches"] == 5, (route, order, info, mixed)
+    else:
+        assert mixed["frames"] == 5 and mixed["launches"] <= 4, (route, order, info, mixed)
 
 
 # ---- instantiation sweeps: every template instantiation of the two headline kernel families is launched by the suite ----
@@ -1781,32 +2037,36 @@ def _sweep_case(cformat, over, tail, taps, src_wh, dst_wh, seed):
 
 def _tiers_agree(mpcvr, torch, c, fast_flags, expect):
     from videorenderer_amd import api
-    got, info = run_product(mpcvr, torch, c, extra_flags=fast_flags)
-    assert expect in info, (c, info)
-    ref, info_ref = run_product(mpcvr, torch, c, extra_flags=api.FLAG_NO_FUSED)
-    assert info_ref.startswith("passes:"), info_ref
+    # every render-target layout, both tiers: a source / epilogue pair whose specialised store needs an aligned target runs its generic twin
+    # under `off4` / `off8` (run_layouts checks the bytes around the pixels; the oracle's frame is computed once)
+    fast = run_layouts(mpcvr, torch, c, extra_flags=fast_flags, what=f"{expect} sweep {c}")
+    plain = run_layouts(mpcvr, torch, c, extra_flags=api.FLAG_NO_FUSED, what=f"plain tier {c}")
     # Round 6: the plain tier carries the ORACLE's bits (tails included), so "the fast tier within the bar of the plain one" below IS "within the
     # bar of the oracle" — checked here on every sweep case instead of assumed (round 5's review: ~90 sweep tests compared two GPU tiers only)
     from oracle import oracle as O
     frame, pitch = case_frame(c)
     po = oracle_params(O, c)
     want = O.process(po, frame, pitch, dst=np.full((po.window_h, po.window_w, 4), BG, dtype=np.uint8))
-    if c.get("output_format", 0) == 1:
-        assert np.array_equal(_codes10(ref), _codes10(want)), (c, info_ref, "plain tier != oracle")
-    else:
-        assert np.array_equal(ref[..., :3], want[..., :3]), (c, info_ref, "plain tier != oracle", int(np.abs(ref[..., :3].astype(int) - want[..., :3].astype(int)).max()))
-    if c.get("output_format", 0) == 1:
-        g, r = got.view(np.uint32)[..., 0], ref.view(np.uint32)[..., 0]
-        lim = 5 if internal_is_8bit(c) else 2 if has_tail(c) else 1
-        if c.get("iUpscaling") == 5:     # Jinc2m's weights sum to |w| = 1.9: one code of the block convert in the 10-bit texture comes out as up to two
-            lim = max(lim, 2)
-        for sh in (0, 10, 20):
-            d = np.abs(((g >> sh) & 1023).astype(np.int32) - ((r >> sh) & 1023).astype(np.int32))
-            assert d.max() <= lim, (c, info, int(d.max()))
-    else:
-        d = np.abs(got[..., :3].astype(np.int16) - ref[..., :3].astype(np.int16))
-        assert d.max() <= 1, (c, info, int(d.max()), int((d > 1).sum()))        # two GPU tiers of one frame
-        assert np.array_equal(got[..., 3], ref[..., 3])
+    for layout in LAYOUTS:
+        (got, info), (ref, info_ref) = fast[layout], plain[layout]
+        assert kernel_under(layout, expect) in info, (c, layout, info)
+        assert info_ref.startswith("passes:"), info_ref
+        if c.get("output_format", 0) == 1:
+            assert np.array_equal(_codes10(ref), _codes10(want)), (c, layout, info_ref, "plain tier != oracle")
+        else:
+            assert np.array_equal(ref[..., :3], want[..., :3]), (c, layout, info_ref, "plain tier != oracle", int(np.abs(ref[..., :3].astype(int) - want[..., :3].astype(int)).max()))
+        if c.get("output_format", 0) == 1:
+            g, r = got.view(np.uint32)[..., 0], ref.view(np.uint32)[..., 0]
+            lim = 5 if internal_is_8bit(c) else 2 if has_tail(c) else 1
+            if c.get("iUpscaling") == 5:     # Jinc2m's weights sum to |w| = 1.9: one code of the block convert in the 10-bit texture comes out as up to two
+                lim = max(lim, 2)
+            for sh in (0, 10, 20):
+                d = np.abs(((g >> sh) & 1023).astype(np.int32) - ((r >> sh) & 1023).astype(np.int32))
+                assert d.max() <= lim, (c, layout, info, int(d.max()))
+        else:
+            d = np.abs(got[..., :3].astype(np.int16) - ref[..., :3].astype(np.int16))
+            assert d.max() <= 1, (c, layout, info, int(d.max()), int((d > 1).sum()))        # two GPU tiers of one frame
+            assert np.array_equal(got[..., 3], ref[..., 3])
 
 
 @pytest.mark.parametrize("taps", sorted(_SWEEP_TAPS))
@@ -1997,17 +2257,19 @@ def test_strip_kernel_from_a_surface_whole_frame(mpcvr, oracle, torch_cuda, labe
     frame, pitch = case_frame(c)
     p = oracle_params(oracle, c)
     want = oracle.process(p, frame, pitch, dst=np.full((p.window_h, p.window_w, 4), BG, dtype=np.uint8))
-    got, info = run_product(mpcvr, torch, c, extra_flags=api.FLAG_NO_PERIOD)      # (4:3 and friends would go to k_fused_period:surface)
-    assert "kernel=fused_strip:surface" in info, info
-    same = compare(got, want, f"{label} [{info}]", min_same=WHOLE_FRAME_FLOOR)
-    alt, info_alt = run_product(mpcvr, torch, c, extra_flags=api.FLAG_NO_STRIP)
-    assert "kernel=" not in info_alt, info_alt
-    if has_tail(c) or (c.get("rotation") and c["cformat"] < 29):
-        # (a 4:2:0 source turned by 180 degrees: the alternative is the fused block convert + the tiled kernel — a fused tier, <= 1 LSB)
-        compare(alt, want, f"{label} [{info_alt}]", min_same=WHOLE_FRAME_FLOOR)
-    else:
-        compare(alt, want, f"{label} [{info_alt}]", exact=True)
-    print(f"{label}: identical channels {same:.6f}  [{info}]")
+    surf = run_layouts(mpcvr, torch, c, extra_flags=api.FLAG_NO_PERIOD, what=label)      # (4:3 and friends would go to k_fused_period:surface)
+    tiled = run_layouts(mpcvr, torch, c, extra_flags=api.FLAG_NO_STRIP, what=label)
+    for layout in LAYOUTS:             # every render-target layout (run_layouts checks the bytes around the pixels)
+        (got, info), (alt, info_alt) = surf[layout], tiled[layout]
+        assert "kernel=fused_strip:surface" in info, info
+        same = compare(got, want, f"{label} <{layout}> [{info}]", min_same=WHOLE_FRAME_FLOOR)
+        assert "kernel=" not in info_alt, info_alt
+        if has_tail(c) or (c.get("rotation") and c["cformat"] < 29):
+            # (a 4:2:0 source turned by 180 degrees: the alternative is the fused block convert + the tiled kernel — a fused tier, <= 1 LSB)
+            compare(alt, want, f"{label} <{layout}> [{info_alt}]", min_same=WHOLE_FRAME_FLOOR)
+        else:
+            compare(alt, want, f"{label} <{layout}> [{info_alt}]", exact=True)
+        print(f"{label} <{layout}>: identical channels {same:.6f}  [{info}]")
 
 
 def _cr_cases():
@@ -2410,16 +2672,21 @@ def test_correction_passes_vs_oracle(mpcvr, oracle, torch_cuda, kind, src_fmt, d
     src[0, :8] = [0, 0xffffffff, 0x3ff, 0x3ff << 10, 0x3ff << 20, 0x00ff0000, 0x0000ff00, 0x000000ff]
     want = oracle.correction_pass(kind, src, 10 if src_fmt else 8, 10 if dst_fmt else 8, sdr_nits=125)
     d_src = torch.from_numpy(src.view(np.int32)).cuda()
-    d_dst = torch.zeros((h, w), dtype=torch.int32, device="cuda")
-    api.correction_pass(kind, d_src, w * 4, src_fmt, d_dst, w * 4, dst_fmt, w, h, sdr_nits=125)
-    torch.cuda.synchronize()
-    got = d_dst.cpu().numpy().view(np.uint32)
-    if dst_fmt:
-        compare_rgb10(got.reshape(h, w, 1).view(np.uint8).reshape(h, w, 4), want.reshape(h, w, 1).view(np.uint8).reshape(h, w, 4),
-                      f"correction {kind}", exact=(kind == 2))
-    else:
-        compare(got.view(np.uint8).reshape(h, w, 4), want.view(np.uint8).reshape(h, w, 4), f"correction {kind}",
-                exact=(kind == 2), min_same=0.99)
+    # the pass writes through dst_pitch: every render-target layout, the bytes around the w x h texels untouched
+    outs = {}
+    for layout in LAYOUTS:
+        base, dst_pitch = layout_of(layout, w)
+        t = CarvedTargets(torch, w, h, dst_pitch, [base])
+        api.correction_pass(kind, d_src, w * 4, src_fmt, t.ptrs[0], dst_pitch, dst_fmt, w, h, sdr_nits=125)
+        torch.cuda.synchronize()
+        t.assert_guards_intact(f"correction {kind} layout {layout}")
+        outs[layout] = t.pixels()
+        if dst_fmt:
+            compare_rgb10(outs[layout], want.reshape(h, w, 1).view(np.uint8).reshape(h, w, 4), f"correction {kind} <{layout}>", exact=(kind == 2))
+        else:
+            compare(outs[layout], want.view(np.uint8).reshape(h, w, 4), f"correction {kind} <{layout}>", exact=(kind == 2), min_same=0.99)
+    assert np.array_equal(outs["tight"], outs["padded16"])
+    got = np.ascontiguousarray(outs["tight"]).view(np.uint32)[..., 0]
     # in place
     api.correction_pass(kind, d_src, w * 4, src_fmt, d_src, w * 4, src_fmt, w, h, sdr_nits=125)
     torch.cuda.synchronize()
@@ -3016,6 +3283,113 @@ def test_batches_on_the_lanes_equal_batches_in_stream_order(mpcvr, torch_cuda, n
         assert lanes == expect_lanes, lanes
         for i, (g, w) in enumerate(zip(got, want)):
             assert torch.equal(g, w), f"round {rep}: target {i} differs from the stream-ordered run"
+
+
+@pytest.mark.parametrize("name,size,dst,route", [
+    ("c3hdr_p010_pq_lanczos3_2x", (1920, 1080), (3840, 2160), "fused_up2x"),
+    ("c3hdr_p010_pq_lanczos3_2x", (1920, 1080), (2560, 1440), "kernel=fused_period"),
+    ("c3hdr_p010_pq_lanczos3_2x", (1920, 1080), (2304, 1296), "kernel=fused_strip"),
+    ("c1_nv12_bt709_passthrough", (1920, 1080), (1920, 1080), "direct:convert")])
+def test_overlapping_targets_keep_their_order_on_the_lanes(mpcvr, torch_cuda, name, size, dst, route):
+    """Two writers of the same MEMORY stay in the order they were queued whatever pointers they were given (include/mpcvr.h): a window a few
+    rows further down in one surface, the same surface addressed from another base.  Like test_batches_on_the_lanes_equal_batches_in_stream_order:
+    a context on a caller's stream gives the stream-ordered truth, a context that owns its stream (batches and single frames on the lanes) must
+    leave the same bytes, three rounds.  All targets are rows of ONE allocation of 3n * window_h + window_h (+ r) rows, addressed by pointer.
+    Each sequence makes the race decide: the earlier writer is long (8 frames), the later, overlapping one short and aimed at what the long one
+    writes last, both from different noise frames — "the earlier one finished last" leaves other bytes.
+      shifted_batch        batch into rows k * window_h, then a batch window_h // 2 rows further down (each target over two targets in flight)
+      frame_into_batch     mpcvr_process into a pointer inside a target of the batch in flight                          (PickFrameLane)
+      batch_over_frames    a batch over single frames still in flight on a frame lane                                   (PickBatchLane, the rings)
+      other_base           the allocation from its base pointer, then from base + dst_pitch * r, window unchanged
+      adjacent             targets that touch (end of one == start of the next) and rows whose PADDING interleaves: still on both lanes,
+                           and touching targets wait for nothing (GetLastBatchInfo: waits=0) — the order is kept without serialising everything"""
+    import ctypes as C
+    from videorenderer_amd import api, synth
+    torch = torch_cuda
+    c = dict(GOLDEN_CASES[name])
+    c.update(w=size[0], h=size[1], dst=dst)
+    (ww, wh), vr = case_geometry(c)
+    n, r = 8, 16
+    frames = []
+    for i in range(2 * n + 4):
+        f, pitch = synth.make_frame(c["cformat"], c["w"], c["h"], "noise", seed=1900 + i)
+        frames.append(torch.from_numpy(np.ascontiguousarray(f)).cuda())
+    kw = {k: c[k] for k in SETTING_KEYS if k in c}
+    row = ww * 4
+    rows_total = 3 * n * wh + wh + r
+
+    def shifted_batch(vp, at, note):
+        vp.ProcessBatch(frames[0:n], [at(i * wh) for i in range(n)], row); note(vp)
+        vp.ProcessBatch(frames[n:n + 2], [at((n - 2 + j) * wh + wh // 2) for j in range(2)], row); note(vp)      # over targets 6, 7 (and free rows)
+        vp.ProcessBatch(frames[n + 2:n + 4], [at((n + 2 + j) * wh) for j in range(2)], row); note(vp)              # disjoint: beside them
+
+    def frame_into_batch(vp, at, note):
+        vp.CopySample(frames[n + 2], pitch); vp.Process(at(2 * n * wh), row)         # (takes the first frame lane: the next frame gets another lane than the batch)
+        vp.ProcessBatch(frames[0:n], [at(i * wh) for i in range(n)], row); note(vp)
+        vp.CopySample(frames[n], pitch); vp.Process(at((n - 1) * wh + wh // 2), row)
+
+    def batch_over_frames(vp, at, note):
+        vp.CopySample(frames[n + 3], pitch); vp.Process(at(2 * n * wh), row)         # (the first frame lane — the lane the batch below takes)
+        # seven frames into ONE target queue up on the second lane (mpcvr_process_frames: no interpreter between them, so they do queue up)
+        arr = C.c_void_p * 7
+        assert api.load_library().mpcvr_process_frames(vp._ctx, 7, arr(*[f.data_ptr() for f in frames[:7]]), pitch, api.MEM_DEVICE, arr(*[at(2 * wh)] * 7), row) == 0
+        vp.ProcessBatch(frames[n:n + 2], [at(wh + wh // 2), at(2 * wh + wh // 2)], row); note(vp)
+
+    def other_base(vp, at, note):
+        vp.ProcessBatch(frames[0:n], [at(i * wh) for i in range(n)], row); note(vp)
+        vp.ProcessBatch(frames[n:n + 2], [at(r + (n - 2 + j) * wh) for j in range(2)], row); note(vp)             # the same surface, r rows further down
+
+    def adjacent(vp, at, note):
+        for b in range(4):                    # every batch starts on the byte the one before ended on
+            vp.ProcessBatch(frames[b * 4:b * 4 + 4], [at((b * 4 + i) * wh) for i in range(4)], row); note(vp, touching=b > 0)
+        # a surface twice as wide: the left halves of its rows, then the right halves (each target's padding is the other's pixels)
+        vp.ProcessBatch(frames[0:2], [at(4 * n * wh // 2 + 2 * i * wh) for i in range(2)], 2 * row); note(vp)
+        vp.ProcessBatch(frames[2:4], [at(4 * n * wh // 2 + 2 * i * wh) + row for i in range(2)], 2 * row); note(vp)
+
+    def play(seq, own):
+        if not own:
+            with torch.cuda.stream(torch.cuda.Stream()):         # (torch's default stream is NULL = "the context's own stream")
+                return play_on(seq, False)
+        return play_on(seq, True)
+
+    def play_on(seq, own):
+        vp = api.VideoProcessor(api.default_settings(**kw), use_torch_stream=not own)
+        vp.InitMediaType(c["cformat"], c["w"], c["h"], extfmt=c.get("exfmt", 0))
+        vp.SetWindowRect((0, 0, ww, wh)); vp.SetVideoRect(vr)
+        surf = torch.full((rows_total * row,), BG, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        lanes, waits_touching = [], []
+
+        def note(vp, touching=False):
+            b = vp.GetLastBatchInfo()
+            lanes.append(b["lane"])
+            if touching:
+                waits_touching.append(b["waits"])
+
+        seq(vp, lambda first_row: surf.data_ptr() + first_row * row, note)
+        vp.Synchronize()
+        torch.cuda.synchronize()
+        info = vp.GetVPInfo()
+        vp.close()
+        return surf, lanes, waits_touching, info
+
+    failed = []
+    for seq in (shifted_batch, frame_into_batch, batch_over_frames, other_base, adjacent):
+        want, lanes_ref, _, info = play(seq, False)
+        assert route in info, info
+        assert set(lanes_ref) == {-1}, lanes_ref              # a caller's stream promises stream order: no lanes
+        assert int((want != BG).sum()) >= 2 * wh * row        # (every sequence draws at least two frames)
+        for rep in range(3):
+            got, lanes, waits_touching, _ = play(seq, True)
+            # the batches still take turns on the two lanes
+            assert lanes == [i % 2 for i in range(len(lanes))], (seq.__name__, lanes)
+            assert not any(waits_touching), (seq.__name__, "targets that only touch were ordered behind each other", waits_touching)
+            if not torch.equal(got, want):
+                bad = torch.nonzero((got != want).view(rows_total, row).any(dim=1)).flatten()
+                failed.append(f"{seq.__name__} round {rep}: rows {int(bad[0])}..{int(bad[-1])} ({bad.numel()} rows) differ from the stream-ordered run")
+                break
+            del got
+    assert not failed, failed
 
 
 def test_bench_through_rccl_in_a_world_of_one(mpcvr, torch_cuda):

@@ -216,19 +216,48 @@ int CHipVideoProcessor::FrameLaneCount()
     return n;
 }
 
-// the lane of the frame about to be queued: one that still holds a frame into the same render target if there is one (stream order
-// then keeps the two writes apart; further lanes holding such a frame are waited for), else the next in turn
-CHipVideoProcessor::FrameLane *CHipVideoProcessor::PickFrameLane(const void *rt)
+// ---- what is in flight, as memory: two writers are ordered when the bytes their render targets cover overlap, whatever pointers they were
+// given (a window a few rows further down in one surface, the same surface from another base); targets that merely touch run side by side ----
+CHipVideoProcessor::RtSpan CHipVideoProcessor::TargetSpan(const void *rt, int rtPitch) const
+{
+    RtSpan s;
+    s.lo = (uintptr_t)rt;
+    s.hi = s.lo + (size_t)std::max(m_windowRect.Height() - 1, 0) * (size_t)rtPitch + (size_t)m_windowRect.Width() * 4;
+    return s;
+}
+
+// sorted by address, spans that overlap or touch merged into one: the result is disjoint, so both ends ascend
+void CHipVideoProcessor::SortAndMergeSpans(std::vector<RtSpan> &v)
+{
+    std::sort(v.begin(), v.end(), [](const RtSpan &a, const RtSpan &b) { return a.lo < b.lo; });
+    size_t m = 0;
+    for (size_t i = 0; i < v.size(); i++) {
+        if (m && v[i].lo <= v[m - 1].hi) v[m - 1].hi = std::max(v[m - 1].hi, v[i].hi);
+        else v[m++] = v[i];
+    }
+    v.resize(m);
+}
+
+bool CHipVideoProcessor::SpansOverlap(const std::vector<RtSpan> &sorted, const RtSpan &s)
+{
+    // the first span that ends behind s.lo is the only candidate: the ones in front end too early, the ones behind start later still
+    const auto it = std::upper_bound(sorted.begin(), sorted.end(), s.lo, [](uintptr_t lo, const RtSpan &x) { return lo < x.hi; });
+    return it != sorted.end() && it->lo < s.hi;
+}
+
+// the lane of the frame about to be queued: one that still holds a frame into memory this one's render target overlaps if there is one
+// (stream order then keeps the two writes apart; further lanes holding such a frame are waited for), else the next in turn
+CHipVideoProcessor::FrameLane *CHipVideoProcessor::PickFrameLane(const RtSpan &rt)
 {
     FrameLane *pick = nullptr;
     hipEvent_t also[kFrameLanes];
     int n_also = 0;
     for (int li = 0; li < FrameLaneCount(); li++) {
         FrameLane &fl = m_flanes[li];
-        hipEvent_t latest = nullptr;                 // the lane's most recent unfinished frame into rt (the ring is walked oldest first)
+        hipEvent_t latest = nullptr;                 // the lane's most recent unfinished frame into rt's bytes (the ring is walked oldest first)
         for (int i = 0; i < kLaneDepth; i++) {
             LaneFrame &f = fl.ring[(fl.head + i) % kLaneDepth];
-            if (!f.pending || f.rt != rt) continue;          // (only a frame into the same target is worth a driver call)
+            if (!f.pending || !f.rt.Overlaps(rt)) continue;  // (only a frame into the same memory is worth a driver call)
             if (hipEventQuery(f.done) == hipSuccess) { f.pending = false; continue; }
             latest = f.done;
         }
@@ -238,63 +267,65 @@ CHipVideoProcessor::FrameLane *CHipVideoProcessor::PickFrameLane(const void *rt)
     if (!pick) { pick = &m_flanes[m_flaneNext]; m_flaneNext = (m_flaneNext + 1) % FrameLaneCount(); }
     if (!pick->stream && hipStreamCreateWithFlags(&pick->stream, hipStreamDefault) != hipSuccess) { pick->stream = nullptr; return nullptr; }
     for (int i = 0; i < n_also; i++) (void)hipStreamWaitEvent(pick->stream, also[i], 0);
-    // ... and behind a whole batch still in flight on another lane that writes this target (the pick's own batches: stream order)
+    // ... and behind a whole batch still in flight on another lane that writes into this target's bytes (the pick's own batches: stream order)
     for (int li = 0; li < kFrameLanes; li++) {
         FrameLane &bl = m_flanes[li];
         if (!bl.batchPending || &bl == pick) continue;
-        if (hipEventQuery(bl.batchDone) == hipSuccess) { bl.batchPending = false; bl.batchRts.clear(); continue; }
-        if (std::binary_search(bl.batchRts.begin(), bl.batchRts.end(), rt)) (void)hipStreamWaitEvent(pick->stream, bl.batchDone, 0);
+        if (hipEventQuery(bl.batchDone) == hipSuccess) { bl.batchPending = false; bl.batchSpans.clear(); continue; }
+        if (SpansOverlap(bl.batchSpans, rt)) (void)hipStreamWaitEvent(pick->stream, bl.batchDone, 0);
     }
     return pick;
 }
 
 // ---- whole batches on the lanes (see FrameLane; which batches may take them: ProcessBatchRoutes) ----
-// the lane of the batch about to be queued (the two take turns), ordered behind everything still in flight on OTHER lanes that writes one
-// of its render targets: single frames (their ring entries) and batches
-CHipVideoProcessor::FrameLane *CHipVideoProcessor::PickBatchLane(int n, void *const *dsts)
+// the lane of the batch about to be queued (the two take turns), ordered behind everything still in flight on OTHER lanes that writes into
+// the bytes of one of its render targets: single frames (their ring entries) and batches
+CHipVideoProcessor::FrameLane *CHipVideoProcessor::PickBatchLane(int n, void *const *dsts, int rtPitch)
 {
     FrameLane *pick = &m_flanes[m_blaneNext];
     if (!pick->stream && hipStreamCreateWithFlags(&pick->stream, hipStreamDefault) != hipSuccess) { pick->stream = nullptr; return nullptr; }
     // (two lanes: MPCVR_BATCH_LANE_COUNT = 2 .. 8 for the A/B — profiles/r06/batch_lane_count_call34.txt)
     static const int count = [] { const char *e = std::getenv("MPCVR_BATCH_LANE_COUNT"); const int v = e && *e ? std::atoi(e) : kBatchLanes; return v < 2 ? 2 : v > kFrameLanes ? kFrameLanes : v; }();
     m_blaneNext = (m_blaneNext + 1) % count;
-    std::vector<const void *> rts(dsts, dsts + n);
-    std::sort(rts.begin(), rts.end());
+    std::vector<RtSpan> &spans = m_batchSpans;
+    spans.clear();
+    for (int i = 0; i < n; i++) spans.push_back(TargetSpan(dsts[i], rtPitch));
+    SortAndMergeSpans(spans);
+    m_lastBatchWaits = 0;
     for (FrameLane &fl : m_flanes) {
         if (&fl == pick || !fl.stream) continue;
         for (LaneFrame &f : fl.ring) {
             if (!f.pending) continue;
             if (hipEventQuery(f.done) == hipSuccess) { f.pending = false; continue; }
-            if (std::binary_search(rts.begin(), rts.end(), f.rt)) (void)hipStreamWaitEvent(pick->stream, f.done, 0);
+            if (SpansOverlap(spans, f.rt)) { (void)hipStreamWaitEvent(pick->stream, f.done, 0); m_lastBatchWaits++; }
         }
         if (!fl.batchPending) continue;
-        if (hipEventQuery(fl.batchDone) == hipSuccess) { fl.batchPending = false; fl.batchRts.clear(); continue; }
+        if (hipEventQuery(fl.batchDone) == hipSuccess) { fl.batchPending = false; fl.batchSpans.clear(); continue; }
         bool shared = false;
-        for (size_t a = 0, b = 0; a < rts.size() && b < fl.batchRts.size() && !shared;) {
-            if (rts[a] == fl.batchRts[b]) shared = true;
-            else if (rts[a] < fl.batchRts[b]) a++; else b++;
+        for (size_t a = 0, b = 0; a < spans.size() && b < fl.batchSpans.size() && !shared;) {
+            if (spans[a].Overlaps(fl.batchSpans[b])) shared = true;
+            else if (spans[a].hi <= fl.batchSpans[b].lo) a++; else b++;
         }
-        if (shared) (void)hipStreamWaitEvent(pick->stream, fl.batchDone, 0);
+        if (shared) { (void)hipStreamWaitEvent(pick->stream, fl.batchDone, 0); m_lastBatchWaits++; }
     }
     return pick;
 }
 
-// the batch just queued on `fl` writes dsts[0..n): its completion event, and its targets joined to those of the lane's batches still in flight
-void CHipVideoProcessor::NoteLaneBatch(FrameLane *fl, int n, void *const *dsts)
+// the batch just queued on `fl` (m_batchSpans, from PickBatchLane): its completion event, and its spans joined to those of the lane's batches still in flight
+void CHipVideoProcessor::NoteLaneBatch(FrameLane *fl)
 {
     if (!fl->batchDone && hipEventCreateWithFlags(&fl->batchDone, hipEventDisableTiming) != hipSuccess) { fl->batchDone = nullptr; (void)hipStreamSynchronize(fl->stream); return; }
     if (fl->batchPending && hipEventQuery(fl->batchDone) == hipSuccess) fl->batchPending = false;
-    if (!fl->batchPending) fl->batchRts.clear();
-    fl->batchRts.insert(fl->batchRts.end(), dsts, dsts + n);
-    std::sort(fl->batchRts.begin(), fl->batchRts.end());
-    fl->batchRts.erase(std::unique(fl->batchRts.begin(), fl->batchRts.end()), fl->batchRts.end());
+    if (!fl->batchPending) fl->batchSpans.clear();
+    fl->batchSpans.insert(fl->batchSpans.end(), m_batchSpans.begin(), m_batchSpans.end());
+    SortAndMergeSpans(fl->batchSpans);
     (void)hipEventRecord(fl->batchDone, fl->stream);
     fl->batchPending = true;
     fl->last = fl->batchDone;
 }
 
 // the frame just queued on `fl` writes `rt`: its completion event takes the ring's oldest slot (whose frame must have completed)
-void CHipVideoProcessor::NoteLaneFrame(FrameLane *fl, const void *rt)
+void CHipVideoProcessor::NoteLaneFrame(FrameLane *fl, const RtSpan &rt)
 {
     LaneFrame &f = fl->ring[fl->head];
     fl->head = (fl->head + 1) % kLaneDepth;
@@ -333,7 +364,7 @@ HRESULT CHipVideoProcessor::JoinFrameLanes(bool host_wait)
             HRESULT h = CheckHip(hipStreamSynchronize(fl.stream), "frame lane sync");
             if (h) hr = h;
             for (LaneFrame &f : fl.ring) f.pending = false;
-            fl.batchPending = false; fl.batchRts.clear();
+            fl.batchPending = false; fl.batchSpans.clear();
             fl.last = nullptr;
         } else if (m_stream) (void)hipStreamWaitEvent(m_stream, fl.last, 0);
     }
@@ -1245,6 +1276,7 @@ bool CHipVideoProcessor::FillStripTables(const StoreParams &store, int perForce,
 bool CHipVideoProcessor::FillStripParams(const uint8_t *sample, void *dst, int dstPitch, const StoreParams &store, FusedStripParams *sp) const
 {
     FillFusedParams(sample, dst, dstPitch, &sp->fp);
+    sp->fp.dst_aligned16 = (((uintptr_t)dst) & 7) == 0;         // (8 bytes here, as in FillStripSurfParams)
     return FillStripTables(store, (m_cfg.flags & MPCVR_FLAG_FORCE_PERIOD) ? 1 : 0, sp);
 }
 
@@ -1252,7 +1284,10 @@ bool CHipVideoProcessor::FillStripParams(const uint8_t *sample, void *dst, int d
 bool CHipVideoProcessor::FillStripSurfParams(const Surface &src, const StoreParams &store, FusedStripParams *sp) const
 {
     *sp = FusedStripParams{};
-    sp->fp.dst_aligned16 = (((uintptr_t)store.dst) & 15) == 0;      // (batches: the caller knows every target of the table and overrides it)
+    // (the strip kernel decides its 8-byte stores from the pointer itself, the periodic kernel from this flag: 8 bytes is all either needs —
+    // a single frame into a target on an 8-byte boundary takes the periodic kernel like a batch into it does.  Batches: the caller knows
+    // every target of the table and overrides it)
+    sp->fp.dst_aligned16 = (((uintptr_t)store.dst) & 7) == 0;
     sp->surface_mode = 1;
     sp->surf = src;
     sp->other = m_otherX.ptr && !m_tapsX.other_identity ? (const int32_t *)m_otherX.ptr : nullptr;
@@ -1295,11 +1330,22 @@ HRESULT CHipVideoProcessor::ProcessOne(const uint8_t *sample, void *rt, int rtPi
     return ResizeShaderPass(sample, rt, rtPitch, DrawFrames{m_runConv, m_runMid, m_runPost});
 }
 
+// A render target is made of dwords (4 bytes per pixel, and no kernel stores less than one): its first byte and its pitch are multiples of 4
+// (include/mpcvr.h).  Checked in front of every launch, so a target that is refused stays untouched.
+HRESULT CHipVideoProcessor::CheckTargetLayout(int n, void *const *dsts, int rtPitch)
+{
+    if (rtPitch & 3) return Fail(MPCVR_E_INVALIDARG, "render-target pitch is not a multiple of 4");
+    for (int i = 0; i < n; i++)
+        if ((uintptr_t)dsts[i] & 3) return Fail(MPCVR_E_INVALIDARG, "render target does not start on a multiple of 4 bytes");
+    return MPCVR_S_OK;
+}
+
 // Process — DX11VideoProcessor.cpp:3285-3424
 HRESULT CHipVideoProcessor::Process(void *pRenderTarget, int rtPitch, const CRect *srcRect, const CRect *dstRect, bool /*second*/)
 {
     if (!m_bInit || !m_srcParams) return Fail(MPCVR_E_NOT_VALID_STATE, "InitMediaType has not been called");
     if (!pRenderTarget) return Fail(MPCVR_E_POINTER, "null render target");
+    if (HRESULT bad = CheckTargetLayout(1, &pRenderTarget, rtPitch)) return bad;
     if (!m_curSample) return Fail(MPCVR_E_NOT_VALID_STATE, "no sample: call CopySample first");
     if (srcRect && !srcRect->IsRectNull() && *srcRect != m_srcRect)
         return Fail(MPCVR_E_INVALIDARG, "src_rect must equal the input's source rect");
@@ -1309,7 +1355,8 @@ HRESULT CHipVideoProcessor::Process(void *pRenderTarget, int rtPitch, const CRec
     if (rtPitch < m_windowRect.Width() * 4) return Fail(MPCVR_E_INVALIDARG, "render-target pitch smaller than a row");
     if (m_planDirty && (hr = UpdatePlan())) return hr;
     UseContextResources();
-    FrameLane *fl = (m_noLanesOnce || !FrameLanesUsable()) ? nullptr : PickFrameLane(pRenderTarget);
+    const RtSpan span = TargetSpan(pRenderTarget, rtPitch);
+    FrameLane *fl = (m_noLanesOnce || !FrameLanesUsable()) ? nullptr : PickFrameLane(span);
     m_inflight = fl ? FrameLaneCount() : 1;           // the kernels size their segments for that many frames side by side
     if (fl) {
         m_run = fl->stream;
@@ -1340,7 +1387,7 @@ HRESULT CHipVideoProcessor::Process(void *pRenderTarget, int rtPitch, const CRec
     if (timeIt) (void)hipEventRecord(m_evStop, m_run);
     m_lastRun = m_run;
     MarkConsumed();
-    if (fl) NoteLaneFrame(fl, pRenderTarget);
+    if (fl) NoteLaneFrame(fl, span);
     m_inflight = 1;
     UseContextResources();
     m_timed = true;
@@ -1362,12 +1409,13 @@ HRESULT CHipVideoProcessor::ProcessBatch(int n, const void *const *srcs, void *c
 // with it (FrameLane); everything else — and every batch of a context on a caller's stream — in stream order on the context stream
 HRESULT CHipVideoProcessor::ProcessBatchRoutes(int n, const void *const *srcs, void *const *dsts, int rtPitch)
 {
-    m_lastBatchLane = -1;
+    m_lastBatchLane = -1; m_lastBatchWaits = 0;
     if (!m_bInit || !m_srcParams) return Fail(MPCVR_E_NOT_VALID_STATE, "InitMediaType has not been called");
     if (n <= 0 || !srcs || !dsts) return Fail(MPCVR_E_INVALIDARG, "empty batch");
     if (rtPitch < m_windowRect.Width() * 4) return Fail(MPCVR_E_INVALIDARG, "render-target pitch smaller than a row");
-    (void)hipSetDevice(m_device);
     HRESULT hr;
+    if ((hr = CheckTargetLayout(n, dsts, rtPitch))) return hr;
+    (void)hipSetDevice(m_device);
     if (m_planDirty && (hr = UpdatePlan())) return hr;
     for (int i = 0; i < n; i++)
         if (!srcs[i] || !dsts[i]) return Fail(MPCVR_E_POINTER, "null frame in batch");
@@ -1383,7 +1431,7 @@ HRESULT CHipVideoProcessor::ProcessBatchRoutes(int n, const void *const *srcs, v
     const bool laneRoute = rp.route == BatchRoute::FusedUp2x || rp.route == BatchRoute::Strip || rp.route == BatchRoute::DirectConvert;
     const bool onLane = laneRoute && !rp.repackSlot && !lanesOff && m_ownStream && n >= 2 && !m_doviValid && !m_dvFrames && !m_plan.errdiff && !m_plan.hdr_tonemap &&
                         !(m_cfg.flags & (MPCVR_FLAG_NO_FRAME_LANES | MPCVR_FLAG_NO_FUSED | MPCVR_FLAG_NO_FAST_CONVERT | MPCVR_FLAG_NO_STRIP));
-    FrameLane *const bl = onLane ? PickBatchLane(n, dsts) : nullptr;
+    FrameLane *const bl = onLane ? PickBatchLane(n, dsts, rtPitch) : nullptr;
     hipStream_t const ctx = m_stream;
     if (bl) {
         m_lastBatchLane = (int)(bl - m_flanes);
@@ -1397,7 +1445,7 @@ HRESULT CHipVideoProcessor::ProcessBatchRoutes(int n, const void *const *srcs, v
     hr = RunBatchRoute(rp, n, srcs, dsts, rtPitch);
     m_stream = ctx;
     UseContextResources();
-    if (bl) NoteLaneBatch(bl, n, dsts);
+    if (bl) NoteLaneBatch(bl);
     return hr;
 }
 
@@ -1637,10 +1685,11 @@ HRESULT CHipVideoProcessor::ErrDiffPass(int n, const FusedFrame *table, FusedFra
 HRESULT CHipVideoProcessor::ProcessBatchErrDiff(int n, const void *const *srcs, void *const *dsts, int rtPitch)
 {
     if (rtPitch < m_windowRect.Width() * 4) return Fail(MPCVR_E_INVALIDARG, "render-target pitch smaller than a row");
+    HRESULT hr;
+    if ((hr = CheckTargetLayout(n, dsts, rtPitch))) return hr;
     for (int i = 0; i < n; i++)
         if (!srcs[i] || !dsts[i]) return Fail(MPCVR_E_POINTER, "null frame in batch");
     (void)hipSetDevice(m_device);
-    HRESULT hr;
     const size_t one = ((size_t)((m_windowRect.Width() * 4 + 255) & ~255)) * (size_t)m_windowRect.Height();
     // intermediates for up to ~4 GiB of frames at a time, in chunks of equal size: the pass is a chain of dependent steps per frame and only
     // many frames side by side fill the chip (a 33-frame batch as 32 + 1 took 13.8 ms where 32 take 8.5: the odd frame ran alone)
@@ -1833,6 +1882,7 @@ HRESULT CHipVideoProcessor::ProcessBatchDovi(int n, const void *const *srcs, voi
 {
     if (!m_bInit || !m_srcParams) return Fail(MPCVR_E_NOT_VALID_STATE, "InitMediaType has not been called");
     if (n <= 0 || !srcs || !dsts || !rpus) return Fail(MPCVR_E_INVALIDARG, "empty batch");
+    if (HRESULT bad = CheckTargetLayout(n, dsts, rtPitch)) return bad;
     for (int i = 0; i < n; i++)         // all or nothing: no frame is drawn when one RPU of the batch is malformed
         if (!CheckDoviCurves(rpus[i])) return Fail(MPCVR_E_INVALIDARG, "Dolby Vision curves: num_pivots outside [2,9], mapping_idc > 1 or more than 32 level-2 blocks");
     (void)hipSetDevice(m_device);
@@ -1876,11 +1926,11 @@ HRESULT CHipVideoProcessor::ProcessBatchDovi(int n, const void *const *srcs, voi
     return hr;
 }
 
-// how the last mpcvr_process_batch[_dovi] call ran: "frames=<n>;launches=<kernel launches>[;dovi_runs=<frames>:<tables|frames>,...]" —
+// how the last mpcvr_process_batch[_dovi] call ran: "frames=<n>;launches=<kernel launches>;lane=<lane>;waits=<writers on other lanes it was ordered behind>[;dovi_runs=<frames>:<tables|frames>,...]" —
 // a batch on a whole-batch route launches a handful of kernels whatever n is, a frame-by-frame one at least n
 std::string CHipVideoProcessor::GetLastBatchInfo() const
 {
-    std::string s = "frames=" + std::to_string(m_lastBatchFrames) + ";launches=" + std::to_string(m_lastBatchLaunches) + ";lane=" + std::to_string(m_lastBatchLane);
+    std::string s = "frames=" + std::to_string(m_lastBatchFrames) + ";launches=" + std::to_string(m_lastBatchLaunches) + ";lane=" + std::to_string(m_lastBatchLane) + ";waits=" + std::to_string(m_lastBatchWaits);
     if (!m_dvLastInfo.empty()) s += ";dovi_runs=" + m_dvLastInfo;
     return s;
 }

@@ -181,6 +181,7 @@ private:
     unsigned m_launches = 0;                          // kernel launches so far (CheckHip) ...
     int m_lastBatchLane = -1;                                // the lane the last batch ran on (-1: the context stream)
     int m_lastBatchFrames = 0, m_lastBatchLaunches = 0;      // ... and what the last batch call used
+    HRESULT CheckTargetLayout(int n, void *const *dsts, int rtPitch);
     HRESULT ProcessBatchRoutes(int n, const void *const *srcs, void *const *dsts, int rtPitch);
     bool ToneMapActive() const;
     int m_firstAxis = 0;           // screen axis the first draw's tap table runs along
@@ -259,21 +260,29 @@ private:
     // every frame queued on a lane leaves (render target, completion event) in the lane's ring; a slot is reused only after its frame has
     // completed, which also bounds how far the host runs ahead (kFrameLanes x kLaneDepth frames)
     static constexpr int kLaneDepth = 8;
-    struct LaneFrame { const void *rt = nullptr; hipEvent_t done = nullptr; bool pending = false; };
+    // what a frame in flight writes: the bytes [lo, hi) from the first pixel of its render target to the last pixel of its last row (the padding
+    // of the rows in between counts as written: rows of two targets that interleave in one surface are ordered like rows that overlap)
+    struct RtSpan { uintptr_t lo = 0, hi = 0; bool Overlaps(const RtSpan &o) const { return lo < o.hi && o.lo < hi; } };
+    RtSpan TargetSpan(const void *rt, int rtPitch) const;
+    static void SortAndMergeSpans(std::vector<RtSpan> &v);
+    static bool SpansOverlap(const std::vector<RtSpan> &sorted, const RtSpan &s);
+    struct LaneFrame { RtSpan rt; hipEvent_t done = nullptr; bool pending = false; };
     // (round 6) WHOLE BATCHES take turns on the first two lanes as well (ProcessBatch on a context that owns its stream, a plan that is one
     // launch per batch with no intermediate surface): two launches in flight fill each other's ramp-up and tail — same box, 32-frame batches:
-    // 4K -> 8K 22.6 k -> 23.5 k frames/s, 1080p -> 1440p 99.4 k -> 115.6 k (profiles/r06/final4/bench_workloads.jsonl).  batchRts: the render targets of
-    // the lane's batches still in flight (sorted), batchDone: the event behind the last of them.
+    // 4K -> 8K 22.6 k -> 23.5 k frames/s, 1080p -> 1440p 99.4 k -> 115.6 k (profiles/r06/final4/bench_workloads.jsonl).  batchSpans: the bytes the render targets of
+    // the lane's batches still in flight cover (sorted, disjoint: spans that touch are merged), batchDone: the event behind the last of them.
     struct FrameLane { hipStream_t stream = nullptr; LaneFrame ring[kLaneDepth]; int head = 0; hipEvent_t last = nullptr; unsigned seenGen = 0;
-                       std::vector<const void *> batchRts; hipEvent_t batchDone = nullptr; bool batchPending = false; };
+                       std::vector<RtSpan> batchSpans; hipEvent_t batchDone = nullptr; bool batchPending = false; };
     static constexpr int kBatchLanes = 2;
     int m_blaneNext = 0;
-    FrameLane *PickBatchLane(int n, void *const *dsts);
-    void NoteLaneBatch(FrameLane *fl, int n, void *const *dsts);
+    int m_lastBatchWaits = 0;                 // writers still in flight on other lanes the last batch was ordered behind (GetLastBatchInfo)
+    std::vector<RtSpan> m_batchSpans;         // the batch being queued (PickBatchLane fills it, NoteLaneBatch files it)
+    FrameLane *PickBatchLane(int n, void *const *dsts, int rtPitch);
+    void NoteLaneBatch(FrameLane *fl);
     // work queued on the CONTEXT stream (a batch, a frame that ran off the lanes, a sample copy / repack, a read-back) since a lane last
     // waited for it: every such call bumps m_streamGen; a lane whose seenGen is behind waits for an event recorded on the context stream
     // (m_evStreamMark, recorded once per generation) before its next frame — a lane frame into the render target, or out of the sample, that
-    // the context stream is still writing or reading can then neither overtake nor overlap it (mpcvr.h: frames into the same target stay in order)
+    // the context stream is still writing or reading can then neither overtake nor overlap it (mpcvr.h: frames into overlapping memory stay in order)
     unsigned m_streamGen = 0, m_markGen = ~0u;
     hipEvent_t m_evStreamMark = nullptr;
     void NoteStreamWork() { m_streamGen++; }
@@ -285,9 +294,9 @@ private:
     bool m_noLanesOnce = false;               // the snapshot's Process stays on the context stream
     hipStream_t m_lastRun = nullptr;          // the stream the current sample's last Process ran on (MarkConsumed records there)
     bool FrameLanesUsable() const;
-    FrameLane *PickFrameLane(const void *rt);
+    FrameLane *PickFrameLane(const RtSpan &rt);
     HRESULT JoinFrameLanes(bool host_wait);
-    void NoteLaneFrame(FrameLane *fl, const void *rt);
+    void NoteLaneFrame(FrameLane *fl, const RtSpan &rt);
     size_t m_convBytes = 0, m_midBytes = 0, m_postBytes = 0;
     // resources of the frame being processed: the context stream's, or (Process) a frame lane's stream with the context's surfaces
     hipStream_t m_run = nullptr;
