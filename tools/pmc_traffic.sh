@@ -8,7 +8,7 @@ W=${1:-c1}; STEPS=${2:-6}; WARM=2
 OUT=gpurun_out/traffic_$W; rm -rf $OUT; mkdir -p $OUT
 for c in FETCH_SIZE WRITE_SIZE "SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY"; do
   d=${c%% *}
-  timeout -k 5 200 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/$d -o p -- python bench.py --workload $W --steps $STEPS --warmup $WARM --settle 0 --no-cpu-baseline --no-host-path > $OUT/log_$d 2>&1 || tail -2 $OUT/log_$d
+  timeout -k 5 200 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/$d -o p -- python bench.py --workload $W --steps $STEPS --warmup $WARM --settle 0 --no-cpu-baseline --no-host-path > $OUT/log_$d 2>&1 || { rc=$?; tail -2 $OUT/log_$d; exit $rc; }     # a pass that failed or ran out of time: start nothing more on the GPU
 done
 python - "$W" "$STEPS" "$WARM" <<'PY'
 import csv, glob, sys, json

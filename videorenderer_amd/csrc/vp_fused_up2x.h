@@ -14,7 +14,7 @@
 //   16-byte store per lane and output row) and marches down a segment of source rows, two rows per
 //   iteration, with no workgroup barrier inside the loop:
 //     stage C  lane j converts the 2x2 block {cols 2j,2j+1} x {rows a,a+1} of the 128-column window
-//              (4-px halo each side) from raw codes prefetched one iteration ahead and writes it, rounded to
+//              (4-px halo each side) from raw codes prefetched two iterations ahead and writes it, rounded to
 //              the internal UNORM format, to this wave's LDS slice A as (row a, row a+1) pairs
 //     stage X  lane l reads columns 2l..2l+9 (5 x ds_read_b128 per channel) and produces the 4 output
 //              columns it owns for BOTH rows at once (v_pk_fma_f32 on the row pairs); the fp16-rounded
@@ -30,6 +30,7 @@
 // -DMPCVR_UP2X_HEADLINE_ONLY (tools/isa_headline.sh): only the headline instantiation <5, PQ table, P01x, integer dither>.
 #pragma once
 #include "vp_fused_dev.h"
+#include "vp_fused_prefetch.h"
 
 namespace mpcvr {
 
@@ -37,6 +38,9 @@ namespace {
 
 #ifndef MPCVR_UP2X_WAVES
 #define MPCVR_UP2X_WAVES 3     // waves per SIMD the register allocation aims at (experiment builds: tools/build_variant.sh)
+#endif
+#ifndef MPCVR_UP2X_COMPILER_WAITS
+#define MPCVR_UP2X_COMPILER_WAITS 0    // 1 (experiment builds): the prefetch as plain loads the compiler waits for, the loop as it was before the counted wait
 #endif
 template <int NT, int TAIL, int SRC, int EPI, int XC>
 __device__ __forceinline__ void fused_up2x_body(const FusedArgs &P, const FusedFrame *__restrict__ frames, const FusedFrame &single)
@@ -114,19 +118,35 @@ __device__ __forceinline__ void fused_up2x_body(const FusedArgs &P, const FusedF
     // iteration t adds virtual rows a, a+1 with a = s0 - 3 + 2t; from t = 3 on it emits output rows of k = a-3, a-2
     const int n_iter = (s1 - s0 + 1) / 2 + 3;
     // raw codes are prefetched TWO iterations ahead, in two buffers used alternately: vmcnt counts loads and stores in issue
-    // order, so a load only reports back once the output stores issued before it have been acknowledged — with one iteration
-    // of distance every iteration waited for the previous iteration's stores
+    // order, so a load only reports back once the output stores issued before it have been acknowledged.  The fixed-count
+    // sources issue the prefetch from inline assembly and wait for it with the exact count in front of the convert stage —
+    // s_waitcnt vmcnt(loads + 8) in the steady state: the row stores of the two preceding iterations and the next prefetch stay
+    // in flight (load_raw_unseen / raw_unseen_arrived, vp_fused_prefetch.h).  SRC_GENERIC — and every source in a
+    // -DMPCVR_UP2X_COMPILER_WAITS=1 build — leaves loads and waits to the compiler, which writes vmcnt(3..0) there: each
+    // iteration then waits for the stores of the previous one and for the prefetch issued one iteration ago.
+    constexpr int NL = MPCVR_UP2X_COMPILER_WAITS ? 0 : raw_unseen_loads<SRC>();
+    constexpr bool UNSEEN = NL != 0;
     Raw raw2[2];
+    RawUnseen<raw_unseen_loads<SRC>() ? raw_unseen_loads<SRC>() : 1> pend2[2];
     RawAddr ra;
     make_raw_addr<SRC>(P, Xg, ra);
-    load_raw<SRC>(P, py, ra, clampi(s0 - 3, 0, H - 1), clampi(s0 - 2, 0, H - 1), raw2[0]);
-    load_raw<SRC>(P, py, ra, clampi(s0 - 1, 0, H - 1), clampi(s0, 0, H - 1), raw2[1]);
+    auto prefetch = [&](int ar, int b) __attribute__((always_inline)) {
+        if constexpr (UNSEEN) load_raw_unseen<SRC>(P, py, ra, clampi(ar, 0, H - 1), clampi(ar + 1, 0, H - 1), pend2[b]);
+        else load_raw<SRC>(P, py, ra, clampi(ar, 0, H - 1), clampi(ar + 1, 0, H - 1), raw2[b]);
+    };
+    prefetch(s0 - 3, 0);
+    prefetch(s0 - 1, 1);
 
-    // stage C for virtual rows ar, ar+1 (whose raw codes were prefetched into buffer b): convert, write A, prefetch rows ar+4, ar+5
-    auto stage_c = [&](int ar, int b) {
+    // stage C for virtual rows ar, ar+1 (whose raw codes were prefetched into buffer b): convert, write A, prefetch rows ar+4, ar+5;
+    // tw = the loop iteration it runs in (0 in front of the loop): what the wait for the raw codes may leave in flight
+    auto stage_c = [&](int ar, int b, int tw) {
         f2 rc[2][3];
+        if constexpr (UNSEEN) {
+            raw_unseen_arrived<NL>(tw);
+            raw_unseen_finish<SRC>(pend2[b], raw2[b]);
+        }
         convert_block<TAIL, SRC, DV_NONE, XC, XC == XC_ALWAYS ? OUT_CODE_F : OUT_NORM>(P, MM, GG, CC, raw2[b], P.rect_t + clampi(ar, 0, H - 1), P.rect_t + clampi(ar + 1, 0, H - 1), T, rc);
-        load_raw<SRC>(P, py, ra, clampi(ar + 4, 0, H - 1), clampi(ar + 5, 0, H - 1), raw2[b]);
+        prefetch(ar + 4, b);
 #pragma unroll
         for (int c = 0; c < 3; c++) {
             // store to m_TexConvertOutput (UNORM: floor(sat(x)*maxv + 0.5)) and read back (q/maxv to 1 ulp)
@@ -146,7 +166,7 @@ __device__ __forceinline__ void fused_up2x_body(const FusedArgs &P, const FusedF
     // global prefetch behind it) is covered by the Y stage instead of stalling the wave.  A is exchanged between
     // lanes of this wave only: LDS operations of one wave execute in order; the fences keep the compiler from
     // reordering the A reads and writes (which look unrelated thread by thread).
-    stage_c(s0 - 3, 0);
+    stage_c(s0 - 3, 0, 0);
 
     for (int tb = 0; tb < n_iter; tb += 4) {
 #pragma unroll
@@ -194,7 +214,7 @@ __device__ __forceinline__ void fused_up2x_body(const FusedArgs &P, const FusedF
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 
             // ---------------- stage C of the NEXT iteration ----------------
-            if (t + 1 < n_iter) stage_c(a + 2, (u + 1) & 1);
+            if (t + 1 < n_iter) stage_c(a + 2, (u + 1) & 1, t);
 
             // ---------------- stage Y + final pass ----------------
             // window slot of virtual row r is (r - (s0-3)) & 7; rows a-6 .. a+1 are live: slot(a-6+i) = (2u+2+i) & 7
