@@ -364,8 +364,12 @@ int32_t mpcvr_broadcast_param_blob(mpcvr_ctx *ctx, void *nccl_comm, int32_t root
 int32_t mpcvr_get_color_matrix(mpcvr_ctx *ctx, float out12[12]);     /* cm_r, cm_g, cm_b, cm_c */
 int32_t mpcvr_get_extfmt(mpcvr_ctx *ctx, uint32_t *extfmt);           /* after SpecifyExtendedFormat */
 int32_t mpcvr_get_frame_bytes(mpcvr_ctx *ctx, size_t *bytes, int32_t *pitch);
+/* The table image the exact-2x fused kernel stages into LDS, as baked for the current plan (two-call size protocol): 1024 uint16
+ * (the dither table's fp16 bits) | 1024 uint32 ((uint32_t)(d * 1024 + 0.5) << 14) | 4096 float pairs {lut[i], lut[min(i+1, 4095)] - lut[i]}
+ * of the plan's PQ -> SDR or HLG -> SDR table (zeros where the plan has none). */
+int32_t mpcvr_get_fused_tables(mpcvr_ctx *ctx, void *buf, size_t *size);
 int32_t mpcvr_get_path_info(mpcvr_ctx *ctx, char *buf, size_t buf_size); /* e.g. "fused_up2x" / "fused_jinc2x" / "passes:convert,resizeX,resizeY+final" */
-/* How the last mpcvr_process_batch / mpcvr_process_batch_dovi call ran: "frames=<n>;launches=<kernel launches>;lane=<lane>;waits=<n>[;dovi_runs=<frames>:<tables|frames>,...]".
+/* How the last mpcvr_process_batch / mpcvr_process_batch_dovi call ran: "frames=<n>;launches=<kernel launches>;lane=<lane>;waits=<n>;uploads=<frame tables copied to the device in the stream>[;dovi_runs=<frames>:<tables|frames>,...]".
  * A batch on a whole-batch route launches a handful of kernels whatever n is (one per stage and <= 4 GiB chunk of intermediates); a
  * frame-by-frame one at least n.  dovi_runs: the runs mpcvr_process_batch_dovi cut the frames into and whether a run read its RPUs from the
  * per-frame tables or went frame by frame. */

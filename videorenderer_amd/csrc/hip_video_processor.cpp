@@ -858,11 +858,13 @@ HRESULT CHipVideoProcessor::UpdatePlan()
         m_pqLutValid = false;
     }
     if (m_tail == TAIL_HLG_TO_SDR && !m_hlgLut.ptr) {          // constants only: built once per context
-        std::vector<float> t(kPqLutSize);
+        std::vector<float> &t = m_hlgLutHost;
+        t.resize(kPqLutSize);
         BuildHlgInverseLut(t.data());
         if ((hr = CheckHip(m_hlgLut.CheckCreate(t.size() * sizeof(float)), "hlg lut"))) return hr;
         if ((hr = CheckHip(hipMemcpy(m_hlgLut.ptr, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice), "hlg lut upload"))) return hr;
     }
+    if ((hr = UploadFusedTables())) return hr;
     m_jincFusedTab = nullptr;
     if (m_plan.fused_jinc) {
         // the fused Jinc2m kernel's weights: the phase table of a 2x draw (integer origins drop out of it) in the kernel's reading order
@@ -1091,6 +1093,10 @@ void CHipVideoProcessor::FillFusedParams(const uint8_t *sample, void *rt, int rt
     fp->jinc_tab = m_plan.fused_jinc ? m_jincFusedTab : nullptr;
     fp->exact_wide = m_plan.hdr_tonemap ? 1 : 0;
     fp->inflight = m_inflight;
+    static const bool no_baked = [] { const char *e = std::getenv("MPCVR_FUSED_NO_BAKED"); return e && *e && *e != '0'; }();     // (A/B: the kernel's own staging loops)
+    fp->baked = (m_fusedTabValid && !no_baked) ? m_fusedTab.ptr : nullptr;
+    fp->baked_lut = m_fusedTabLut;
+    fp->frames_host = nullptr;
     fp->dst_aligned16 = (((uintptr_t)rt) & 15) == 0;        // batches: ProcessBatch checks every target
     fp->src_aligned16 = (((uintptr_t)sample) & 15) == 0;
     // vectorised convert: dword loads need 4-byte aligned rows and a source rect starting on a 4-px boundary
@@ -1396,12 +1402,13 @@ HRESULT CHipVideoProcessor::Process(void *pRenderTarget, int rtPitch, const CRec
 
 HRESULT CHipVideoProcessor::ProcessBatch(int n, const void *const *srcs, void *const *dsts, int rtPitch)
 {
-    const unsigned before = m_launches;
+    const unsigned before = m_launches, uploadsBefore = m_tableUploads;
     HRESULT hr = MPCVR_S_OK;
     if (m_cfg.bUseDither == MPCVR_DITHER_ErrorDiffusion_EXT && m_bInit && m_srcParams && n > 0 && srcs && dsts && m_planDirty) hr = UpdatePlan();
     if (!hr) hr = (m_bInit && m_srcParams && n > 0 && srcs && dsts && !m_planDirty && m_plan.errdiff) ? ProcessBatchErrDiff(n, srcs, dsts, rtPitch)
                                                                                                      : ProcessBatchRoutes(n, srcs, dsts, rtPitch);
     m_lastBatchFrames = n; m_lastBatchLaunches = (int)(m_launches - before);
+    m_lastBatchUploads = (int)(m_tableUploads - uploadsBefore);
     return hr;
 }
 
@@ -1617,10 +1624,17 @@ HRESULT CHipVideoProcessor::RunBatchRoute(BatchRoutePlan &rp, int n, const void 
         hr = CheckHip(LaunchFusedStrip(rp.strip, table, FusedFrame{nullptr, nullptr}, n, m_stream), "k_fused_strip");
         break;
     case BatchRoute::FusedUp2x: {
-        if ((hr = UploadFrameTable(n, srcs, dsts, nullptr, 0, &table, &done))) break;
         FusedParams fp{};
         FillFusedParams((const uint8_t *)srcs[0], nullptr, rtPitch, &fp);
         fp.dst_aligned16 = rp.aligned ? 1 : 0;
+        // up to 32 frames travel in the exact-2x kernel's arguments: no table copy on the stream in front of the launch and no slot event
+        // behind it (the fused Jinc2m kernel, which LaunchFusedUp2x may launch instead, reads an uploaded table)
+        FusedFrame tab[32];
+        if (n <= 32 && !fp.jinc_tab) {
+            for (int i = 0; i < n; i++) tab[i] = FusedFrame{(const uint8_t *)srcs[i], dsts[i]};
+            fp.frames_host = tab;
+            table = tab;           // (LaunchFusedUp2x wants a table for n > 1; with frames_host set no kernel is handed this pointer)
+        } else if ((hr = UploadFrameTable(n, srcs, dsts, nullptr, 0, &table, &done))) break;
         start();
         hr = CheckHip(LaunchFusedUp2x(fp, table, FusedFrame{nullptr, nullptr}, n, m_stream), "k_fused_up2x");
         break;
@@ -1753,8 +1767,73 @@ HRESULT CHipVideoProcessor::UploadFrameTable(int n, const void *const *srcs, voi
     for (int i = 0; i < n; i++) { fr[i].src = srcs ? (const uint8_t *)srcs[i] : nullptr; fr[i].dst = dsts ? dsts[i] : (void *)(dst_base + (size_t)i * dst_stride); }
     if ((hr = CheckHip(hipMemcpyAsync(slot.dev.ptr, fr, sizeof(FusedFrame) * n, hipMemcpyHostToDevice, m_stream), "frame table"))) return hr;
     slot.used = true;        // the caller records *done behind the last launch that reads the table
+    m_tableUploads++;
     *dev = (const FusedFrame *)slot.dev.ptr;
     *done = slot.done;
+    return MPCVR_S_OK;
+}
+
+// The exact-2x kernel's tables as it keeps them in LDS, computed once per plan instead of by every workgroup of every launch
+// (vp_launch.h has the layout).  The expressions are the kernel prologue's own, in the same fp32 operations; the float -> unsigned
+// conversion saturates as v_cvt_u32_f32 does, so a dither table from a parameter blob gives the same words whatever it holds.
+void BakeFusedTables(const uint16_t *dither, const float *lut, void *out)
+{
+    auto half_bits_to_float = [](uint16_t h) {
+        const uint32_t sign = (uint32_t)(h & 0x8000u) << 16, e = (h >> 10) & 31u, m = h & 1023u;
+        float mag;
+        if (e == 31) { uint32_t b = 0x7f800000u | (m << 13); std::memcpy(&mag, &b, 4); }
+        else if (e == 0) mag = (float)m * (1.0f / 16777216.0f);                     // subnormal: m * 2^-24, exact
+        else { uint32_t b = ((e + 112u) << 23) | (m << 13); std::memcpy(&mag, &b, 4); }
+        uint32_t b;
+        std::memcpy(&b, &mag, 4);
+        b |= sign;
+        std::memcpy(&mag, &b, 4);
+        return mag;
+    };
+    unsigned char *o = (unsigned char *)out;
+    uint16_t *D = (uint16_t *)o;
+    uint32_t *Di = (uint32_t *)(o + 1024 * 2);
+    float *T = (float *)(o + kBakedDitherBytes);
+    for (int i = 0; i < 1024; i++) {
+        D[i] = dither[i];
+        const float x = half_bits_to_float(dither[i]) * 1024.0f + 0.5f;
+        const uint32_t j = x >= 4294967296.0f ? 0xffffffffu : x > 0.0f ? (uint32_t)x : 0u;       // (a NaN gives 0)
+        Di[i] = j << 14;
+    }
+    for (int i = 0; i < kPqLutSize; i++) {
+        const float v = lut ? lut[i] : 0.0f, n = lut ? lut[std::min(i + 1, kPqLutSize - 1)] : 0.0f;
+        T[2 * i] = v;
+        T[2 * i + 1] = n - v;
+    }
+}
+
+HRESULT CHipVideoProcessor::UploadFusedTables()
+{
+    m_fusedTabValid = false;
+    const float *host = nullptr;
+    m_fusedTabLut = nullptr;
+    if (m_tail == TAIL_PQ_TO_SDR && m_pqLutValid) { host = m_pqLutHost; m_fusedTabLut = (const float *)m_pqLut.ptr; }
+    else if (m_tail == TAIL_HLG_TO_SDR && m_hlgLut.ptr && m_hlgLutHost.size() == (size_t)kPqLutSize) { host = m_hlgLutHost.data(); m_fusedTabLut = (const float *)m_hlgLut.ptr; }
+    m_fusedTabHost.resize(kBakedTableBytes);
+    BakeFusedTables(m_ditherHost, host, m_fusedTabHost.data());
+    HRESULT hr;
+    if ((hr = CheckHip(m_fusedTab.CheckCreate(kBakedTableBytes), "fused tables"))) return hr;
+    if ((hr = CheckHip(hipMemcpy(m_fusedTab.ptr, m_fusedTabHost.data(), kBakedTableBytes, hipMemcpyHostToDevice), "fused tables upload"))) return hr;
+    m_fusedTabValid = true;
+    return MPCVR_S_OK;
+}
+
+HRESULT CHipVideoProcessor::GetFusedTables(void *buf, size_t *size)
+{
+    if (!size) return Fail(MPCVR_E_POINTER, "null size");
+    if (!m_srcParams) return Fail(MPCVR_E_NOT_VALID_STATE, "InitMediaType has not been called");
+    if (!buf) { *size = kBakedTableBytes; return MPCVR_S_OK; }
+    if (*size < (size_t)kBakedTableBytes) { *size = kBakedTableBytes; return Fail(MPCVR_E_INVALIDARG, "buffer too small"); }
+    HRESULT hr;
+    if (m_planDirty && (hr = UpdatePlan())) return hr;
+    if (!m_fusedTabValid) return Fail(MPCVR_E_NOT_VALID_STATE, "no baked tables");
+    std::memcpy(buf, m_fusedTabHost.data(), kBakedTableBytes);
+    *size = kBakedTableBytes;
     return MPCVR_S_OK;
 }
 
@@ -1926,11 +2005,12 @@ HRESULT CHipVideoProcessor::ProcessBatchDovi(int n, const void *const *srcs, voi
     return hr;
 }
 
-// how the last mpcvr_process_batch[_dovi] call ran: "frames=<n>;launches=<kernel launches>;lane=<lane>;waits=<writers on other lanes it was ordered behind>[;dovi_runs=<frames>:<tables|frames>,...]" —
+// how the last mpcvr_process_batch[_dovi] call ran: "frames=<n>;launches=<kernel launches>;lane=<lane>;waits=<writers on other lanes it was ordered behind>;uploads=<frame tables copied to the device>[;dovi_runs=<frames>:<tables|frames>,...]" —
 // a batch on a whole-batch route launches a handful of kernels whatever n is, a frame-by-frame one at least n
 std::string CHipVideoProcessor::GetLastBatchInfo() const
 {
-    std::string s = "frames=" + std::to_string(m_lastBatchFrames) + ";launches=" + std::to_string(m_lastBatchLaunches) + ";lane=" + std::to_string(m_lastBatchLane) + ";waits=" + std::to_string(m_lastBatchWaits);
+    std::string s = "frames=" + std::to_string(m_lastBatchFrames) + ";launches=" + std::to_string(m_lastBatchLaunches) + ";lane=" + std::to_string(m_lastBatchLane) + ";waits=" + std::to_string(m_lastBatchWaits) +
+                    ";uploads=" + std::to_string(m_lastBatchUploads);
     if (!m_dvLastInfo.empty()) s += ";dovi_runs=" + m_dvLastInfo;
     return s;
 }

@@ -74,6 +74,8 @@ public:
 
     HRESULT GetParamBlob(void *buf, size_t *size);
     HRESULT SetParamBlob(const void *buf, size_t size);
+    // the current plan's baked table image for the exact-2x kernel (kBakedTableBytes; two-call size protocol)
+    HRESULT GetFusedTables(void *buf, size_t *size);
     // the one collective of the path — rank `root`'s parameter blob to every rank of an RCCL communicator the host created
     // (ncclCommInitRank / ncclCommInitAll), on the context's stream.  Begin queues the broadcast (inside the host's ncclGroupStart /
     // ncclGroupEnd when one process drives several devices), End waits for it and adopts the blob on the other ranks.
@@ -180,6 +182,8 @@ private:
     unsigned m_laneFrames = 0;                        // frames queued on the frame lanes (the timing pair is recorded on every n-th)
     unsigned m_launches = 0;                          // kernel launches so far (CheckHip) ...
     int m_lastBatchLane = -1;                                // the lane the last batch ran on (-1: the context stream)
+    unsigned m_tableUploads = 0;                             // UploadFrameTable calls so far
+    int m_lastBatchUploads = 0;                              // ... of the last batch call (a table of up to 32 frames travels in the exact-2x kernel's arguments: 0)
     int m_lastBatchFrames = 0, m_lastBatchLaunches = 0;      // ... and what the last batch call used
     HRESULT CheckTargetLayout(int n, void *const *dsts, int rtPitch);
     HRESULT ProcessBatchRoutes(int n, const void *const *srcs, void *const *dsts, int rtPitch);
@@ -241,6 +245,13 @@ private:
     DevBuffer m_eotfLut;           // kEotfLutSize + 1 floats: PQ EOTF (Dolby Vision block convert), uploaded with the first RPU
     float m_pqLutHost[kPqLutSize];
     bool m_pqLutValid = false;
+    // the exact-2x kernel's table LDS image (BakeFusedTables, vp_launch.h), rebuilt by UpdatePlan from m_ditherHost and the plan's tone-map table
+    DevBuffer m_fusedTab;
+    std::vector<unsigned char> m_fusedTabHost;      // its host copy (GetFusedTables)
+    std::vector<float> m_hlgLutHost;                // what m_hlgLut holds
+    const float *m_fusedTabLut = nullptr;           // the device table its tone-map part was baked from (null: none)
+    bool m_fusedTabValid = false;
+    HRESULT UploadFusedTables();
     DevBuffer m_tapsXi, m_tapsXw, m_tapsXs, m_tapsYi, m_tapsYw, m_tapsYs, m_otherX, m_otherY, m_tapsXb, m_tapsYb;
     AxisTaps m_tapsX{}, m_tapsY{};
     // ring of frame-table slots for mpcvr_process_batch (pinned host copy + device copy + completion event)

@@ -42,8 +42,36 @@ namespace {
 #ifndef MPCVR_UP2X_COMPILER_WAITS
 #define MPCVR_UP2X_COMPILER_WAITS 0    // 1 (experiment builds): the prefetch as plain loads the compiler waits for, the loop as it was before the counted wait
 #endif
+static_assert(LDS_D + LDS_DB == kBakedDitherBytes && LDS_D + LDS_DB + LDS_T == kBakedTableBytes, "the baked image is the LDS layout");
+static_assert(LDS_A % 16 == 0 && LDS_D + LDS_DB == 256 * 16 + 256 * 8 && LDS_T == 8 * 256 * 16, "stage_baked_tables: pieces per thread");
+
+// The baked table image (BakeFusedTables, vp_launch.h) into LDS: every thread issues all its loads back to back — one 16-byte and one
+// 8-byte piece of the dither tables, eight 16-byte pieces of the tone-map table — and only then stores them, so a workgroup pays one
+// round trip to memory where the loops below pay one per 256 entries.
+template <bool WITH_LUT>
+__device__ __forceinline__ void stage_baked_tables(unsigned char *tables, const unsigned char *__restrict__ img)
+{
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+    const int t = threadIdx.x;
+    const u32x4 d0 = ((const u32x4 *)img)[t];
+    const u32x2 d1 = ((const u32x2 *)(img + 256 * 16))[t];
+    u32x4 l[8];
+    if (WITH_LUT) {
+#pragma unroll
+        for (int k = 0; k < 8; k++) l[k] = ((const u32x4 *)(img + LDS_D + LDS_DB))[t + 256 * k];
+    }
+    ((u32x4 *)tables)[t] = d0;
+    ((u32x2 *)(tables + 256 * 16))[t] = d1;
+    if (WITH_LUT) {
+#pragma unroll
+        for (int k = 0; k < 8; k++) ((u32x4 *)(tables + LDS_D + LDS_DB))[t + 256 * k] = l[k];
+    }
+}
+
 template <int NT, int TAIL, int SRC, int EPI, int XC>
-__device__ __forceinline__ void fused_up2x_body(const FusedArgs &P, const FusedFrame *__restrict__ frames, const FusedFrame &single)
+__device__ __forceinline__ void fused_up2x_body(const FusedArgs &P, const FusedFrame *__restrict__ frames, const unsigned char *__restrict__ baked,
+                                                const FrameTable32 &tab)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float *Aall = (float *)smem;
@@ -51,16 +79,19 @@ __device__ __forceinline__ void fused_up2x_body(const FusedArgs &P, const FusedF
     uint32_t *Di = (uint32_t *)(smem + LDS_A + LDS_D);
     f2 *T = (f2 *)(smem + LDS_A + LDS_D + LDS_DB);
 
-    for (int i = threadIdx.x; i < 1024; i += 256) {
-        const unsigned short d = P.dither[i];
-        D[i] = d;
-        Di[i] = (uint32_t)(__half2float(__ushort_as_half(d)) * 1024.0f + 0.5f) << 14;     // d = j/1024 exactly (dither32x32float16.bin)
-    }
-    if (tail_has_table(TAIL))
-        for (int i = threadIdx.x; i < LUT_N; i += 256) {
-            const float v = P.lut[i], n = P.lut[min(i + 1, LUT_N - 1)];
-            T[i] = f2{v, n - v};
+    if (baked) stage_baked_tables<tail_has_table(TAIL)>(smem + LDS_A, baked);
+    else {                                             // no image for this launch: the tables from their sources, 256 entries per round trip
+        for (int i = threadIdx.x; i < 1024; i += 256) {
+            const unsigned short d = P.dither[i];
+            D[i] = d;
+            Di[i] = (uint32_t)(__half2float(__ushort_as_half(d)) * 1024.0f + 0.5f) << 14;     // d = j/1024 exactly (dither32x32float16.bin)
         }
+        if (tail_has_table(TAIL))
+            for (int i = threadIdx.x; i < LUT_N; i += 256) {
+                const float v = P.lut[i], n = P.lut[min(i + 1, LUT_N - 1)];
+                T[i] = f2{v, n - v};
+            }
+    }
     __syncthreads();                                   // the only workgroup barrier: tables visible
 
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;      // (wave-uniform, and the compiler should know)
@@ -72,7 +103,13 @@ __device__ __forceinline__ void fused_up2x_body(const FusedArgs &P, const FusedF
     float *A = Aall + wave * A_FLOATS;
 
     // the frame table entry is wave-uniform; readfirstlane tells the compiler so (SGPR bases => saddr loads/stores)
-    const FusedFrame frame = frames ? frames[blockIdx.z] : single;
+    // (tab: up to 32 frames in the kernel arguments — scalar loads from the kernarg segment; a single frame is its entry 0)
+    // (read unconditionally, the index kept inside the table, and pinned in SGPRs: left a choice between the two POINTERS the compiler
+    // makes this one flat vector load)
+    uint64_t tab_src = (uint64_t)tab.f[blockIdx.z & 31].src, tab_dst = (uint64_t)tab.f[blockIdx.z & 31].dst;
+    asm volatile("" : "+s"(tab_src), "+s"(tab_dst));
+    FusedFrame frame{(const uint8_t *)tab_src, (void *)tab_dst};
+    if (frames) frame = frames[blockIdx.z];
     auto uniform_ptr = [](const void *q) {
         const uint64_t v = (uint64_t)q;
         return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
@@ -320,9 +357,10 @@ __device__ __forceinline__ void fused_up2x_body(const FusedArgs &P, const FusedF
 }
 
 template <int NT, int TAIL, int SRC, int EPI, int XC = XC_NEVER>
-__global__ __launch_bounds__(256, MPCVR_UP2X_WAVES) void k_fused_up2x(FusedArgs P, const FusedFrame *__restrict__ frames, FusedFrame single)
+__global__ __launch_bounds__(256, MPCVR_UP2X_WAVES) void k_fused_up2x(FusedArgs P, const FusedFrame *__restrict__ frames, const unsigned char *__restrict__ baked,
+                                                                      FrameTable32 tab)
 {
-    fused_up2x_body<NT, TAIL, SRC, EPI, XC>(P, frames, single);
+    fused_up2x_body<NT, TAIL, SRC, EPI, XC>(P, frames, baked, tab);
 }
 // the kernel of an instantiation: its exact-form twin where one exists and the launch asks for it (exact_capable, vp_fused_dev.h)
 template <int NT, int TAIL, int SRC, int EPI>
@@ -346,6 +384,17 @@ hipError_t LaunchFusedUp2xNT(const FusedParams &P, const FusedArgs &a_in, int st
     const FusedArgs &a = a_in;
     const size_t lds = LDS_A + LDS_D + LDS_DB + (tail_has_table(tailk) ? LDS_T : 0) + (size_t)lds_pad;
     const int srck = FusedSourceKind(P);
+    // the table image is staged instead of the tables' sources when it was baked from this launch's tone-map table (or the kernel reads none)
+    const unsigned char *baked = (P.baked && (((uintptr_t)P.baked) & 15) == 0 && (!tail_has_table(tailk) || (P.baked_lut && P.baked_lut == a.lut)))
+                                     ? (const unsigned char *)P.baked : nullptr;
+    // up to 32 frames by value: a host table, or the single frame as entry 0; the kernel reads frames_dev only where it is handed one
+    FrameTable32 tab{};
+    if (n_frames <= 32 && (P.frames_host || !frames_dev)) {
+        if (!P.frames_host && n_frames != 1) return hipErrorInvalidValue;
+        tab.n = n_frames;
+        for (int i = 0; i < n_frames; i++) tab.f[i] = P.frames_host ? P.frames_host[i] : single;
+        frames_dev = nullptr;
+    } else if (!frames_dev) return hipErrorInvalidValue;
     // the specialised epilogues use 16-byte stores / dither reads: off_x % 4 == 0 and 16-byte aligned rows; the integer
     // final pass additionally needs k*M + (j << 14) < 2^32 and M < 2^24 (true for 10-bit internal -> 8-bit target)
     const bool aligned = P.dst_aligned16 && (a.off_x & 3) == 0 && (a.dst_pitch & 15) == 0;
@@ -354,7 +403,7 @@ hipError_t LaunchFusedUp2xNT(const FusedParams &P, const FusedArgs &a_in, int st
                    : (!a.final_pass && P.store.dst_fmt == SF_BGRA8 && P.store.quant == 255) ? EPI_DIRECT8
                    : (!a.final_pass && P.store.dst_fmt == SF_RGB10A2 && P.store.quant == 1023) ? EPI_DIRECT8 : EPI_GENERIC;
     // instantiated (source, epilogue) pairs: each source with the epilogue it normally meets + the generic one
-#define MPCVR_LAUNCH3(NTK, TK, SK, EK) hipLaunchKernelGGL((fused_up2x_kernel<NTK, TK, SK, EK>(a.exact_cv != 0)), grid, block, lds, s, a, frames_dev, single)
+#define MPCVR_LAUNCH3(NTK, TK, SK, EK) hipLaunchKernelGGL((fused_up2x_kernel<NTK, TK, SK, EK>(a.exact_cv != 0)), grid, block, lds, s, a, frames_dev, baked, tab)
 #define MPCVR_LAUNCH(NT, TK) do { \
         if (srck == SRC_P01X && epik == EPI_DITHER8) MPCVR_LAUNCH3(NT, TK, SRC_P01X, EPI_DITHER8); \
         else if (srck == SRC_P01X && epik == EPI_DIRECT8) MPCVR_LAUNCH3(NT, TK, SRC_P01X, EPI_DIRECT8); \

@@ -81,7 +81,21 @@ struct FusedParams {
                               // (FusedArgs::exact_cv).  LaunchFusedUp2x / LaunchFusedStrip set it themselves; the block convert's callers say so.
     int inflight;             // single-frame launches: frames the host keeps running side by side (the context's frame lanes), 0 / 1 = none.  The
                               // segment rules count them like frames of a batch: four overlapping 4K frames fill the chip with long segments
+    // exact-2x kernel (vp_fused_up2x.h), both optional:
+    const void *baked;        // device, kBakedTableBytes on a 16-byte boundary: the kernel's table LDS image (BakeFusedTables), staged in one burst of
+                              // 16-byte loads; null => the kernel derives the tables from store.dither and the tone-map table, as the other fused kernels do
+    const float *baked_lut;   // the device table the image's tone-map part was baked from (pq_lut, hlg_lut or null): an image baked from another
+                              // table than the launch's is not used
+    const FusedFrame *frames_host;   // host, n_frames entries, n_frames <= 32: the frame table travels by value in the kernel arguments and
+                              // frames_dev is not handed to the kernel (LaunchFusedUp2x still wants it non-null for n_frames > 1)
 };
+// The LDS image of the fused kernels' read-only tables, byte for byte what their prologue computes (vp_fused_dev.h: LDS_D | LDS_DB | LDS_T):
+//   D[1024]  uint16   the dither table's fp16 bits
+//   Di[1024] uint32   (uint32_t)(half(d) * 1024.0f + 0.5f) << 14
+//   T[4096]  float[2] {lut[i], lut[min(i + 1, 4095)] - lut[i]}      (zeros when the plan has no tone-map table)
+enum { kBakedDitherBytes = 1024 * 2 + 1024 * 4, kBakedTableBytes = kBakedDitherBytes + kPqLutSize * 8 };
+// dither: 1024 fp16 bit patterns; lut: kPqLutSize floats or null; out: kBakedTableBytes of host memory
+void BakeFusedTables(const uint16_t *dither, const float *lut, void *out);
 // vp_errdiff.hip — the error-diffusion final pass (EXTENSION, bUseDither = 2; definition in vp_errdiff_core.h): frame z's R10G10B10A2 image
 // (frames[z].src, window geometry, src_pitch) -> its B8G8R8A8 render target (frames[z].dst, dst_pitch) inside [x0, x1) x [y0, y1)
 struct ErrDiffParams {
