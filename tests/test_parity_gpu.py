@@ -1235,7 +1235,9 @@ DOVI_BATCH_CASES = (
 def test_process_batch_dovi_one_rpu_per_frame(mpcvr, oracle, torch_cuda, label):
     """mpcvr_process_batch_dovi: frame i of the batch runs on rpus[i].  Must equal, bit for bit, the reference's own pattern — the RPU read
     from every sample: SetDoviMetadata + CopySample + Process frame after frame on a second context — and the oracle run with frame i's
-    RPU; the whole-batch routes must really be taken (GetVPInfo names the runs), and the context must end up on the last RPU."""
+    RPU; the whole-batch routes must really be taken (GetVPInfo names the runs), and the context must end up on the last RPU.  Nothing of a
+    Dolby Vision batch outlives the call: a plain batch behind it runs on the context's own RPU and reports no runs, and a batch behind a
+    refused one equals the loop as before."""
     torch = torch_cuda
     from videorenderer_amd import api, synth
     from tests.golden import cases as G
@@ -1292,6 +1294,21 @@ def test_process_batch_dovi_one_rpu_per_frame(mpcvr, oracle, torch_cuda, label):
     vp.Process(again, ww * 4)
     vp.Synchronize()
     assert torch.equal(again, dsts[-1]), label
+    if label in ("same_size_sdr", "resized_sdr"):
+        # a plain batch behind it, on the RPU the context still holds: equals CopySample + Process of the same frames there, and its record is its
+        # own (mpcvr.h: the string describes the last call) — no runs of the Dolby Vision batch before it
+        plain = [torch.full((wh, ww, 4), BG, dtype=torch.uint8, device="cuda") for _ in range(3)]
+        vp.ProcessBatch(frames[:3], plain, ww * 4)
+        vp.Synchronize()
+        plain_route = vp.GetLastBatchInfo()
+        for i in range(3):
+            alone = torch.full((wh, ww, 4), BG, dtype=torch.uint8, device="cuda")
+            vp.CopySample(frames[i], pitch)
+            vp.Process(alone, ww * 4)
+            vp.Synchronize()
+            assert torch.equal(plain[i], alone), (label, "plain batch after the Dolby Vision batch", i, plain_route)
+        assert not torch.equal(plain[0], dsts[0])       # (frame 0 on the last RPU, not on its own)
+        assert plain_route["frames"] == 3 and plain_route["dovi_runs"] == "", plain_route
     # a second batch through the same context: the table slots are reused; starts on the sticky level-2 state like the loop would
     dsts2 = [torch.full((wh, ww, 4), BG, dtype=torch.uint8, device="cuda") for _ in range(3)]
     vp.ProcessBatchDovi(frames[:3], dsts2, ww * 4, rpus[:3])
@@ -1313,6 +1330,13 @@ def test_process_batch_dovi_one_rpu_per_frame(mpcvr, oracle, torch_cuda, label):
         vp.ProcessBatchDovi(frames[:2], untouched, ww * 4, [rpus[0], bad])
     vp.Synchronize()
     assert all(bool((u == BG).all()) for u in untouched)
+    if label in ("same_size_sdr", "resized_sdr"):
+        # ... and nothing of the refused call is left in the context: the batch before it, once more
+        dsts3 = [torch.full((wh, ww, 4), BG, dtype=torch.uint8, device="cuda") for _ in range(3)]
+        vp.ProcessBatchDovi(frames[:3], dsts3, ww * 4, rpus[:3])
+        vp.Synchronize()
+        for i in range(3):
+            assert torch.equal(singles2[i], dsts3[i]), (label, "batch after the refused one", i, vp.GetLastBatchInfo())
     vp.close(); one.close()
     if c.get("hdr_tonemap"):
         return          # (level-1 data stay as last seen: the loop above is the statement of that; the tone-mapping step has its own oracle tests)

@@ -77,22 +77,14 @@ CHipVideoProcessor::~CHipVideoProcessor()
         if (d.pinned) (void)hipHostFree(d.pinned);
         if (d.copied) (void)hipEventDestroy(d.copied);
     }
-    for (DoviTableSlot &d : m_dvSlots) {
-        d.dev.Release();
-        if (d.pinned) (void)hipHostFree(d.pinned);
-        if (d.done) (void)hipEventDestroy(d.done);
-    }
+    for (TableSlot &ts : m_dvSlots) ts.Release();
     if (m_evStreamMark) (void)hipEventDestroy(m_evStreamMark);
     for (FrameLane &fl : m_flanes) {
         if (fl.stream) { (void)hipStreamSynchronize(fl.stream); (void)hipStreamDestroy(fl.stream); }
         for (LaneFrame &f : fl.ring) if (f.done) (void)hipEventDestroy(f.done);
         if (fl.batchDone) (void)hipEventDestroy(fl.batchDone);
     }
-    for (FrameSlot &fs : m_slots) {
-        fs.dev.Release();
-        if (fs.pinned) (void)hipHostFree(fs.pinned);
-        if (fs.done) (void)hipEventDestroy(fs.done);
-    }
+    for (TableSlot &ts : m_slots) ts.Release();
     if (m_evStart) (void)hipEventDestroy(m_evStart);
     if (m_evStop) (void)hipEventDestroy(m_evStop);
     for (hipEvent_t *e : {&m_evUp0, &m_evUp1, &m_evRb0, &m_evRb1}) { if (*e) (void)hipEventDestroy(*e); *e = nullptr; }
@@ -1056,7 +1048,7 @@ void CHipVideoProcessor::FillConvertParams(const uint8_t *sample, ConvertParams 
     P->lum_scale = m_lumScale;
     std::memcpy(P->gamut, m_gamut, sizeof(m_gamut));
     P->out_fmt = m_plan.internal_fmt;
-    P->dovi = !m_doviValid ? nullptr : m_dvTabDev ? m_dvTabDev : (const DoviParams *)m_doviDev.ptr;     // (m_dvTabDev: one RPU per frame, ProcessBatchDovi)
+    P->dovi = m_doviValid ? (const DoviParams *)m_doviDev.ptr : nullptr;        // (one RPU per frame: RunBatchRoute points a whole-batch launch at the run's tables)
     P->pq_lut = (m_pqLutValid && !(m_cfg.flags & (MPCVR_FLAG_NO_LUT | MPCVR_FLAG_NO_FUSED))) ? (const float *)m_pqLut.ptr : nullptr;
 }
 
@@ -1089,7 +1081,7 @@ void CHipVideoProcessor::FillFusedParams(const uint8_t *sample, void *rt, int rt
     fp->hlg_lut = (m_tail == TAIL_HLG_TO_SDR && !no_lut) ? (const float *)m_hlgLut.ptr : nullptr;
     fp->eotf_lut = (m_doviValid && !no_lut) ? (const float *)m_eotfLut.ptr : nullptr;
     fp->dovi_l2 = (m_doviValid && m_doviHost.l2_enabled) ? 1 : 0;
-    fp->dovi_cm = (m_doviValid && m_dvTabDev) ? m_dvCmDev : nullptr;
+    fp->dovi_cm = nullptr;
     fp->jinc_tab = m_plan.fused_jinc ? m_jincFusedTab : nullptr;
     fp->exact_wide = m_plan.hdr_tonemap ? 1 : 0;
     fp->inflight = m_inflight;
@@ -1387,7 +1379,7 @@ HRESULT CHipVideoProcessor::Process(void *pRenderTarget, int rtPitch, const CRec
         // EXTENSION (bUseDither = 2): the draws render into the window-sized R10G10B10A2 intermediate, as for a 10-bit swap chain; the
         // error-diffusion pass takes it to the render target
         if (!(hr = PrepareErrDiff(1)) && !(hr = ProcessOne(m_curSample, m_edBase, m_edPitch)))
-            hr = ErrDiffPass(1, nullptr, FusedFrame{m_edBase, pRenderTarget}, &pRenderTarget, rtPitch, m_run);
+            hr = ErrDiffPass(1, nullptr, FusedFrame{m_edBase, pRenderTarget}, rtPitch, m_run);
     } else
         hr = ProcessOne(m_curSample, pRenderTarget, rtPitch);
     if (timeIt) (void)hipEventRecord(m_evStop, m_run);
@@ -1400,33 +1392,44 @@ HRESULT CHipVideoProcessor::Process(void *pRenderTarget, int rtPitch, const CRec
     return hr;
 }
 
-HRESULT CHipVideoProcessor::ProcessBatch(int n, const void *const *srcs, void *const *dsts, int rtPitch)
+// What every batch entry point starts with: the call's record (GetLastBatchInfo) starts empty — RunBatch adds what each run of the call
+// uses — and the arguments are checked once, before anything is applied or queued
+HRESULT CHipVideoProcessor::BeginBatch(int n, const void *const *srcs, void *const *dsts, int rtPitch)
 {
-    const unsigned before = m_launches, uploadsBefore = m_tableUploads;
-    HRESULT hr = MPCVR_S_OK;
-    if (m_cfg.bUseDither == MPCVR_DITHER_ErrorDiffusion_EXT && m_bInit && m_srcParams && n > 0 && srcs && dsts && m_planDirty) hr = UpdatePlan();
-    if (!hr) hr = (m_bInit && m_srcParams && n > 0 && srcs && dsts && !m_planDirty && m_plan.errdiff) ? ProcessBatchErrDiff(n, srcs, dsts, rtPitch)
-                                                                                                     : ProcessBatchRoutes(n, srcs, dsts, rtPitch);
-    m_lastBatchFrames = n; m_lastBatchLaunches = (int)(m_launches - before);
-    m_lastBatchUploads = (int)(m_tableUploads - uploadsBefore);
-    return hr;
-}
-
-// One batch: validated, classified once (ClassifyBatch), then run on one of two lanes beside the batch before it when its route shares nothing
-// with it (FrameLane); everything else — and every batch of a context on a caller's stream — in stream order on the context stream
-HRESULT CHipVideoProcessor::ProcessBatchRoutes(int n, const void *const *srcs, void *const *dsts, int rtPitch)
-{
-    m_lastBatchLane = -1; m_lastBatchWaits = 0;
+    m_lastBatchFrames = n; m_lastBatchLaunches = m_lastBatchUploads = 0; m_lastBatchLane = -1; m_lastBatchWaits = 0;
+    m_dvLastInfo.clear();
     if (!m_bInit || !m_srcParams) return Fail(MPCVR_E_NOT_VALID_STATE, "InitMediaType has not been called");
     if (n <= 0 || !srcs || !dsts) return Fail(MPCVR_E_INVALIDARG, "empty batch");
     if (rtPitch < m_windowRect.Width() * 4) return Fail(MPCVR_E_INVALIDARG, "render-target pitch smaller than a row");
-    HRESULT hr;
-    if ((hr = CheckTargetLayout(n, dsts, rtPitch))) return hr;
-    (void)hipSetDevice(m_device);
-    if (m_planDirty && (hr = UpdatePlan())) return hr;
+    if (HRESULT bad = CheckTargetLayout(n, dsts, rtPitch)) return bad;
     for (int i = 0; i < n; i++)
         if (!srcs[i] || !dsts[i]) return Fail(MPCVR_E_POINTER, "null frame in batch");
-    BatchRoutePlan rp = ClassifyBatch(n, srcs, dsts, rtPitch);
+    return MPCVR_S_OK;
+}
+
+HRESULT CHipVideoProcessor::ProcessBatch(int n, const void *const *srcs, void *const *dsts, int rtPitch)
+{
+    if (HRESULT bad = BeginBatch(n, srcs, dsts, rtPitch)) return bad;
+    BatchRun run{n, srcs, dsts, rtPitch};
+    return RunBatch(run);
+}
+
+HRESULT CHipVideoProcessor::RunBatch(BatchRun &run)
+{
+    const unsigned before = m_launches, uploadsBefore = m_tableUploads;
+    (void)hipSetDevice(m_device);
+    HRESULT hr = m_planDirty ? UpdatePlan() : MPCVR_S_OK;
+    if (!hr) hr = m_plan.errdiff ? ProcessBatchErrDiff(run) : ProcessBatchRoutes(run);
+    m_lastBatchLaunches += (int)(m_launches - before);
+    m_lastBatchUploads += (int)(m_tableUploads - uploadsBefore);
+    return hr;
+}
+
+// One batch: classified once (ClassifyBatch), then run on one of two lanes beside the batch before it when its route shares nothing
+// with it (FrameLane); everything else — and every batch of a context on a caller's stream — in stream order on the context stream
+HRESULT CHipVideoProcessor::ProcessBatchRoutes(BatchRun &run)
+{
+    BatchRoutePlan rp = ClassifyBatch(run);
     // The same rule as for single frames — nothing a batch touches may be shared with the batch beside it — read off the route the batch takes:
     // the exact-2x kernel, the strip / periodic kernel reading the samples themselves, the same-size block convert (no intermediate surface; a
     // repacked v210 batch reads the shared m_batchTex); default tier only.  Two launches in flight were measured to pay on every such route (same
@@ -1436,9 +1439,9 @@ HRESULT CHipVideoProcessor::ProcessBatchRoutes(int n, const void *const *srcs, v
     // Jinc2m +4 %.  (An earlier table that had the strip kernels LOSE was a wall clock around 30 launches of 0.3 ms: it measured the closing synchronize.)
     static const bool lanesOff = [] { const char *e = std::getenv("MPCVR_NO_BATCH_LANES"); return e && *e && *e != '0'; }();
     const bool laneRoute = rp.route == BatchRoute::FusedUp2x || rp.route == BatchRoute::Strip || rp.route == BatchRoute::DirectConvert;
-    const bool onLane = laneRoute && !rp.repackSlot && !lanesOff && m_ownStream && n >= 2 && !m_doviValid && !m_dvFrames && !m_plan.errdiff && !m_plan.hdr_tonemap &&
+    const bool onLane = laneRoute && !rp.repackSlot && !lanesOff && m_ownStream && run.n >= 2 && !m_doviValid && !run.dvFrames && !m_plan.errdiff && !m_plan.hdr_tonemap &&
                         !(m_cfg.flags & (MPCVR_FLAG_NO_FRAME_LANES | MPCVR_FLAG_NO_FUSED | MPCVR_FLAG_NO_FAST_CONVERT | MPCVR_FLAG_NO_STRIP));
-    FrameLane *const bl = onLane ? PickBatchLane(n, dsts, rtPitch) : nullptr;
+    FrameLane *const bl = onLane ? PickBatchLane(run.n, run.dsts, run.rtPitch) : nullptr;
     hipStream_t const ctx = m_stream;
     if (bl) {
         m_lastBatchLane = (int)(bl - m_flanes);
@@ -1449,7 +1452,7 @@ HRESULT CHipVideoProcessor::ProcessBatchRoutes(int n, const void *const *srcs, v
         NoteStreamWork();                    // ... and single frames queued after it run behind the batch (LaneWaitsForStream)
     }
     UseContextResources();
-    hr = RunBatchRoute(rp, n, srcs, dsts, rtPitch);
+    const HRESULT hr = RunBatchRoute(rp, run);
     m_stream = ctx;
     UseContextResources();
     if (bl) NoteLaneBatch(bl);
@@ -1458,8 +1461,11 @@ HRESULT CHipVideoProcessor::ProcessBatchRoutes(int n, const void *const *srcs, v
 
 // The route of a batch, from the plan and the frames' pointers alone: nothing is launched, allocated or written here.  The pointers of
 // buffers RunBatchRoute may still (re)allocate are left null in the parameters (their checks do not read them).
-CHipVideoProcessor::BatchRoutePlan CHipVideoProcessor::ClassifyBatch(int n, const void *const *srcs, void *const *dsts, int rtPitch) const
+CHipVideoProcessor::BatchRoutePlan CHipVideoProcessor::ClassifyBatch(const BatchRun &run) const
 {
+    const int n = run.n, rtPitch = run.rtPitch;
+    const void *const *const srcs = run.srcs;
+    void *const *const dsts = run.dsts;
     BatchRoutePlan rp;
     const bool v210 = m_srcParams->cformat == MPCVR_CF_V210, rgb = m_srcParams->layout == LAY_RGB;
     const bool fast = !(m_cfg.flags & (MPCVR_FLAG_NO_FUSED | MPCVR_FLAG_NO_FAST_CONVERT)), fastStrip = fast && !(m_cfg.flags & MPCVR_FLAG_NO_STRIP);
@@ -1481,11 +1487,11 @@ CHipVideoProcessor::BatchRoutePlan CHipVideoProcessor::ClassifyBatch(int n, cons
     const StoreParams target = MakeStore(dsts[0], rtPitch, m_plan.swap_fmt, true);
     // the arbitrary-ratio fused kernel takes the whole batch in one launch, like the 2x kernel
     FusedStripParams sp{};
-    const bool strip = m_strip && !m_plan.fused_up2x && !m_plan.hdr_tonemap && rp.src4 && !m_dvFrames && FillStripParams(sample0, dsts[0], rtPitch, target, &sp);
+    const bool strip = m_strip && !m_plan.fused_up2x && !m_plan.hdr_tonemap && rp.src4 && !run.dvFrames && FillStripParams(sample0, dsts[0], rtPitch, target, &sp);
     // pass-per-kernel path, whole batch per launch: possible when every stage has a kernel with a frame dimension.  One RPU per frame
     // (ProcessBatchDovi): the block convert's Dolby Vision variants index the run's tables by the frame; the HDR10 tone-mapping step takes
     // its level-1 constants by value, so such a run goes frame by frame
-    const bool batchable = !m_plan.fused_up2x && !strip && n > 1 && rp.src4 && fast && !(m_dvFrames && (!m_dvTabReady || m_plan.hdr_tonemap)) &&
+    const bool batchable = !m_plan.fused_up2x && !strip && n > 1 && rp.src4 && fast && !(run.dvFrames && (!run.dvTab || m_plan.hdr_tonemap)) &&
                            BatchPlan(sample0, dsts[0], rtPitch, rp.aligned, rp.repackSlot != 0, rp.src16, &rp.conv, &rp.direct);
     auto take = [&rp](BatchRoute r) { rp.route = r; return rp; };
     if (batchable && m_plan.direct_convert) return take(BatchRoute::DirectConvert);
@@ -1512,10 +1518,13 @@ CHipVideoProcessor::BatchRoutePlan CHipVideoProcessor::ClassifyBatch(int n, cons
 }
 
 // the launches of a classified batch on m_stream (the context stream or a lane's)
-HRESULT CHipVideoProcessor::RunBatchRoute(BatchRoutePlan &rp, int n, const void *const *srcs, void *const *dsts, int rtPitch)
+HRESULT CHipVideoProcessor::RunBatchRoute(BatchRoutePlan &rp, BatchRun &run)
 {
+    const int n = run.n, rtPitch = run.rtPitch;
+    const void *const *srcs = run.srcs;
+    void *const *const dsts = run.dsts;
     HRESULT hr = MPCVR_S_OK;
-    bool started = m_keepStart;                         // m_evStart sits in front of the batch's first launch (the repack's, if any)
+    bool started = run.started;                         // m_evStart sits in front of the batch's first launch (the repack's, if any)
     auto start = [&] { if (!started) (void)hipEventRecord(m_evStart, m_stream); started = true; };
     std::vector<const void *> slots;
     if (rp.repackSlot) {
@@ -1527,15 +1536,14 @@ HRESULT CHipVideoProcessor::RunBatchRoute(BatchRoutePlan &rp, int n, const void 
         for (int i = 0; i < n; i++) slots[i] = (uint8_t *)m_batchTex.ptr + (size_t)i * rp.repackSlot;
         srcs = slots.data();
     }
-    if (m_dvFrames && (rp.route == BatchRoute::DirectConvert || rp.route == BatchRoute::WholeBatchLaunches)) {
-        // one RPU per frame: the block convert reads the run's tables (what FillConvertParams / FillFusedParams point the kernels at from here on)
-        m_dvTabDev = m_dvTabReady; m_dvCmDev = m_dvCmReady;
-        if (m_doviValid) { rp.direct.conv.dovi = rp.conv.conv.dovi = m_dvTabDev; rp.direct.dovi_cm = rp.conv.dovi_cm = m_dvCmDev; }
+    if (run.dvFrames && (rp.route == BatchRoute::DirectConvert || rp.route == BatchRoute::WholeBatchLaunches)) {
+        // one RPU per frame: the block convert indexes the run's tables by the frame (ClassifyBatch takes these routes only with the tables uploaded)
+        run.usedTables = true;
+        rp.direct.conv.dovi = rp.conv.conv.dovi = run.dvTab; rp.direct.dovi_cm = rp.conv.dovi_cm = run.dvCm;
     }
     // The frame table travels through a small ring of pinned/device slots so the host can queue several batches ahead; a slot is reused
-    // only after the launches that read it have completed (`done`, recorded behind them).
-    const FusedFrame *table = nullptr;
-    hipEvent_t done = nullptr;
+    // only after the launches that read it have completed (the lease records its event behind them, at the end of this function).
+    SlotLease table;
     switch (rp.route) {
     case BatchRoute::DirectConvert:
         if (n <= kHostTableMax) {
@@ -1547,9 +1555,9 @@ HRESULT CHipVideoProcessor::RunBatchRoute(BatchRoutePlan &rp, int n, const void 
             const hipError_t e = LaunchConvertBlocks(rp.direct, nullptr, FusedFrame{nullptr, nullptr}, n, m_stream, 0, tab);
             if (e != hipErrorInvalidValue || n <= 32) { hr = CheckHip(e, "k_convert_blocks"); break; }
         }
-        if ((hr = UploadFrameTable(n, srcs, dsts, nullptr, 0, &table, &done))) break;
+        if ((hr = UploadFrameTable(n, srcs, dsts, nullptr, 0, &table))) break;
         start();
-        hr = CheckHip(LaunchConvertBlocks(rp.direct, table, FusedFrame{nullptr, nullptr}, n, m_stream), "k_convert_blocks");
+        hr = CheckHip(LaunchConvertBlocks(rp.direct, table.frames(), FusedFrame{nullptr, nullptr}, n, m_stream), "k_convert_blocks");
         break;
     case BatchRoute::RgbSurfaceStrip: {
         // Interleaved RGB without a convert draw (m_PSConvColorData.bEnable false, :849-853): every frame is repacked into its own slot of a
@@ -1563,7 +1571,7 @@ HRESULT CHipVideoProcessor::RunBatchRoute(BatchRoutePlan &rp, int n, const void 
         // texels the reference's copy loop never writes (RGB48 remainder) stay zero, as in PrepareSample
         if (fresh && (hr = CheckHip(hipMemsetAsync(m_batchTex.ptr, 0, texBytes * chunk, m_stream), "clear batch texture"))) break;
         m_batchTexZeroed = true;
-        if ((hr = UploadFrameTable(n, srcs, dsts, nullptr, 0, &table, &done))) break;
+        if ((hr = UploadFrameTable(n, srcs, dsts, nullptr, 0, &table))) break;
         rp.strip.surf.ptr = m_batchTex.ptr;
         rp.strip.surf_stride = texBytes;
         rp.strip.fp.dst_aligned16 = rp.aligned8 ? 1 : 0;
@@ -1572,7 +1580,7 @@ HRESULT CHipVideoProcessor::RunBatchRoute(BatchRoutePlan &rp, int n, const void 
             const int m = std::min(chunk, n - at);
             hr = CheckHip(LaunchRepackRgb(m_srcParams->repack, nullptr, m_srcBottomUp ? -m_srcPitch : m_srcPitch, (uint8_t *)m_batchTex.ptr, tp,
                                           m_srcWidth, m_srcHeight, m_stream, srcs + at, m, texBytes), "k_repack_rgb");
-            if (!hr) hr = CheckHip(LaunchFusedStrip(rp.strip, table + at, FusedFrame{nullptr, nullptr}, m, m_stream), "k_fused_strip<surface>");
+            if (!hr) hr = CheckHip(LaunchFusedStrip(rp.strip, table.frames() + at, FusedFrame{nullptr, nullptr}, m, m_stream), "k_fused_strip<surface>");
         }
         break;
     }
@@ -1590,15 +1598,12 @@ HRESULT CHipVideoProcessor::RunBatchRoute(BatchRoutePlan &rp, int n, const void 
         start();
         for (int at = 0; at < n && !hr; at += chunk) {
             const int m = std::min(chunk, n - at);
-            const FusedFrame *drawTab = nullptr, *realTab = nullptr;
-            hipEvent_t d1 = nullptr, d2 = nullptr;
-            if ((hr = UploadFrameTable(m, srcs + at, nullptr, (uint8_t *)m_batchPost.ptr, postStride, &drawTab, &d1))) break;
-            if ((hr = UploadFrameTable(m, srcs + at, dsts + at, nullptr, 0, &realTab, &d2))) break;
-            ResizeBatch tb; tb.n = m; tb.in_stride = postStride; tb.frames = realTab;
-            if (!(hr = CheckHip(LaunchFusedStrip(rp.strip, drawTab, FusedFrame{nullptr, nullptr}, m, m_stream), "k_fused_strip")))
+            SlotLease drawTab, realTab;            // (both until the end of the chunk's two launches)
+            if ((hr = UploadFrameTable(m, srcs + at, nullptr, (uint8_t *)m_batchPost.ptr, postStride, &drawTab))) break;
+            if ((hr = UploadFrameTable(m, srcs + at, dsts + at, nullptr, 0, &realTab))) break;
+            ResizeBatch tb; tb.n = m; tb.in_stride = postStride; tb.frames = realTab.frames();
+            if (!(hr = CheckHip(LaunchFusedStrip(rp.strip, drawTab.frames(), FusedFrame{nullptr, nullptr}, m, m_stream), "k_fused_strip")))
                 hr = CheckHip(LaunchHdr10ToneMap(post, m_hdrTm, w2, h2, MakeStore(dsts[at], rtPitch, m_plan.swap_fmt, true), m_stream, &tb), "k_hdr10_tonemap");
-            (void)hipEventRecord(d1, m_stream);
-            (void)hipEventRecord(d2, m_stream);
         }
         break;
     }
@@ -1608,20 +1613,20 @@ HRESULT CHipVideoProcessor::RunBatchRoute(BatchRoutePlan &rp, int n, const void 
         for (int i = 0; i < n && !hr; i++) {
             const uint8_t *tex = (const uint8_t *)srcs[i];           // (repacked: already in m_TexSrcVideo's layout, a slot of the batch texture)
             if (!rp.repackSlot && (hr = PrepareSample((const uint8_t *)srcs[i], &tex))) break;
-            if (m_dvFrames && (hr = ApplyDoviFrame(m_dvFrames[i]))) break;          // this frame's RPU: constants, matrix, tone-mapping metadata
+            if (run.dvFrames && (hr = ApplyDoviFrame(run.dvFrames[i]))) break;          // this frame's RPU: constants, matrix, tone-mapping metadata
             hr = ProcessOne(tex, dsts[i], rtPitch);
         }
         break;
     case BatchRoute::WholeBatchLaunches:
-        if ((hr = UploadFrameTable(n, srcs, dsts, nullptr, 0, &table, &done))) break;
+        if ((hr = UploadFrameTable(n, srcs, dsts, nullptr, 0, &table))) break;
         start();
-        hr = ProcessBatchLaunches(n, table, dsts[0], rtPitch, rp.aligned, rp.conv);
+        hr = ProcessBatchLaunches(run, table.frames(), rp.aligned, rp.conv);
         break;
     case BatchRoute::Strip:
-        if ((hr = UploadFrameTable(n, srcs, dsts, nullptr, 0, &table, &done))) break;
+        if ((hr = UploadFrameTable(n, srcs, dsts, nullptr, 0, &table))) break;
         rp.strip.fp.dst_aligned16 = rp.aligned8 ? 1 : 0;
         start();
-        hr = CheckHip(LaunchFusedStrip(rp.strip, table, FusedFrame{nullptr, nullptr}, n, m_stream), "k_fused_strip");
+        hr = CheckHip(LaunchFusedStrip(rp.strip, table.frames(), FusedFrame{nullptr, nullptr}, n, m_stream), "k_fused_strip");
         break;
     case BatchRoute::FusedUp2x: {
         FusedParams fp{};
@@ -1633,15 +1638,14 @@ HRESULT CHipVideoProcessor::RunBatchRoute(BatchRoutePlan &rp, int n, const void 
         if (n <= 32 && !fp.jinc_tab) {
             for (int i = 0; i < n; i++) tab[i] = FusedFrame{(const uint8_t *)srcs[i], dsts[i]};
             fp.frames_host = tab;
-            table = tab;           // (LaunchFusedUp2x wants a table for n > 1; with frames_host set no kernel is handed this pointer)
-        } else if ((hr = UploadFrameTable(n, srcs, dsts, nullptr, 0, &table, &done))) break;
+        } else if ((hr = UploadFrameTable(n, srcs, dsts, nullptr, 0, &table))) break;
         start();
-        hr = CheckHip(LaunchFusedUp2x(fp, table, FusedFrame{nullptr, nullptr}, n, m_stream), "k_fused_up2x");
+        // (LaunchFusedUp2x wants a table for n > 1; with frames_host set no kernel is handed this pointer)
+        hr = CheckHip(LaunchFusedUp2x(fp, fp.frames_host ? tab : table.frames(), FusedFrame{nullptr, nullptr}, n, m_stream), "k_fused_up2x");
         break;
     }
     }
     (void)hipEventRecord(m_evStop, m_stream);
-    if (done) (void)hipEventRecord(done, m_stream);
     m_timed = true;
     return hr;
 }
@@ -1661,14 +1665,13 @@ HRESULT CHipVideoProcessor::PrepareErrDiff(int frames)
     return hr;
 }
 
-HRESULT CHipVideoProcessor::ErrDiffPass(int n, const FusedFrame *table, FusedFrame single, void *const *dsts, int rtPitch, hipStream_t s)
+HRESULT CHipVideoProcessor::ErrDiffPass(int n, const FusedFrame *table, FusedFrame single, int rtPitch, hipStream_t s)
 {
     ErrDiffParams P{};
     P.x0 = std::max((int)m_videoRect.left, 0); P.y0 = std::max((int)m_videoRect.top, 0);
     P.x1 = std::min((int)m_videoRect.right, m_windowRect.Width()); P.y1 = std::min((int)m_videoRect.bottom, m_windowRect.Height());
     if (P.x1 <= P.x0 || P.y1 <= P.y0) return MPCVR_S_OK;          // the video rect lies outside the window: nothing is drawn
     P.src_pitch = m_edPitch; P.dst_pitch = rtPitch;
-    (void)dsts;
     // band-major ticket order: same box, 32 frames 4K -> 8K: 3.85 k frames/s against 3.28 k frame-major (profiles/r04/ab_call24_errdiff_order.jsonl)
     static const int order = [] { const char *e = std::getenv("MPCVR_ERRDIFF_ORDER"); return e ? std::atoi(e) : 1; }();
     P.order = order;
@@ -1696,14 +1699,11 @@ HRESULT CHipVideoProcessor::ErrDiffPass(int n, const FusedFrame *table, FusedFra
     return CheckHip(LaunchErrorDiffusion(P, table, single, n, s), "k_error_diffusion");
 }
 
-HRESULT CHipVideoProcessor::ProcessBatchErrDiff(int n, const void *const *srcs, void *const *dsts, int rtPitch)
+// a validated batch of an error-diffusion plan (RunBatch): chunks of frames through the routes into the intermediates, a pass behind each
+HRESULT CHipVideoProcessor::ProcessBatchErrDiff(BatchRun &run)
 {
-    if (rtPitch < m_windowRect.Width() * 4) return Fail(MPCVR_E_INVALIDARG, "render-target pitch smaller than a row");
+    const int n = run.n;
     HRESULT hr;
-    if ((hr = CheckTargetLayout(n, dsts, rtPitch))) return hr;
-    for (int i = 0; i < n; i++)
-        if (!srcs[i] || !dsts[i]) return Fail(MPCVR_E_POINTER, "null frame in batch");
-    (void)hipSetDevice(m_device);
     const size_t one = ((size_t)((m_windowRect.Width() * 4 + 255) & ~255)) * (size_t)m_windowRect.Height();
     // intermediates for up to ~4 GiB of frames at a time, in chunks of equal size: the pass is a chain of dependent steps per frame and only
     // many frames side by side fill the chip (a 33-frame batch as 32 + 1 took 13.8 ms where 32 take 8.5: the odd frame ran alone)
@@ -1713,63 +1713,66 @@ HRESULT CHipVideoProcessor::ProcessBatchErrDiff(int n, const void *const *srcs, 
     const int chunks = (n + most - 1) / most;
     const int chunk = (n + chunks - 1) / chunks;
     if ((hr = PrepareErrDiff(chunk))) return hr;
-    bool usedTables = false;         // (ProcessBatchDovi reports per run whether the per-frame tables were read)
     std::vector<void *> mids(chunk);
     for (int i = 0; i < chunk; i++) mids[i] = m_edBase + (size_t)i * m_edStride;
     // the batch's process time runs from in front of the first chunk to behind the last chunk's pass
     (void)JoinFrameLanes(false);
     (void)hipEventRecord(m_evStart, m_stream);
-    m_keepStart = true;
-    struct KeepStartGuard { bool &f; ~KeepStartGuard() { f = false; } } keepGuard{m_keepStart};
     for (int at = 0; at < n; at += chunk) {
         const int m = std::min(chunk, n - at);
         // the whole-batch routes of the 10-bit plan, into the intermediates (the previous chunk's pass reads them in stream order); a run of
-        // ProcessBatchDovi hands its per-frame RPU state over by frame index: the chunk sees its own slice
-        const DoviFrameState *const dvFrames = m_dvFrames;
-        const DoviParams *const dvTab = m_dvTabReady;
-        const float *const dvCm = m_dvCmReady;
-        if (m_dvFrames) m_dvFrames += at;
-        if (m_dvTabReady) { m_dvTabReady += at; m_dvCmReady += (size_t)12 * at; }
-        if (m_dvFrames) { m_dvTabDev = nullptr; m_dvCmDev = nullptr; }      // (a chunk that goes frame by frame must not read the tables the chunk before it took)
-        hr = ProcessBatchRoutes(m, srcs + at, mids.data(), m_edPitch);
-        m_dvFrames = dvFrames; m_dvTabReady = dvTab; m_dvCmReady = dvCm;
+        // ProcessBatchDovi: the chunk sees its own slice of the per-frame RPU state
+        BatchRun part = run.Slice(at, m);
+        part.dsts = mids.data(); part.rtPitch = m_edPitch; part.started = true;
+        hr = ProcessBatchRoutes(part);
+        run.usedTables = run.usedTables || part.usedTables;
         if (hr) return hr;
-        usedTables = usedTables || m_dvTabDev != nullptr;
-        const FusedFrame *tab = nullptr;
-        hipEvent_t done = nullptr;
-        if ((hr = UploadFrameTable(m, (const void *const *)mids.data(), dsts + at, nullptr, 0, &tab, &done))) return hr;
-        hr = ErrDiffPass(m, tab, FusedFrame{nullptr, nullptr}, dsts + at, rtPitch, m_stream);
-        (void)hipEventRecord(done, m_stream);
-        if (hr) return hr;
+        SlotLease tab;
+        if ((hr = UploadFrameTable(m, (const void *const *)mids.data(), run.dsts + at, nullptr, 0, &tab))) return hr;
+        if ((hr = ErrDiffPass(m, tab.frames(), FusedFrame{nullptr, nullptr}, run.rtPitch, m_stream))) return hr;
     }
-    if (m_dvFrames && usedTables && !m_dvTabDev) { m_dvTabDev = m_dvTabReady; m_dvCmDev = m_dvCmReady; }
     (void)hipEventRecord(m_evStop, m_stream);       // (the batch's process time includes the pass)
     m_timed = true;
     return MPCVR_S_OK;
 }
 
-HRESULT CHipVideoProcessor::UploadFrameTable(int n, const void *const *srcs, void *const *dsts, uint8_t *dst_base, size_t dst_stride, const FusedFrame **dev, hipEvent_t *done)
+void CHipVideoProcessor::TableSlot::Release()
 {
-    HRESULT hr;
-    FrameSlot &slot = m_slots[m_slotNext];
-    m_slotNext = (m_slotNext + 1) % kFrameSlots;
-    if (!slot.done && (hr = CheckHip(hipEventCreateWithFlags(&slot.done, hipEventDisableTiming), "slot event"))) return hr;
-    if (slot.used && (hr = CheckHip(hipEventSynchronize(slot.done), "slot wait"))) return hr;
-    if ((size_t)n > slot.cap) {
+    dev.Release();
+    if (pinned) (void)hipHostFree(pinned);
+    if (done) (void)hipEventDestroy(done);
+}
+
+// A slot of the frame-table or the Dolby Vision table ring on loan: free to be rewritten (the launches behind its last lease have completed)
+// and large enough for `bytes` (allocated for `atLeast` or more, so that batches of growing size do not reallocate one by one).  An event
+// that was never recorded counts as complete.
+HRESULT CHipVideoProcessor::AcquireSlot(TableSlot &slot, size_t bytes, size_t atLeast, SlotLease *lease)
+{
+    HRESULT hr = slot.done ? CheckHip(hipEventSynchronize(slot.done), "table slot wait")
+                           : CheckHip(hipEventCreateWithFlags(&slot.done, hipEventDisableTiming), "table slot event");
+    if (hr) return hr;
+    if (bytes > slot.cap) {
         if (slot.pinned) (void)hipHostFree(slot.pinned);
         slot.pinned = nullptr; slot.cap = 0;
-        const size_t cap = n < 64 ? 64 : (size_t)n;
-        if ((hr = CheckHip(hipHostMalloc(&slot.pinned, sizeof(FusedFrame) * cap, hipHostMallocDefault), "frames pinned"))) return hr;
-        if ((hr = CheckHip(slot.dev.CheckCreate(sizeof(FusedFrame) * cap), "frames"))) return hr;
+        const size_t cap = std::max(bytes, atLeast);
+        if ((hr = CheckHip(hipHostMalloc(&slot.pinned, cap, hipHostMallocDefault), "table slot pinned"))) return hr;
+        if ((hr = CheckHip(slot.dev.CheckCreate(cap), "table slot"))) return hr;
         slot.cap = cap;
     }
+    *lease = SlotLease(slot.dev.ptr, slot.done, m_stream);
+    return MPCVR_S_OK;
+}
+
+HRESULT CHipVideoProcessor::UploadFrameTable(int n, const void *const *srcs, void *const *dsts, uint8_t *dst_base, size_t dst_stride, SlotLease *lease)
+{
+    HRESULT hr;
+    TableSlot &slot = m_slots[m_slotNext];
+    m_slotNext = (m_slotNext + 1) % kFrameSlots;
+    if ((hr = AcquireSlot(slot, sizeof(FusedFrame) * n, sizeof(FusedFrame) * 64, lease))) return hr;
     FusedFrame *fr = (FusedFrame *)slot.pinned;
     for (int i = 0; i < n; i++) { fr[i].src = srcs ? (const uint8_t *)srcs[i] : nullptr; fr[i].dst = dsts ? dsts[i] : (void *)(dst_base + (size_t)i * dst_stride); }
     if ((hr = CheckHip(hipMemcpyAsync(slot.dev.ptr, fr, sizeof(FusedFrame) * n, hipMemcpyHostToDevice, m_stream), "frame table"))) return hr;
-    slot.used = true;        // the caller records *done behind the last launch that reads the table
     m_tableUploads++;
-    *dev = (const FusedFrame *)slot.dev.ptr;
-    *done = slot.done;
     return MPCVR_S_OK;
 }
 
@@ -1861,8 +1864,9 @@ bool CHipVideoProcessor::BatchPlan(const uint8_t *sample0, void *rt0, int rtPitc
 }
 
 // convert all -> first draw all -> second draw all, a frame dimension in every grid; the intermediates hold `chunk` frames
-HRESULT CHipVideoProcessor::ProcessBatchLaunches(int n, const FusedFrame *table, void *rt0, int rtPitch, bool aligned, FusedParams conv)
+HRESULT CHipVideoProcessor::ProcessBatchLaunches(const BatchRun &run, const FusedFrame *table, bool aligned, FusedParams conv)
 {
+    const int n = run.n;
     HRESULT hr;
     // intermediates for up to `chunk` frames (at most ~4 GiB)
     const bool hdr = m_plan.hdr_tonemap;
@@ -1875,9 +1879,10 @@ HRESULT CHipVideoProcessor::ProcessBatchLaunches(int n, const FusedFrame *table,
     DrawFrames df{m_batchConv.ptr, m_batchMid.ptr, m_batchPost.ptr, m_convBytes, m_midBytes, postStride};
     // HDR10 tone-mapping step: the draws write frame z's post-scale texture (a second frame table whose targets are the slots of
     // m_batchPost), then ONE k_hdr10_tonemap launch per chunk writes the render targets (:3359-3367)
-    hipEvent_t postDone = nullptr;
+    SlotLease postTab;
     if (hdr) {
-        if ((hr = UploadFrameTable(chunk, nullptr, nullptr, (uint8_t *)m_batchPost.ptr, postStride, &df.lastTab, &postDone))) return hr;
+        if ((hr = UploadFrameTable(chunk, nullptr, nullptr, (uint8_t *)m_batchPost.ptr, postStride, &postTab))) return hr;
+        df.lastTab = postTab.frames();
         aligned = true;             // the slots of m_batchPost start on 256-byte boundaries
     }
     df.aligned = aligned ? 1 : 0;
@@ -1885,14 +1890,14 @@ HRESULT CHipVideoProcessor::ProcessBatchLaunches(int n, const FusedFrame *table,
         const int m = std::min(chunk, n - at);
         // frame z of the chunk: sample from the table, output at m_batchConv + z * m_convBytes
         conv.store.dst = m_batchConv.ptr;
-        if (m_dvTabDev) { conv.conv.dovi = m_dvTabDev + at; conv.dovi_cm = m_dvCmDev + (size_t)12 * at; }       // (the chunk's slice of the per-frame RPU tables)
+        const BatchRun part = run.Slice(at, m);
+        if (part.dvTab) { conv.conv.dovi = part.dvTab; conv.dovi_cm = part.dvCm; }       // (the chunk's slice of the per-frame RPU tables)
         if ((hr = CheckHip(LaunchConvertBlocks(conv, table + at, FusedFrame{nullptr, nullptr}, m, m_stream, m_convBytes), "k_convert_blocks"))) return hr;
         df.n = m;
         df.rtTab = table + at;
         if (!hdr) df.lastTab = df.rtTab;
-        if ((hr = ResizeShaderPass(nullptr, rt0, rtPitch, df))) return hr;
+        if ((hr = ResizeShaderPass(nullptr, run.dsts[0], run.rtPitch, df))) return hr;
     }
-    if (postDone) (void)hipEventRecord(postDone, m_stream);
     return MPCVR_S_OK;
 }
 
@@ -1927,48 +1932,34 @@ HRESULT CHipVideoProcessor::ApplyDoviFrame(const DoviFrameState &f)
 }
 
 // DoviParams[n] followed by cm[12 n], staged through one of two pinned / device slots (a slot is rewritten only after the launches
-// that read it have completed: `done`, recorded by ProcessBatchDovi behind the run)
-HRESULT CHipVideoProcessor::UploadDoviTables(int n, hipEvent_t *done)
+// that read it have completed: the lease, which ProcessBatchDovi keeps until the run is queued); fills run->dvTab / dvCm
+HRESULT CHipVideoProcessor::UploadDoviTables(BatchRun *run, SlotLease *lease)
 {
+    const int n = run->n;
     HRESULT hr;
-    DoviTableSlot &slot = m_dvSlots[m_dvSlotNext++ % 2];
-    if (!slot.done && (hr = CheckHip(hipEventCreateWithFlags(&slot.done, hipEventDisableTiming), "dovi table event"))) return hr;
-    if (slot.used && (hr = CheckHip(hipEventSynchronize(slot.done), "dovi table wait"))) return hr;
-    const size_t need = (size_t)n * (sizeof(DoviParams) + 12 * sizeof(float));
-    if (need > slot.cap) {
-        if (slot.pinned) (void)hipHostFree(slot.pinned);
-        slot.pinned = nullptr; slot.cap = 0;
-        const size_t cap = std::max<size_t>(need, 64 * (sizeof(DoviParams) + 12 * sizeof(float)));
-        if ((hr = CheckHip(hipHostMalloc(&slot.pinned, cap, hipHostMallocDefault), "dovi tables pinned"))) return hr;
-        if ((hr = CheckHip(slot.dev.CheckCreate(cap), "dovi tables"))) return hr;
-        slot.cap = cap;
-    }
+    TableSlot &slot = m_dvSlots[m_dvSlotNext++ % 2];
+    const size_t each = sizeof(DoviParams) + 12 * sizeof(float), need = each * n;
+    if ((hr = AcquireSlot(slot, need, each * 64, lease))) return hr;
     DoviParams *tp = (DoviParams *)slot.pinned;
     float *tc = (float *)(tp + n);
     for (int i = 0; i < n; i++) {
-        tp[i] = m_dvFrames[i].p;
-        std::memcpy(tc + (size_t)12 * i, m_dvFrames[i].cm, 12 * sizeof(float));
+        tp[i] = run->dvFrames[i].p;
+        std::memcpy(tc + (size_t)12 * i, run->dvFrames[i].cm, 12 * sizeof(float));
     }
     if ((hr = CheckHip(hipMemcpyAsync(slot.dev.ptr, slot.pinned, need, hipMemcpyHostToDevice, m_stream), "dovi tables upload"))) return hr;
-    m_dvTabReady = (const DoviParams *)slot.dev.ptr;
-    m_dvCmReady = (const float *)((const DoviParams *)slot.dev.ptr + n);
-    slot.used = true;
-    *done = slot.done;
+    run->dvTab = (const DoviParams *)slot.dev.ptr;
+    run->dvCm = (const float *)(run->dvTab + n);
     return MPCVR_S_OK;
 }
 
 HRESULT CHipVideoProcessor::ProcessBatchDovi(int n, const void *const *srcs, void *const *dsts, int rtPitch, const mpcvr_dovi_metadata *rpus)
 {
-    if (!m_bInit || !m_srcParams) return Fail(MPCVR_E_NOT_VALID_STATE, "InitMediaType has not been called");
-    if (n <= 0 || !srcs || !dsts || !rpus) return Fail(MPCVR_E_INVALIDARG, "empty batch");
-    if (HRESULT bad = CheckTargetLayout(n, dsts, rtPitch)) return bad;
+    if (HRESULT bad = BeginBatch(n, rpus ? srcs : nullptr, dsts, rtPitch)) return bad;        // (no RPUs: an empty batch, like no samples)
     for (int i = 0; i < n; i++)         // all or nothing: no frame is drawn when one RPU of the batch is malformed
         if (!CheckDoviCurves(rpus[i])) return Fail(MPCVR_E_INVALIDARG, "Dolby Vision curves: num_pivots outside [2,9], mapping_idc > 1 or more than 32 level-2 blocks");
     (void)hipSetDevice(m_device);
     HRESULT hr = MPCVR_S_OK;
     std::vector<DoviFrameState> fs((size_t)n);
-    m_dvLastInfo.clear();
-    int launches = 0;
     auto collect = [&](int i) { fs[i].p = m_doviHost; std::memcpy(fs[i].cm, m_cm, sizeof(m_cm)); fs[i].tm = m_hdrTm; };
     DoviWalkState back;
     for (int i = 0; i < n && !hr;) {
@@ -1986,22 +1977,15 @@ HRESULT CHipVideoProcessor::ProcessBatchDovi(int n, const void *const *srcs, voi
         }
         if (hr) break;
         const int len = j - i;
-        m_dvFrames = fs.data() + i; m_dvCount = len;
-        m_dvTabReady = nullptr; m_dvCmReady = nullptr; m_dvTabDev = nullptr; m_dvCmDev = nullptr;
-        hipEvent_t done = nullptr;
-        if (len > 1 && !m_plan.hdr_tonemap) hr = UploadDoviTables(len, &done);
-        if (!hr) hr = ProcessBatch(len, srcs + i, dsts + i, rtPitch);
-        const bool tables = m_dvTabDev != nullptr;
-        launches += m_lastBatchLaunches;
-        m_dvLastInfo += (m_dvLastInfo.empty() ? "" : ",") + std::to_string(len) + (tables ? ":tables" : ":frames");
-        m_dvFrames = nullptr; m_dvCount = 0;
-        m_dvTabReady = nullptr; m_dvCmReady = nullptr; m_dvTabDev = nullptr; m_dvCmDev = nullptr;
-        if (done) (void)hipEventRecord(done, m_stream);
+        BatchRun run{len, srcs + i, dsts + i, rtPitch, fs.data() + i};
+        SlotLease tables;           // (until the run is queued)
+        if (len > 1 && !m_plan.hdr_tonemap) hr = UploadDoviTables(&run, &tables);
+        if (!hr) hr = RunBatch(run);
+        m_dvLastInfo += (m_dvLastInfo.empty() ? "" : ",") + std::to_string(len) + (run.usedTables ? ":tables" : ":frames");
         // the context's own copy of the constants: the run's last frame (a whole-batch route did not touch it)
-        if (!hr && tables) hr = UploadDoviParams();
+        if (!hr && run.usedTables) hr = UploadDoviParams();
         i = j;
     }
-    m_lastBatchFrames = n; m_lastBatchLaunches = launches;
     return hr;
 }
 

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/mpcvr.h"
@@ -92,7 +93,6 @@ public:
 private:
     HRESULT Fail(HRESULT hr, const std::string &msg);
     HRESULT CheckHip(hipError_t e, const char *what);
-    bool IsInit() const { return m_bInit; }
 
     // mirrors of the reference's private helpers
     void SetShaderConvertColorParams();                  // :813
@@ -167,18 +167,47 @@ private:
     };
     void SaveDoviWalk(DoviWalkState *s) const;
     void RestoreDoviWalk(const DoviWalkState &s);
-    const DoviFrameState *m_dvFrames = nullptr;       // set around ProcessBatch by ProcessBatchDovi: the frames of the run in flight
-    int m_dvCount = 0;
-    const DoviParams *m_dvTabReady = nullptr;         // device tables of the run, uploaded: DoviParams[n], then cm[12 n] ...
-    const float *m_dvCmReady = nullptr;
-    const DoviParams *m_dvTabDev = nullptr;           // ... and in use: ProcessBatch took a whole-batch route (FillConvertParams / FillFusedParams point the kernels at them)
-    const float *m_dvCmDev = nullptr;
-    struct DoviTableSlot { void *pinned = nullptr; size_t cap = 0; DevBuffer dev; hipEvent_t done = nullptr; bool used = false; };
-    DoviTableSlot m_dvSlots[2];
+    // One batch call in flight, handed down by reference from ProcessBatch / ProcessBatchDovi to the launches: the frames and, for a run of
+    // ProcessBatchDovi, its per-frame RPU state.  Nothing of it outlives the call.
+    struct BatchRun {
+        int n = 0;
+        const void *const *srcs = nullptr;
+        void *const *dsts = nullptr;
+        int rtPitch = 0;
+        const DoviFrameState *dvFrames = nullptr;      // one RPU per frame: the frames of the run (null: the context's own RPU, if any)
+        const DoviParams *dvTab = nullptr;             // ... and its tables on the device, DoviParams[n] then cm[12 n] (null: not uploaded, the run goes frame by frame)
+        const float *dvCm = nullptr;
+        bool started = false;                          // m_evStart is in place already (error diffusion: in front of the first chunk)
+        bool usedTables = false;                       // out: a whole-batch route read dvTab / dvCm
+        BatchRun Slice(int at, int m) const {          // the frames [at, at + m), every per-frame pointer advanced together
+            BatchRun r = *this;
+            r.n = m; r.srcs += at; r.dsts += at;
+            if (dvFrames) r.dvFrames += at;
+            if (dvTab) { r.dvTab += at; r.dvCm += (size_t)12 * at; }
+            r.usedTables = false;
+            return r;
+        }
+    };
+    // A ring slot (frame table, Dolby Vision tables) on loan: leaving scope records the slot's event on the stream the copy was queued on, that is
+    // behind every launch queued there since, and the slot is rewritten only after that event.  Scope = the last launch that reads the slot.
+    struct SlotLease {
+        const void *dev = nullptr; hipEvent_t done = nullptr; hipStream_t stream = nullptr;
+        SlotLease() = default;
+        SlotLease(const void *d, hipEvent_t e, hipStream_t s) : dev(d), done(e), stream(s) {}
+        SlotLease(SlotLease &&o) noexcept : dev(o.dev), done(o.done), stream(o.stream) { o.done = nullptr; }             // (move-only: copies are deleted with it)
+        SlotLease &operator=(SlotLease &&o) noexcept { std::swap(dev, o.dev); std::swap(done, o.done); std::swap(stream, o.stream); return *this; }     // (what was here leaves with o)
+        ~SlotLease() { if (done) (void)hipEventRecord(done, stream); }
+        const FusedFrame *frames() const { return (const FusedFrame *)dev; }
+    };
+    // a slot of a table ring (the frame tables of a batch, the Dolby Vision tables of a run): pinned host copy, device copy of `cap` bytes, and
+    // the event behind the last launch that reads it (SlotLease)
+    struct TableSlot { void *pinned = nullptr; size_t cap = 0; DevBuffer dev; hipEvent_t done = nullptr; void Release(); };
+    HRESULT AcquireSlot(TableSlot &slot, size_t bytes, size_t atLeast, SlotLease *lease);
+    TableSlot m_dvSlots[2];
     unsigned m_dvSlotNext = 0;
-    HRESULT UploadDoviTables(int n, hipEvent_t *done);
+    HRESULT UploadDoviTables(BatchRun *run, SlotLease *lease);
     HRESULT ApplyDoviFrame(const DoviFrameState &f);
-    std::string m_dvLastInfo;                         // the runs of the last ProcessBatchDovi call (GetLastBatchInfo: ";dovi_runs=3:tables,1:frames")
+    std::string m_dvLastInfo;                         // the runs of the last batch call, if it was a ProcessBatchDovi (GetLastBatchInfo: ";dovi_runs=3:tables,1:frames")
     unsigned m_laneFrames = 0;                        // frames queued on the frame lanes (the timing pair is recorded on every n-th)
     unsigned m_launches = 0;                          // kernel launches so far (CheckHip) ...
     int m_lastBatchLane = -1;                                // the lane the last batch ran on (-1: the context stream)
@@ -186,7 +215,9 @@ private:
     int m_lastBatchUploads = 0;                              // ... of the last batch call (a table of up to 32 frames travels in the exact-2x kernel's arguments: 0)
     int m_lastBatchFrames = 0, m_lastBatchLaunches = 0;      // ... and what the last batch call used
     HRESULT CheckTargetLayout(int n, void *const *dsts, int rtPitch);
-    HRESULT ProcessBatchRoutes(int n, const void *const *srcs, void *const *dsts, int rtPitch);
+    HRESULT BeginBatch(int n, const void *const *srcs, void *const *dsts, int rtPitch);         // opens the call's record and checks what every batch entry point checks
+    HRESULT RunBatch(BatchRun &run);                  // a validated batch: the plan, then error diffusion or the routes
+    HRESULT ProcessBatchRoutes(BatchRun &run);
     bool ToneMapActive() const;
     int m_firstAxis = 0;           // screen axis the first draw's tap table runs along
     bool m_firstSwap = false;      // rotation 90/270: taps address the other texture axis
@@ -256,8 +287,7 @@ private:
     AxisTaps m_tapsX{}, m_tapsY{};
     // ring of frame-table slots for mpcvr_process_batch (pinned host copy + device copy + completion event)
     static constexpr int kFrameSlots = 4;
-    struct FrameSlot { void *pinned = nullptr; DevBuffer dev; size_t cap = 0; hipEvent_t done = nullptr; bool used = false; };
-    FrameSlot m_slots[kFrameSlots];
+    TableSlot m_slots[kFrameSlots];
     int m_slotNext = 0;
     uint16_t m_ditherHost[1024];
     // mpcvr_process frame after frame (the reference's own call pattern, Render -> Process, DX11VideoProcessor.cpp:2730): a single 4K
@@ -331,14 +361,13 @@ private:
     int m_edPitch = 0;             // bytes per row of an intermediate (a multiple of 256)
     size_t m_edStride = 0;         // bytes per intermediate
     HRESULT PrepareErrDiff(int frames);
-    HRESULT ErrDiffPass(int n, const FusedFrame *table, FusedFrame single, void *const *dsts, int rtPitch, hipStream_t s);
-    HRESULT ProcessBatchErrDiff(int n, const void *const *srcs, void *const *dsts, int rtPitch);
+    HRESULT ErrDiffPass(int n, const FusedFrame *table, FusedFrame single, int rtPitch, hipStream_t s);
+    HRESULT ProcessBatchErrDiff(BatchRun &run);
     size_t PostStride() const { return (m_postBytes + 255) & ~(size_t)255; }
     // a frame table in a slot of the ring (pinned copy + device copy): frame i = {srcs ? srcs[i] : null, dsts ? dsts[i] : dst_base + i * dst_stride}
-    HRESULT UploadFrameTable(int n, const void *const *srcs, void *const *dsts, uint8_t *dst_base, size_t dst_stride, const FusedFrame **dev, hipEvent_t *done);
+    HRESULT UploadFrameTable(int n, const void *const *srcs, void *const *dsts, uint8_t *dst_base, size_t dst_stride, SlotLease *lease);
     DevBuffer m_batchTex;          // interleaved RGB / v210 batches: the frames' m_TexSrcVideo copies side by side (ProcessBatch)
     bool m_texSrcZeroed = false, m_batchTexZeroed = false;     // the texels the RGB copy loops never write have been cleared for the current media type
-    bool m_keepStart = false;      // ProcessBatchErrDiff: m_evStart sits in front of the FIRST chunk; the chunks' ProcessBatchRoutes calls leave it there
     // Jinc2m phase tables of the first / second draw (null: weights per pixel)
     DevBuffer m_jincFirst, m_jincSecond, m_jincFused;
     const float *m_jincFusedTab = nullptr;                                  // the fused Jinc2m kernel's weight table (BuildFusedJincTable), PassPlan::fused_jinc
@@ -370,10 +399,10 @@ private:
         FusedStripParams strip{};      // RgbSurfaceStrip / StripToneMap / Strip (surface / post-scale pointers: set by RunBatchRoute)
         FusedParams conv{}, direct{};  // WholeBatchLaunches / DirectConvert (BatchPlan)
     };
-    BatchRoutePlan ClassifyBatch(int n, const void *const *srcs, void *const *dsts, int rtPitch) const;
-    HRESULT RunBatchRoute(BatchRoutePlan &rp, int n, const void *const *srcs, void *const *dsts, int rtPitch);
+    BatchRoutePlan ClassifyBatch(const BatchRun &run) const;
+    HRESULT RunBatchRoute(BatchRoutePlan &rp, BatchRun &run);
     bool BatchPlan(const uint8_t *sample0, void *rt0, int rtPitch, bool aligned, bool repacked, bool src16, FusedParams *conv, FusedParams *direct) const;
-    HRESULT ProcessBatchLaunches(int n, const FusedFrame *table, void *rt0, int rtPitch, bool aligned, FusedParams conv);
+    HRESULT ProcessBatchLaunches(const BatchRun &run, const FusedFrame *table, bool aligned, FusedParams conv);
 };
 
 }  // namespace mpcvr
