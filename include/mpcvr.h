@@ -259,9 +259,18 @@ int32_t mpcvr_set_procamp(mpcvr_ctx *ctx, uint32_t flags, float brightness, floa
  * MPCVR_MEM_HOST: copied into one of three pinned staging buffers and uploaded on a copy stream, so the upload of
  * sample n+1 overlaps the processing of sample n (CopyPlane10to16's <<6 / CopyFrameV210 / CopyFrameRGB* run on the
  * device); the caller's buffer is free again when the call returns.  MPCVR_MEM_HOST_PINNED: the buffer is page-locked
- * (hipHostMalloc / hipHostRegister) and is DMA'd from directly; it must stay untouched until mpcvr_synchronize or the
- * third following copy_sample.  MPCVR_MEM_DEVICE: zero-copy — the pointer is used in place and must stay valid until
- * the following process/render call has completed (mirrors the IMediaSampleD3D11 branch :2528-2569). */
+ * (hipHostMalloc / hipHostRegister) and is DMA'd from directly; it must stay untouched until mpcvr_synchronize has
+ * returned, or until the third following copy_sample OF A HOST SAMPLE (MPCVR_MEM_HOST or MPCVR_MEM_HOST_PINNED: that one
+ * takes this sample's upload slot and waits for it; an MPCVR_MEM_DEVICE sample takes no slot and does not count) has
+ * returned.  A sample that is never drawn is uploaded all the same, and the same rule holds for its buffer.  A page-locked
+ * buffer handed over as MPCVR_MEM_HOST is staged like any other.  A host sample may be drawn any number of times (several
+ * targets, mpcvr_render, the snapshot): its slot is reused behind all of them.
+ * MPCVR_MEM_DEVICE: zero-copy — the pointer is used in place and must stay valid until
+ * the following process/render call has completed (mirrors the IMediaSampleD3D11 branch :2528-2569).
+ * Refusals — a NULL data: MPCVR_E_POINTER; a pitch that is not the media type's: MPCVR_E_UNEXPECTED (:2545); a mem_kind
+ * that is none of the three: MPCVR_E_INVALIDARG — are answered before anything is touched: the sample handed over
+ * before stays current and the next mpcvr_process draws it.  After mpcvr_flush there is no current sample
+ * (mpcvr_process: MPCVR_E_NOT_VALID_STATE) until the next copy_sample. */
 int32_t mpcvr_copy_sample(mpcvr_ctx *ctx, const void *data, int32_t pitch, int32_t mem_kind);
 
 /* Process — DX11VideoProcessor.cpp:3285-3424.  dst: DEVICE pointer to a window_w x window_h render

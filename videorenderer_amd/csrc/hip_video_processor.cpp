@@ -1105,6 +1105,8 @@ HRESULT CHipVideoProcessor::CopySample(const void *data, int pitch, int memKind)
     if (!m_bInit || !m_srcParams) return Fail(MPCVR_E_NOT_VALID_STATE, "InitMediaType has not been called");
     if (!data) return Fail(MPCVR_E_POINTER, "null sample");
     if (pitch != (m_srcBottomUp ? -m_srcPitch : m_srcPitch)) return Fail(MPCVR_E_UNEXPECTED, "sample pitch differs from the media type");   // :2545
+    // (every refusal comes before anything is touched: the current sample, its upload slot and the stream it was last drawn on stay as they are)
+    if (memKind != MPCVR_MEM_HOST && memKind != MPCVR_MEM_DEVICE && memKind != MPCVR_MEM_HOST_PINNED) return Fail(MPCVR_E_INVALIDARG, "mem_kind");
     (void)hipSetDevice(m_device);
     const size_t bytes = (size_t)m_srcPitch * m_srcLines;
     HRESULT hr;
@@ -1117,7 +1119,6 @@ HRESULT CHipVideoProcessor::CopySample(const void *data, int pitch, int memKind)
     if (memKind == MPCVR_MEM_DEVICE) {               // zero-copy, cf. the IMediaSampleD3D11 branch :2528-2569
         return PrepareSample((const uint8_t *)data, &m_curSample);
     }
-    if (memKind != MPCVR_MEM_HOST && memKind != MPCVR_MEM_HOST_PINNED) return Fail(MPCVR_E_INVALIDARG, "mem_kind");
     if (!m_copyStream && (hr = CheckHip(hipStreamCreateWithFlags(&m_copyStream, hipStreamNonBlocking), "copy stream"))) return hr;
     const int si = m_upNext;
     m_upNext = (m_upNext + 1) % kUploadSlots;
@@ -1158,7 +1159,12 @@ void CHipVideoProcessor::MarkConsumed()
 {
     if (m_curSlot < 0) return;
     UploadSlot &u = m_up[m_curSlot];
-    if (u.consumed && hipEventRecord(u.consumed, m_lastRun ? m_lastRun : m_stream) == hipSuccess) u.consumedRecorded = true;
+    if (!u.consumed) return;
+    hipStream_t const s = m_lastRun ? m_lastRun : m_stream;
+    // one event stands for every reader: a sample drawn again on another stream (a second target on another lane, Render, the snapshot) puts
+    // that stream behind the readers recorded so far before the event moves there.  A sample drawn once records on one stream and never waits.
+    if (u.consumedRecorded && u.consumedOn != s) (void)hipStreamWaitEvent(s, u.consumed, 0);
+    if (hipEventRecord(u.consumed, s) == hipSuccess) { u.consumedRecorded = true; u.consumedOn = s; }
 }
 
 // the block convert into m_TexConvertOutput (`out`; a batch's chunks set it to theirs) in front of a draw

@@ -261,6 +261,7 @@ private:
         hipEvent_t uploaded = nullptr, consumed = nullptr;
         bool inFlight = false;         // an upload into this slot has been queued
         bool consumedRecorded = false; // a Process that read it has been queued after that upload
+        hipStream_t consumedOn = nullptr;   // ... and `consumed` was last recorded on this stream (compared only, never used: MarkConsumed)
     };
     static constexpr int kUploadSlots = 3;
     UploadSlot m_up[kUploadSlots];
