@@ -22,6 +22,7 @@ SOURCES = [
     ("vp_plan.cpp", ["-ffp-contract=off"]),
     ("vp_dovi.cpp", ["-ffp-contract=off", "-std=c++20"]),
     ("hip_video_processor.cpp", []),
+    ("vp_lanes.cpp", []),
     ("mpcvr_capi.cpp", []),
     ("vp_kernels.hip", ["-ffp-contract=off", "-DMPCVR_EXACT_FP"]),
     ("vp_fused.hip", []),

@@ -78,12 +78,7 @@ CHipVideoProcessor::~CHipVideoProcessor()
         if (d.copied) (void)hipEventDestroy(d.copied);
     }
     for (TableSlot &ts : m_dvSlots) ts.Release();
-    if (m_evStreamMark) (void)hipEventDestroy(m_evStreamMark);
-    for (FrameLane &fl : m_flanes) {
-        if (fl.stream) { (void)hipStreamSynchronize(fl.stream); (void)hipStreamDestroy(fl.stream); }
-        for (LaneFrame &f : fl.ring) if (f.done) (void)hipEventDestroy(f.done);
-        if (fl.batchDone) (void)hipEventDestroy(fl.batchDone);
-    }
+    m_lanes.Release();
     for (TableSlot &ts : m_slots) ts.Release();
     if (m_evStart) (void)hipEventDestroy(m_evStart);
     if (m_evStop) (void)hipEventDestroy(m_evStop);
@@ -183,7 +178,7 @@ HRESULT CHipVideoProcessor::Synchronize()
     return MPCVR_S_OK;
 }
 
-// ---- frame lanes (see hip_video_processor.h) ----
+// ---- frame lanes (vp_lanes.h): what may take one ----
 // A frame may run beside its predecessor when nothing it touches is shared with it: the context owns its stream (a caller's stream
 // promises stream order), the sample is read in place (no repack / copy into m_TexSrcVideo), no per-frame constants are uploaded on
 // the context stream (Dolby Vision), and the plan has no intermediate surface (one fused kernel per frame: exact 2x, the strip /
@@ -193,174 +188,8 @@ bool CHipVideoProcessor::FrameLanesUsable() const
     static const bool off = [] { const char *e = std::getenv("MPCVR_NO_FRAME_LANES"); return e && *e && *e != '0'; }();
     if (off || !m_ownStream || (m_cfg.flags & MPCVR_FLAG_NO_FRAME_LANES) || m_doviValid || !m_srcParams) return false;
     if (m_srcParams->cformat == MPCVR_CF_V210 || m_srcParams->layout == LAY_RGB || ((uintptr_t)m_curSample & 3) != 0) return false;
-    if (m_plan.errdiff) return false;                 // (the error-diffusion pass reads the context's one intermediate)
-    if (m_plan.fused_up2x) return true;
-    if (m_strip && !m_plan.hdr_tonemap) return true;
-    if (m_plan.direct_convert) return true;
-    return false;
-}
-
-// Four lanes: measured on MI355X with 4K P010 -> 8K frames (bench.py process_per_frame) — one lane 14.4 k frames/s, two 18.2 k, four
-// 19.3 k; the kernels size their segments for that many frames side by side (FusedParams::inflight).
-int CHipVideoProcessor::FrameLaneCount()
-{
-    static const int n = [] { const char *e = std::getenv("MPCVR_FRAME_LANES"); const int v = e && *e ? std::atoi(e) : 4; return v < 1 ? 1 : v > kFrameLanes ? kFrameLanes : v; }();
-    return n;
-}
-
-// ---- what is in flight, as memory: two writers are ordered when the bytes their render targets cover overlap, whatever pointers they were
-// given (a window a few rows further down in one surface, the same surface from another base); targets that merely touch run side by side ----
-CHipVideoProcessor::RtSpan CHipVideoProcessor::TargetSpan(const void *rt, int rtPitch) const
-{
-    RtSpan s;
-    s.lo = (uintptr_t)rt;
-    s.hi = s.lo + (size_t)std::max(m_windowRect.Height() - 1, 0) * (size_t)rtPitch + (size_t)m_windowRect.Width() * 4;
-    return s;
-}
-
-// sorted by address, spans that overlap or touch merged into one: the result is disjoint, so both ends ascend
-void CHipVideoProcessor::SortAndMergeSpans(std::vector<RtSpan> &v)
-{
-    std::sort(v.begin(), v.end(), [](const RtSpan &a, const RtSpan &b) { return a.lo < b.lo; });
-    size_t m = 0;
-    for (size_t i = 0; i < v.size(); i++) {
-        if (m && v[i].lo <= v[m - 1].hi) v[m - 1].hi = std::max(v[m - 1].hi, v[i].hi);
-        else v[m++] = v[i];
-    }
-    v.resize(m);
-}
-
-bool CHipVideoProcessor::SpansOverlap(const std::vector<RtSpan> &sorted, const RtSpan &s)
-{
-    // the first span that ends behind s.lo is the only candidate: the ones in front end too early, the ones behind start later still
-    const auto it = std::upper_bound(sorted.begin(), sorted.end(), s.lo, [](uintptr_t lo, const RtSpan &x) { return lo < x.hi; });
-    return it != sorted.end() && it->lo < s.hi;
-}
-
-// the lane of the frame about to be queued: one that still holds a frame into memory this one's render target overlaps if there is one
-// (stream order then keeps the two writes apart; further lanes holding such a frame are waited for), else the next in turn
-CHipVideoProcessor::FrameLane *CHipVideoProcessor::PickFrameLane(const RtSpan &rt)
-{
-    FrameLane *pick = nullptr;
-    hipEvent_t also[kFrameLanes];
-    int n_also = 0;
-    for (int li = 0; li < FrameLaneCount(); li++) {
-        FrameLane &fl = m_flanes[li];
-        hipEvent_t latest = nullptr;                 // the lane's most recent unfinished frame into rt's bytes (the ring is walked oldest first)
-        for (int i = 0; i < kLaneDepth; i++) {
-            LaneFrame &f = fl.ring[(fl.head + i) % kLaneDepth];
-            if (!f.pending || !f.rt.Overlaps(rt)) continue;  // (only a frame into the same memory is worth a driver call)
-            if (hipEventQuery(f.done) == hipSuccess) { f.pending = false; continue; }
-            latest = f.done;
-        }
-        if (!latest) continue;
-        if (!pick) pick = &fl; else also[n_also++] = latest;
-    }
-    if (!pick) { pick = &m_flanes[m_flaneNext]; m_flaneNext = (m_flaneNext + 1) % FrameLaneCount(); }
-    if (!pick->stream && hipStreamCreateWithFlags(&pick->stream, hipStreamDefault) != hipSuccess) { pick->stream = nullptr; return nullptr; }
-    for (int i = 0; i < n_also; i++) (void)hipStreamWaitEvent(pick->stream, also[i], 0);
-    // ... and behind a whole batch still in flight on another lane that writes into this target's bytes (the pick's own batches: stream order)
-    for (int li = 0; li < kFrameLanes; li++) {
-        FrameLane &bl = m_flanes[li];
-        if (!bl.batchPending || &bl == pick) continue;
-        if (hipEventQuery(bl.batchDone) == hipSuccess) { bl.batchPending = false; bl.batchSpans.clear(); continue; }
-        if (SpansOverlap(bl.batchSpans, rt)) (void)hipStreamWaitEvent(pick->stream, bl.batchDone, 0);
-    }
-    return pick;
-}
-
-// ---- whole batches on the lanes (see FrameLane; which batches may take them: ProcessBatchRoutes) ----
-// the lane of the batch about to be queued (the two take turns), ordered behind everything still in flight on OTHER lanes that writes into
-// the bytes of one of its render targets: single frames (their ring entries) and batches
-CHipVideoProcessor::FrameLane *CHipVideoProcessor::PickBatchLane(int n, void *const *dsts, int rtPitch)
-{
-    FrameLane *pick = &m_flanes[m_blaneNext];
-    if (!pick->stream && hipStreamCreateWithFlags(&pick->stream, hipStreamDefault) != hipSuccess) { pick->stream = nullptr; return nullptr; }
-    // (two lanes: MPCVR_BATCH_LANE_COUNT = 2 .. 8 for the A/B — profiles/r06/batch_lane_count_call34.txt)
-    static const int count = [] { const char *e = std::getenv("MPCVR_BATCH_LANE_COUNT"); const int v = e && *e ? std::atoi(e) : kBatchLanes; return v < 2 ? 2 : v > kFrameLanes ? kFrameLanes : v; }();
-    m_blaneNext = (m_blaneNext + 1) % count;
-    std::vector<RtSpan> &spans = m_batchSpans;
-    spans.clear();
-    for (int i = 0; i < n; i++) spans.push_back(TargetSpan(dsts[i], rtPitch));
-    SortAndMergeSpans(spans);
-    m_lastBatchWaits = 0;
-    for (FrameLane &fl : m_flanes) {
-        if (&fl == pick || !fl.stream) continue;
-        for (LaneFrame &f : fl.ring) {
-            if (!f.pending) continue;
-            if (hipEventQuery(f.done) == hipSuccess) { f.pending = false; continue; }
-            if (SpansOverlap(spans, f.rt)) { (void)hipStreamWaitEvent(pick->stream, f.done, 0); m_lastBatchWaits++; }
-        }
-        if (!fl.batchPending) continue;
-        if (hipEventQuery(fl.batchDone) == hipSuccess) { fl.batchPending = false; fl.batchSpans.clear(); continue; }
-        bool shared = false;
-        for (size_t a = 0, b = 0; a < spans.size() && b < fl.batchSpans.size() && !shared;) {
-            if (spans[a].Overlaps(fl.batchSpans[b])) shared = true;
-            else if (spans[a].hi <= fl.batchSpans[b].lo) a++; else b++;
-        }
-        if (shared) { (void)hipStreamWaitEvent(pick->stream, fl.batchDone, 0); m_lastBatchWaits++; }
-    }
-    return pick;
-}
-
-// the batch just queued on `fl` (m_batchSpans, from PickBatchLane): its completion event, and its spans joined to those of the lane's batches still in flight
-void CHipVideoProcessor::NoteLaneBatch(FrameLane *fl)
-{
-    if (!fl->batchDone && hipEventCreateWithFlags(&fl->batchDone, hipEventDisableTiming) != hipSuccess) { fl->batchDone = nullptr; (void)hipStreamSynchronize(fl->stream); return; }
-    if (fl->batchPending && hipEventQuery(fl->batchDone) == hipSuccess) fl->batchPending = false;
-    if (!fl->batchPending) fl->batchSpans.clear();
-    fl->batchSpans.insert(fl->batchSpans.end(), m_batchSpans.begin(), m_batchSpans.end());
-    SortAndMergeSpans(fl->batchSpans);
-    (void)hipEventRecord(fl->batchDone, fl->stream);
-    fl->batchPending = true;
-    fl->last = fl->batchDone;
-}
-
-// the frame just queued on `fl` writes `rt`: its completion event takes the ring's oldest slot (whose frame must have completed)
-void CHipVideoProcessor::NoteLaneFrame(FrameLane *fl, const RtSpan &rt)
-{
-    LaneFrame &f = fl->ring[fl->head];
-    fl->head = (fl->head + 1) % kLaneDepth;
-    if (!f.done && hipEventCreateWithFlags(&f.done, hipEventDisableTiming) != hipSuccess) { f.done = nullptr; (void)hipStreamSynchronize(fl->stream); return; }
-    if (f.pending) (void)hipEventSynchronize(f.done);
-    f.rt = rt; f.pending = true;
-    (void)hipEventRecord(f.done, fl->stream);
-    fl->last = f.done;
-}
-
-// the context stream -> lane edge (see m_streamGen): one event record per generation of context-stream work, one wait per lane
-void CHipVideoProcessor::LaneWaitsForStream(FrameLane *fl)
-{
-    if (fl->seenGen == m_streamGen || !m_stream) return;
-    if (m_markGen != m_streamGen) {
-        if (!m_evStreamMark && hipEventCreateWithFlags(&m_evStreamMark, hipEventDisableTiming) != hipSuccess) m_evStreamMark = nullptr;
-        if (!m_evStreamMark || hipEventRecord(m_evStreamMark, m_stream) != hipSuccess) {       // no event: the host waits instead
-            (void)hipStreamSynchronize(m_stream);
-            for (FrameLane &l : m_flanes) l.seenGen = m_streamGen;
-            return;
-        }
-        m_markGen = m_streamGen;
-    }
-    (void)hipStreamWaitEvent(fl->stream, m_evStreamMark, 0);
-    fl->seenGen = m_streamGen;
-}
-
-// host_wait: block until the lanes are idle; otherwise the context stream waits for them (work queued on it afterwards runs behind
-// every frame in flight)
-HRESULT CHipVideoProcessor::JoinFrameLanes(bool host_wait)
-{
-    HRESULT hr = MPCVR_S_OK;
-    for (FrameLane &fl : m_flanes) {
-        if (!fl.stream || !fl.last) continue;
-        if (host_wait) {
-            HRESULT h = CheckHip(hipStreamSynchronize(fl.stream), "frame lane sync");
-            if (h) hr = h;
-            for (LaneFrame &f : fl.ring) f.pending = false;
-            fl.batchPending = false; fl.batchSpans.clear();
-            fl.last = nullptr;
-        } else if (m_stream) (void)hipStreamWaitEvent(m_stream, fl.last, 0);
-    }
-    return hr;
+    // (the error-diffusion pass reads the context's one intermediate)
+    return !m_plan.errdiff && (m_plan.fused_up2x || (m_strip && !m_plan.hdr_tonemap) || m_plan.direct_convert);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -921,7 +750,6 @@ HRESULT CHipVideoProcessor::UpdatePlan()
         m_period = m_stripSurf && FusedPeriodTakes(sp);
     }
     m_planDirty = false;
-    UseContextResources();
     if (LogLevel() >= 2)
         std::fprintf(stderr, "mpcvr[%p]: plan %s (%dx%d -> %dx%d in %dx%d)\n", (void *)this, GetPathInfo().c_str(), m_srcRectWidth, m_srcRectHeight,
                      m_videoRect.Width(), m_videoRect.Height(), m_windowRect.Width(), m_windowRect.Height());
@@ -947,11 +775,6 @@ HRESULT CHipVideoProcessor::UploadJincPhases(const DrawCoords &dc, DevBuffer &bu
     if ((hr = CheckHip(hipMemcpy(buf.ptr, host.data(), host.size(), hipMemcpyHostToDevice), "jinc phases upload"))) return hr;
     *tab = buf.ptr;
     return MPCVR_S_OK;
-}
-
-void CHipVideoProcessor::UseContextResources()
-{
-    m_run = m_stream; m_runConv = m_TexConvertOutput.ptr; m_runMid = m_TexResize.ptr; m_runPost = m_TexPost.ptr;
 }
 
 // m_PSConvColorData.bEnable — DX11VideoProcessor.cpp:849-853: interleaved RGB skips the convert draw unless brightness
@@ -989,15 +812,13 @@ HRESULT CHipVideoProcessor::PrepareSample(const uint8_t *dev_sample, const uint8
         if ((hr = CheckHip(m_TexSrcVideo.CheckCreate(bytes), "m_TexSrcVideo"))) return hr;
         m_texSrcZeroed = false;
         // the copy runs on the context stream: behind every lane frame that still reads the texture, and in front of the lane frames to come
-        (void)JoinFrameLanes(false);
-        NoteStreamWork();
+        OrderOnContextStream();
         if ((hr = CheckHip(hipMemcpyAsync(m_TexSrcVideo.ptr, dev_sample, bytes, hipMemcpyDeviceToDevice, m_stream), "sample copy"))) return hr;
         *tex = (const uint8_t *)m_TexSrcVideo.ptr;
         return MPCVR_S_OK;
     }
     const int tp = TexPitch();
-    (void)JoinFrameLanes(false);
-    NoteStreamWork();                 // (the repacks below run on the context stream)
+    OrderOnContextStream();           // (the repacks below run on the context stream)
     const bool fresh = m_TexSrcVideo.size < (size_t)tp * m_srcHeight || !m_TexSrcVideo.ptr || !m_texSrcZeroed;
     if ((hr = CheckHip(m_TexSrcVideo.CheckCreate((size_t)tp * m_srcHeight), "m_TexSrcVideo"))) return hr;
     if (m_srcParams->layout == LAY_RGB) {
@@ -1066,7 +887,7 @@ StoreParams CHipVideoProcessor::MakeStore(void *dst, int pitch, int dstFmt, bool
     return s;
 }
 
-void CHipVideoProcessor::FillFusedParams(const uint8_t *sample, void *rt, int rtPitch, FusedParams *fp) const
+void CHipVideoProcessor::FillFusedParams(const uint8_t *sample, void *rt, int rtPitch, FusedParams *fp, int inflight) const
 {
     FillConvertParams(sample, &fp->conv);
     fp->plane_off[0] = 0;
@@ -1084,7 +905,7 @@ void CHipVideoProcessor::FillFusedParams(const uint8_t *sample, void *rt, int rt
     fp->dovi_cm = nullptr;
     fp->jinc_tab = m_plan.fused_jinc ? m_jincFusedTab : nullptr;
     fp->exact_wide = m_plan.hdr_tonemap ? 1 : 0;
-    fp->inflight = m_inflight;
+    fp->inflight = inflight;
     static const bool no_baked = [] { const char *e = std::getenv("MPCVR_FUSED_NO_BAKED"); return e && *e && *e != '0'; }();     // (A/B: the kernel's own staging loops)
     fp->baked = (m_fusedTabValid && !no_baked) ? m_fusedTab.ptr : nullptr;
     fp->baked_lut = m_fusedTabLut;
@@ -1168,34 +989,34 @@ void CHipVideoProcessor::MarkConsumed()
 }
 
 // the block convert into m_TexConvertOutput (`out`; a batch's chunks set it to theirs) in front of a draw
-FusedParams CHipVideoProcessor::ConvertOutputParams(const uint8_t *sample, void *out) const
+FusedParams CHipVideoProcessor::ConvertOutputParams(const uint8_t *sample, void *out, int inflight) const
 {
     const int pitch = (int)(m_srcRectWidth * SurfBytesPerPixel(m_plan.internal_fmt));
     FusedParams fp{};
-    FillFusedParams(sample, out, pitch, &fp);
+    FillFusedParams(sample, out, pitch, &fp, inflight);
     fp.store = MakeStore(out, pitch, m_plan.internal_fmt, false);
     fp.dst_aligned16 = 1;
     fp.exact_convert = 1;
     return fp;
 }
 
-HRESULT CHipVideoProcessor::ConvertColorPass(const uint8_t *sample)
+HRESULT CHipVideoProcessor::ConvertColorPass(const uint8_t *sample, const RunOn &on)
 {
     ConvertParams P;
     FillConvertParams(sample, &P);
-    Surface out{m_runConv, (int)(m_srcRectWidth * SurfBytesPerPixel(m_plan.internal_fmt)),
+    Surface out{m_TexConvertOutput.ptr, (int)(m_srcRectWidth * SurfBytesPerPixel(m_plan.internal_fmt)),
                 m_srcRectWidth, m_srcRectHeight, m_plan.internal_fmt};
     if (!(m_cfg.flags & MPCVR_FLAG_NO_FUSED)) {           // the fused kernel's block convert, when the source qualifies
-        const FusedParams fp = ConvertOutputParams(sample, out.ptr);
+        const FusedParams fp = ConvertOutputParams(sample, out.ptr, on.inflight);
         if (ConvertBlocksSupported(fp, false))
-            return CheckHip(LaunchConvertBlocks(fp, nullptr, FusedFrame{sample, out.ptr}, 1, m_run), "k_convert_blocks");
+            return CheckHip(LaunchConvertBlocks(fp, nullptr, FusedFrame{sample, out.ptr}, 1, on.stream), "k_convert_blocks");
     }
-    return CheckHip(LaunchConvert(P, out, m_run, (m_cfg.flags & MPCVR_FLAG_NO_FUSED) != 0), "k_convert");
+    return CheckHip(LaunchConvert(P, out, on.stream, (m_cfg.flags & MPCVR_FLAG_NO_FUSED) != 0), "k_convert");
 }
 
 // ResizeShaderPass (:3103-3187) with FinalPass (:3189-3233) folded into the epilogue of the last draw: one frame, or a chunk of a batch
 // with the chunk as every launch's frame dimension (DrawFrames)
-HRESULT CHipVideoProcessor::ResizeShaderPass(const uint8_t *sample, void *rt, int rtPitch, const DrawFrames &df)
+HRESULT CHipVideoProcessor::ResizeShaderPass(const uint8_t *sample, void *rt, int rtPitch, const DrawFrames &df, const RunOn &on)
 {
     const int w1 = m_srcRectWidth, h1 = m_srcRectHeight, w2 = m_videoRect.Width(), h2 = m_videoRect.Height();
     Surface conv{df.conv, (int)(w1 * SurfBytesPerPixel(m_plan.internal_fmt)), w1, h1, m_plan.internal_fmt};
@@ -1220,24 +1041,24 @@ HRESULT CHipVideoProcessor::ResizeShaderPass(const uint8_t *sample, void *rt, in
         ssp.surf_stride = df.convStride;
         if (df.lastTab) ssp.fp.dst_aligned16 = df.aligned;
         const FusedFrame one = df.lastTab ? FusedFrame{nullptr, nullptr} : FusedFrame{(const uint8_t *)conv.ptr, last.dst};
-        hr = CheckHip(LaunchFusedStrip(ssp, df.lastTab, one, df.n, m_run), "k_fused_strip<surface>");
+        hr = CheckHip(LaunchFusedStrip(ssp, df.lastTab, one, df.n, on.stream), "k_fused_strip<surface>");
     } else if (m_plan.two_pass && !plain && !m_firstJinc && !m_secondJinc && m_firstAxis == 0 && !m_firstSwap &&
         Resize2DSupported(conv, m_tapsX, m_tapsY, last)) {
         // both draws in one LDS-tiled kernel: m_TexResize stays on chip
-        hr = CheckHip(LaunchResize2D(conv, m_tapsX, m_tapsY, (const int32_t *)m_otherX.ptr, m_plan.mid_h, w2, h2, last, m_run, &b), "k_resize_2d");
+        hr = CheckHip(LaunchResize2D(conv, m_tapsX, m_tapsY, (const int32_t *)m_otherX.ptr, m_plan.mid_h, w2, h2, last, on.stream, &b), "k_resize_2d");
     } else if (m_plan.two_pass) {
         Surface mid{df.mid, w2 * 8, w2, m_plan.mid_h, SF_RGBA16F};
         StoreParams st = MakeStore(mid.ptr, mid.pitch, SF_RGBA16F, false);
         ResizeBatch b1; b1.n = df.n; b1.in_stride = df.convStride; b1.dst_stride = df.midStride;
-        if (m_firstJinc) hr = CheckHip(LaunchJinc2(conv, m_firstCoords, w2, m_plan.mid_h, st, m_run, m_jincFirstTab, jfast, &b1, m_jincFirstCtr), "k_jinc2");
-        else hr = CheckHip(LaunchResize(m_firstAxis, m_firstSwap, conv, m_tapsX, (const int32_t *)m_otherX.ptr, w2, m_plan.mid_h, st, m_run, plain, &b1), "k_resize<first>");
+        if (m_firstJinc) hr = CheckHip(LaunchJinc2(conv, m_firstCoords, w2, m_plan.mid_h, st, on.stream, m_jincFirstTab, jfast, &b1, m_jincFirstCtr), "k_jinc2");
+        else hr = CheckHip(LaunchResize(m_firstAxis, m_firstSwap, conv, m_tapsX, (const int32_t *)m_otherX.ptr, w2, m_plan.mid_h, st, on.stream, plain, &b1), "k_resize<first>");
         if (hr) return hr;
         ResizeBatch b2 = b; b2.in_stride = df.midStride;
-        if (m_secondJinc) hr = CheckHip(LaunchJinc2(mid, m_secondCoords, w2, h2, last, m_run, m_jincSecondTab, jfast, &b2, m_jincSecondCtr), "k_jinc2");
-        else hr = CheckHip(LaunchResize(1, false, mid, m_tapsY, (const int32_t *)m_otherY.ptr, w2, h2, last, m_run, plain, &b2), "k_resize<Y>");
+        if (m_secondJinc) hr = CheckHip(LaunchJinc2(mid, m_secondCoords, w2, h2, last, on.stream, m_jincSecondTab, jfast, &b2, m_jincSecondCtr), "k_jinc2");
+        else hr = CheckHip(LaunchResize(1, false, mid, m_tapsY, (const int32_t *)m_otherY.ptr, w2, h2, last, on.stream, plain, &b2), "k_resize<Y>");
     } else if (m_plan.one_pass) {
-        if (m_firstJinc) hr = CheckHip(LaunchJinc2(conv, m_firstCoords, w2, h2, last, m_run, m_jincFirstTab, jfast, &b, m_jincFirstCtr), "k_jinc2");
-        else hr = CheckHip(LaunchResize(m_firstAxis, m_firstSwap, conv, m_tapsX, (const int32_t *)m_otherX.ptr, w2, h2, last, m_run, plain, &b), "k_resize<one>");
+        if (m_firstJinc) hr = CheckHip(LaunchJinc2(conv, m_firstCoords, w2, h2, last, on.stream, m_jincFirstTab, jfast, &b, m_jincFirstCtr), "k_jinc2");
+        else hr = CheckHip(LaunchResize(m_firstAxis, m_firstSwap, conv, m_tapsX, (const int32_t *)m_otherX.ptr, w2, h2, last, on.stream, plain, &b), "k_resize<one>");
     } else {
         drawn = false;
         if (!m_plan.convert) {    // the next step reads the source rect of the texture (pTex = pInputTexture, :3352)
@@ -1248,12 +1069,12 @@ HRESULT CHipVideoProcessor::ResizeShaderPass(const uint8_t *sample, void *rt, in
         if (!m_plan.hdr_tonemap) {
             StoreParams direct = final;
             if (!m_plan.convert) direct.mid_fmt = conv.fmt;   // nothing was drawn into m_TexsPostScale: the final pass sees the texture's own precision
-            return CheckHip(LaunchCopy(conv, w2, h2, direct, m_run), "k_copy");
+            return CheckHip(LaunchCopy(conv, w2, h2, direct, on.stream), "k_copy");
         }
     }
     if (hr || !m_plan.hdr_tonemap) return hr;
     ResizeBatch tb; tb.n = df.n; tb.in_stride = drawn ? df.postStride : df.convStride; tb.frames = df.rtTab;
-    return CheckHip(LaunchHdr10ToneMap(drawn ? post : conv, m_hdrTm, w2, h2, final, m_run, &tb), "k_hdr10_tonemap");
+    return CheckHip(LaunchHdr10ToneMap(drawn ? post : conv, m_hdrTm, w2, h2, final, on.stream, &tb), "k_hdr10_tonemap");
 }
 
 // what both forms of the arbitrary-ratio fused kernel take from the plan: the target, the strip tables and, for a periodic vertical ratio,
@@ -1277,9 +1098,9 @@ bool CHipVideoProcessor::FillStripTables(const StoreParams &store, int perForce,
 }
 
 // parameters of the arbitrary-ratio fused kernel for one launch; false: this launch cannot take it (alignment, sizes)
-bool CHipVideoProcessor::FillStripParams(const uint8_t *sample, void *dst, int dstPitch, const StoreParams &store, FusedStripParams *sp) const
+bool CHipVideoProcessor::FillStripParams(const uint8_t *sample, void *dst, int dstPitch, const StoreParams &store, FusedStripParams *sp, int inflight) const
 {
-    FillFusedParams(sample, dst, dstPitch, &sp->fp);
+    FillFusedParams(sample, dst, dstPitch, &sp->fp, inflight);
     sp->fp.dst_aligned16 = (((uintptr_t)dst) & 7) == 0;         // (8 bytes here, as in FillStripSurfParams)
     return FillStripTables(store, (m_cfg.flags & MPCVR_FLAG_FORCE_PERIOD) ? 1 : 0, sp);
 }
@@ -1299,39 +1120,39 @@ bool CHipVideoProcessor::FillStripSurfParams(const Surface &src, const StorePara
     return FillStripTables(store, 1, sp);      // (per_force: with a periodic vertical ratio the register-window kernel reads the surface as well)
 }
 
-HRESULT CHipVideoProcessor::ProcessOne(const uint8_t *sample, void *rt, int rtPitch)
+HRESULT CHipVideoProcessor::ProcessOne(const uint8_t *sample, void *rt, int rtPitch, const RunOn &on)
 {
     HRESULT hr;
     if (m_plan.fused_up2x) {
         FusedParams fp{};
-        FillFusedParams(sample, rt, rtPitch, &fp);
+        FillFusedParams(sample, rt, rtPitch, &fp, on.inflight);
         const FusedFrame fr{sample, rt};        // a single frame travels by value in the kernel arguments
-        return CheckHip(LaunchFusedUp2x(fp, nullptr, fr, 1, m_run), "k_fused_up2x");
+        return CheckHip(LaunchFusedUp2x(fp, nullptr, fr, 1, on.stream), "k_fused_up2x");
     }
     if (m_strip) {
         // with the HDR10 tone-mapping step the resize draws into the post-scale texture and the step writes the target (:3359-3367)
         const int w2 = m_videoRect.Width(), h2 = m_videoRect.Height();
-        Surface post{m_runPost, (int)(w2 * SurfBytesPerPixel(m_plan.internal_fmt)), w2, h2, m_plan.internal_fmt};
+        Surface post{m_TexPost.ptr, (int)(w2 * SurfBytesPerPixel(m_plan.internal_fmt)), w2, h2, m_plan.internal_fmt};
         const StoreParams final = MakeStore(rt, rtPitch, m_plan.swap_fmt, true);
         const StoreParams last = m_plan.hdr_tonemap ? MakeStore(post.ptr, post.pitch, m_plan.internal_fmt, false) : final;
         FusedStripParams sp{};
-        if (FillStripParams(sample, last.dst, last.dst_pitch, last, &sp)) {
-            if ((hr = CheckHip(LaunchFusedStrip(sp, nullptr, FusedFrame{sample, last.dst}, 1, m_run), "k_fused_strip"))) return hr;
+        if (FillStripParams(sample, last.dst, last.dst_pitch, last, &sp, on.inflight)) {
+            if ((hr = CheckHip(LaunchFusedStrip(sp, nullptr, FusedFrame{sample, last.dst}, 1, on.stream), "k_fused_strip"))) return hr;
             if (!m_plan.hdr_tonemap) return MPCVR_S_OK;
-            return CheckHip(LaunchHdr10ToneMap(post, m_hdrTm, w2, h2, final, m_run), "k_hdr10_tonemap");
+            return CheckHip(LaunchHdr10ToneMap(post, m_hdrTm, w2, h2, final, on.stream), "k_hdr10_tonemap");
         }
     }
     if (m_plan.direct_convert) {
         FusedParams fp{};
-        FillFusedParams(sample, rt, rtPitch, &fp);
+        FillFusedParams(sample, rt, rtPitch, &fp, on.inflight);
         if (ConvertBlocksSupported(fp, true))
-            return CheckHip(LaunchConvertBlocks(fp, nullptr, FusedFrame{sample, rt}, 1, m_run), "k_convert_blocks");
+            return CheckHip(LaunchConvertBlocks(fp, nullptr, FusedFrame{sample, rt}, 1, on.stream), "k_convert_blocks");
         ConvertParams P;
         FillConvertParams(sample, &P);
-        return CheckHip(LaunchConvertDirect(P, MakeStore(rt, rtPitch, m_plan.swap_fmt, true), m_run), "k_convert_direct");
+        return CheckHip(LaunchConvertDirect(P, MakeStore(rt, rtPitch, m_plan.swap_fmt, true), on.stream), "k_convert_direct");
     }
-    if (m_plan.convert && (hr = ConvertColorPass(sample))) return hr;
-    return ResizeShaderPass(sample, rt, rtPitch, DrawFrames{m_runConv, m_runMid, m_runPost});
+    if (m_plan.convert && (hr = ConvertColorPass(sample, on))) return hr;
+    return ResizeShaderPass(sample, rt, rtPitch, DrawFrames{m_TexConvertOutput.ptr, m_TexResize.ptr, m_TexPost.ptr}, on);
 }
 
 // A render target is made of dwords (4 bytes per pixel, and no kernel stores less than one): its first byte and its pitch are multiples of 4
@@ -1345,7 +1166,7 @@ HRESULT CHipVideoProcessor::CheckTargetLayout(int n, void *const *dsts, int rtPi
 }
 
 // Process — DX11VideoProcessor.cpp:3285-3424
-HRESULT CHipVideoProcessor::Process(void *pRenderTarget, int rtPitch, const CRect *srcRect, const CRect *dstRect, bool /*second*/)
+HRESULT CHipVideoProcessor::ProcessFrame(void *pRenderTarget, int rtPitch, const CRect *srcRect, const CRect *dstRect, size_t clearBytes, bool onContextStream)
 {
     if (!m_bInit || !m_srcParams) return Fail(MPCVR_E_NOT_VALID_STATE, "InitMediaType has not been called");
     if (!pRenderTarget) return Fail(MPCVR_E_POINTER, "null render target");
@@ -1358,42 +1179,33 @@ HRESULT CHipVideoProcessor::Process(void *pRenderTarget, int rtPitch, const CRec
     if (dstRect && !dstRect->IsRectNull()) { if ((hr = SetVideoRect(*dstRect))) return hr; }
     if (rtPitch < m_windowRect.Width() * 4) return Fail(MPCVR_E_INVALIDARG, "render-target pitch smaller than a row");
     if (m_planDirty && (hr = UpdatePlan())) return hr;
-    UseContextResources();
     const RtSpan span = TargetSpan(pRenderTarget, rtPitch);
-    FrameLane *fl = (m_noLanesOnce || !FrameLanesUsable()) ? nullptr : PickFrameLane(span);
-    m_inflight = fl ? FrameLaneCount() : 1;           // the kernels size their segments for that many frames side by side
-    if (fl) {
-        m_run = fl->stream;
-        LaneWaitsForStream(fl);           // behind a batch / an off-lane frame / a sample copy still queued on the context stream
+    const int lane = (onContextStream || !FrameLanesUsable()) ? -1 : m_lanes.PickFrameLane(span);
+    // (on the lanes the kernels size their segments for that many frames side by side)
+    const RunOn on{lane >= 0 ? m_lanes.Stream(lane) : m_stream, lane >= 0 ? FrameLanes::Count() : 1};
+    if (lane >= 0) {
+        m_lanes.LaneWaitsForStream(lane, m_stream);     // behind a batch / an off-lane frame / a sample copy still queued on the context stream
         // the sample's upload (copy stream) was ordered in front of the context stream by CopySample: the lane needs the same edge
-        if (m_curSlot >= 0 && m_up[m_curSlot].uploaded) (void)hipStreamWaitEvent(fl->stream, m_up[m_curSlot].uploaded, 0);
-        if (m_clearOnRun) (void)hipMemsetAsync(m_BackBuffer.ptr, 0, m_clearOnRun, fl->stream);
-    } else {
-        // strictly in stream order behind whatever the lanes still hold (a plan that left the lanes, a caller's stream, the snapshot)
-        (void)JoinFrameLanes(false);
-        NoteStreamWork();
-        if (m_clearOnRun) (void)hipMemsetAsync(m_BackBuffer.ptr, 0, m_clearOnRun, m_stream);
-    }
-    m_clearOnRun = 0;
+        if (m_curSlot >= 0 && m_up[m_curSlot].uploaded) (void)hipStreamWaitEvent(on.stream, m_up[m_curSlot].uploaded, 0);
+    } else OrderOnContextStream();        // strictly in stream order behind whatever the lanes still hold (a plan that left the lanes, a caller's stream, the snapshot)
+    if (clearBytes) (void)hipMemsetAsync(m_BackBuffer.ptr, 0, clearBytes, on.stream);
     // the timing pair (m_RenderStats.paintticks' stand-in): every frame off the lanes; on the lanes one frame in eight — two timestamped
     // events per frame are two more packets in front of and behind a 45 us kernel on each of four queues (same box, timed every frame /
     // every 8th: 4K -> 8K 20.03 k -> 20.35 k frames/s, 1080p same size 111 k -> 121-162 k; profiles/r04/ab_call29_lane_timing.jsonl)
     static const int every = [] { const char *e = std::getenv("MPCVR_LANE_TIMING_EVERY"); const int v = e && *e ? std::atoi(e) : 8; return v < 1 ? 1 : v; }();
-    const bool timeIt = !fl || every == 1 || (m_laneFrames++ % (unsigned)every) == 0 || !m_timed;
-    if (timeIt) (void)hipEventRecord(m_evStart, m_run);
+    const bool timeIt = lane < 0 || every == 1 || (m_laneFrames++ % (unsigned)every) == 0 || !m_timed;
+    if (timeIt) (void)hipEventRecord(m_evStart, on.stream);
     if (m_plan.errdiff) {
         // EXTENSION (bUseDither = 2): the draws render into the window-sized R10G10B10A2 intermediate, as for a 10-bit swap chain; the
         // error-diffusion pass takes it to the render target
-        if (!(hr = PrepareErrDiff(1)) && !(hr = ProcessOne(m_curSample, m_edBase, m_edPitch)))
-            hr = ErrDiffPass(1, nullptr, FusedFrame{m_edBase, pRenderTarget}, rtPitch, m_run);
+        if (!(hr = PrepareErrDiff(1)) && !(hr = ProcessOne(m_curSample, m_edBase, m_edPitch, on)))
+            hr = ErrDiffPass(1, nullptr, FusedFrame{m_edBase, pRenderTarget}, rtPitch, on.stream);
     } else
-        hr = ProcessOne(m_curSample, pRenderTarget, rtPitch);
-    if (timeIt) (void)hipEventRecord(m_evStop, m_run);
-    m_lastRun = m_run;
+        hr = ProcessOne(m_curSample, pRenderTarget, rtPitch, on);
+    if (timeIt) (void)hipEventRecord(m_evStop, on.stream);
+    m_lastRun = on.stream;
     MarkConsumed();
-    if (fl) NoteLaneFrame(fl, span);
-    m_inflight = 1;
-    UseContextResources();
+    if (lane >= 0) m_lanes.NoteLaneFrame(lane, span);
     m_timed = true;
     return hr;
 }
@@ -1432,7 +1244,7 @@ HRESULT CHipVideoProcessor::RunBatch(BatchRun &run)
 }
 
 // One batch: classified once (ClassifyBatch), then run on one of two lanes beside the batch before it when its route shares nothing
-// with it (FrameLane); everything else — and every batch of a context on a caller's stream — in stream order on the context stream
+// with it (FrameLanes); everything else — and every batch of a context on a caller's stream — in stream order on the context stream
 HRESULT CHipVideoProcessor::ProcessBatchRoutes(BatchRun &run)
 {
     BatchRoutePlan rp = ClassifyBatch(run);
@@ -1447,21 +1259,16 @@ HRESULT CHipVideoProcessor::ProcessBatchRoutes(BatchRun &run)
     const bool laneRoute = rp.route == BatchRoute::FusedUp2x || rp.route == BatchRoute::Strip || rp.route == BatchRoute::DirectConvert;
     const bool onLane = laneRoute && !rp.repackSlot && !lanesOff && m_ownStream && run.n >= 2 && !m_doviValid && !run.dvFrames && !m_plan.errdiff && !m_plan.hdr_tonemap &&
                         !(m_cfg.flags & (MPCVR_FLAG_NO_FRAME_LANES | MPCVR_FLAG_NO_FUSED | MPCVR_FLAG_NO_FAST_CONVERT | MPCVR_FLAG_NO_STRIP));
-    FrameLane *const bl = onLane ? PickBatchLane(run.n, run.dsts, run.rtPitch) : nullptr;
-    hipStream_t const ctx = m_stream;
-    if (bl) {
-        m_lastBatchLane = (int)(bl - m_flanes);
-        LaneWaitsForStream(bl);              // behind whatever the context stream was given since the lane last looked
-        m_stream = bl->stream;
-    } else {
-        (void)JoinFrameLanes(false);         // a batch runs on the context stream, behind every single frame still in flight
-        NoteStreamWork();                    // ... and single frames queued after it run behind the batch (LaneWaitsForStream)
-    }
-    UseContextResources();
+    // (PrepareSample, ApplyDoviFrame / UploadDoviParams and UploadDoviTables queue on the context stream whatever the run says: they are reached
+    // only from routes that never take a lane — FrameByFrame is no lane route, and a run with Dolby Vision metadata fails the condition above)
+    const int bl = onLane ? m_lanes.PickBatchLane(run.n, run.dsts, TargetSpan(nullptr, run.rtPitch).hi, &m_lastBatchWaits) : -1;
+    run.on = RunOn{bl >= 0 ? m_lanes.Stream(bl) : m_stream};
+    if (bl >= 0) {
+        m_lastBatchLane = bl;
+        m_lanes.LaneWaitsForStream(bl, m_stream);    // behind whatever the context stream was given since the lane last looked
+    } else OrderOnContextStream();           // behind every single frame still in flight, and single frames queued after it run behind the batch
     const HRESULT hr = RunBatchRoute(rp, run);
-    m_stream = ctx;
-    UseContextResources();
-    if (bl) NoteLaneBatch(bl);
+    if (bl >= 0) m_lanes.NoteLaneBatch(bl);
     return hr;
 }
 
@@ -1523,20 +1330,21 @@ CHipVideoProcessor::BatchRoutePlan CHipVideoProcessor::ClassifyBatch(const Batch
     return take(BatchRoute::FusedUp2x);
 }
 
-// the launches of a classified batch on m_stream (the context stream or a lane's)
+// the launches of a classified batch on run.on.stream (the context stream or a lane's)
 HRESULT CHipVideoProcessor::RunBatchRoute(BatchRoutePlan &rp, BatchRun &run)
 {
     const int n = run.n, rtPitch = run.rtPitch;
     const void *const *srcs = run.srcs;
     void *const *const dsts = run.dsts;
+    hipStream_t const stream = run.on.stream;
     HRESULT hr = MPCVR_S_OK;
     bool started = run.started;                         // m_evStart sits in front of the batch's first launch (the repack's, if any)
-    auto start = [&] { if (!started) (void)hipEventRecord(m_evStart, m_stream); started = true; };
+    auto start = [&] { if (!started) (void)hipEventRecord(m_evStart, stream); started = true; };
     std::vector<const void *> slots;
     if (rp.repackSlot) {
         if ((hr = CheckHip(m_batchTex.CheckCreate(rp.repackSlot * n), "batch source texture"))) return hr;
         start();                                        // the repack is part of the batch's process time
-        if ((hr = CheckHip(LaunchRepackV210(nullptr, m_srcPitch, (uint8_t *)m_batchTex.ptr, TexPitch(), m_srcHeight, m_stream, srcs, n, rp.repackSlot), "k_repack_v210"))) return hr;
+        if ((hr = CheckHip(LaunchRepackV210(nullptr, m_srcPitch, (uint8_t *)m_batchTex.ptr, TexPitch(), m_srcHeight, stream, srcs, n, rp.repackSlot), "k_repack_v210"))) return hr;
         m_batchTexZeroed = false;                       // (the RGB batches' zeroed remainder columns are gone)
         slots.resize(n);
         for (int i = 0; i < n; i++) slots[i] = (uint8_t *)m_batchTex.ptr + (size_t)i * rp.repackSlot;
@@ -1558,12 +1366,12 @@ HRESULT CHipVideoProcessor::RunBatchRoute(BatchRoutePlan &rp, BatchRun &run)
             FusedFrame tab[kHostTableMax];
             for (int i = 0; i < n; i++) tab[i] = FusedFrame{(const uint8_t *)srcs[i], dsts[i]};
             start();
-            const hipError_t e = LaunchConvertBlocks(rp.direct, nullptr, FusedFrame{nullptr, nullptr}, n, m_stream, 0, tab);
+            const hipError_t e = LaunchConvertBlocks(rp.direct, nullptr, FusedFrame{nullptr, nullptr}, n, stream, 0, tab);
             if (e != hipErrorInvalidValue || n <= 32) { hr = CheckHip(e, "k_convert_blocks"); break; }
         }
-        if ((hr = UploadFrameTable(n, srcs, dsts, nullptr, 0, &table))) break;
+        if ((hr = UploadFrameTable(n, srcs, dsts, nullptr, 0, stream, &table))) break;
         start();
-        hr = CheckHip(LaunchConvertBlocks(rp.direct, table.frames(), FusedFrame{nullptr, nullptr}, n, m_stream), "k_convert_blocks");
+        hr = CheckHip(LaunchConvertBlocks(rp.direct, table.frames(), FusedFrame{nullptr, nullptr}, n, stream), "k_convert_blocks");
         break;
     case BatchRoute::RgbSurfaceStrip: {
         // Interleaved RGB without a convert draw (m_PSConvColorData.bEnable false, :849-853): every frame is repacked into its own slot of a
@@ -1575,9 +1383,9 @@ HRESULT CHipVideoProcessor::RunBatchRoute(BatchRoutePlan &rp, BatchRun &run)
         const bool fresh = m_batchTex.size < texBytes * chunk || !m_batchTex.ptr || !m_batchTexZeroed;     // (not by size alone: a v210 batch or another media type may have used it since)
         if ((hr = CheckHip(m_batchTex.CheckCreate(texBytes * chunk), "batch source texture"))) break;
         // texels the reference's copy loop never writes (RGB48 remainder) stay zero, as in PrepareSample
-        if (fresh && (hr = CheckHip(hipMemsetAsync(m_batchTex.ptr, 0, texBytes * chunk, m_stream), "clear batch texture"))) break;
+        if (fresh && (hr = CheckHip(hipMemsetAsync(m_batchTex.ptr, 0, texBytes * chunk, stream), "clear batch texture"))) break;
         m_batchTexZeroed = true;
-        if ((hr = UploadFrameTable(n, srcs, dsts, nullptr, 0, &table))) break;
+        if ((hr = UploadFrameTable(n, srcs, dsts, nullptr, 0, stream, &table))) break;
         rp.strip.surf.ptr = m_batchTex.ptr;
         rp.strip.surf_stride = texBytes;
         rp.strip.fp.dst_aligned16 = rp.aligned8 ? 1 : 0;
@@ -1585,8 +1393,8 @@ HRESULT CHipVideoProcessor::RunBatchRoute(BatchRoutePlan &rp, BatchRun &run)
         for (int at = 0; at < n && !hr; at += chunk) {
             const int m = std::min(chunk, n - at);
             hr = CheckHip(LaunchRepackRgb(m_srcParams->repack, nullptr, m_srcBottomUp ? -m_srcPitch : m_srcPitch, (uint8_t *)m_batchTex.ptr, tp,
-                                          m_srcWidth, m_srcHeight, m_stream, srcs + at, m, texBytes), "k_repack_rgb");
-            if (!hr) hr = CheckHip(LaunchFusedStrip(rp.strip, table.frames() + at, FusedFrame{nullptr, nullptr}, m, m_stream), "k_fused_strip<surface>");
+                                          m_srcWidth, m_srcHeight, stream, srcs + at, m, texBytes), "k_repack_rgb");
+            if (!hr) hr = CheckHip(LaunchFusedStrip(rp.strip, table.frames() + at, FusedFrame{nullptr, nullptr}, m, stream), "k_fused_strip<surface>");
         }
         break;
     }
@@ -1605,11 +1413,11 @@ HRESULT CHipVideoProcessor::RunBatchRoute(BatchRoutePlan &rp, BatchRun &run)
         for (int at = 0; at < n && !hr; at += chunk) {
             const int m = std::min(chunk, n - at);
             SlotLease drawTab, realTab;            // (both until the end of the chunk's two launches)
-            if ((hr = UploadFrameTable(m, srcs + at, nullptr, (uint8_t *)m_batchPost.ptr, postStride, &drawTab))) break;
-            if ((hr = UploadFrameTable(m, srcs + at, dsts + at, nullptr, 0, &realTab))) break;
+            if ((hr = UploadFrameTable(m, srcs + at, nullptr, (uint8_t *)m_batchPost.ptr, postStride, stream, &drawTab))) break;
+            if ((hr = UploadFrameTable(m, srcs + at, dsts + at, nullptr, 0, stream, &realTab))) break;
             ResizeBatch tb; tb.n = m; tb.in_stride = postStride; tb.frames = realTab.frames();
-            if (!(hr = CheckHip(LaunchFusedStrip(rp.strip, drawTab.frames(), FusedFrame{nullptr, nullptr}, m, m_stream), "k_fused_strip")))
-                hr = CheckHip(LaunchHdr10ToneMap(post, m_hdrTm, w2, h2, MakeStore(dsts[at], rtPitch, m_plan.swap_fmt, true), m_stream, &tb), "k_hdr10_tonemap");
+            if (!(hr = CheckHip(LaunchFusedStrip(rp.strip, drawTab.frames(), FusedFrame{nullptr, nullptr}, m, stream), "k_fused_strip")))
+                hr = CheckHip(LaunchHdr10ToneMap(post, m_hdrTm, w2, h2, MakeStore(dsts[at], rtPitch, m_plan.swap_fmt, true), stream, &tb), "k_hdr10_tonemap");
         }
         break;
     }
@@ -1620,19 +1428,19 @@ HRESULT CHipVideoProcessor::RunBatchRoute(BatchRoutePlan &rp, BatchRun &run)
             const uint8_t *tex = (const uint8_t *)srcs[i];           // (repacked: already in m_TexSrcVideo's layout, a slot of the batch texture)
             if (!rp.repackSlot && (hr = PrepareSample((const uint8_t *)srcs[i], &tex))) break;
             if (run.dvFrames && (hr = ApplyDoviFrame(run.dvFrames[i]))) break;          // this frame's RPU: constants, matrix, tone-mapping metadata
-            hr = ProcessOne(tex, dsts[i], rtPitch);
+            hr = ProcessOne(tex, dsts[i], rtPitch, run.on);
         }
         break;
     case BatchRoute::WholeBatchLaunches:
-        if ((hr = UploadFrameTable(n, srcs, dsts, nullptr, 0, &table))) break;
+        if ((hr = UploadFrameTable(n, srcs, dsts, nullptr, 0, stream, &table))) break;
         start();
         hr = ProcessBatchLaunches(run, table.frames(), rp.aligned, rp.conv);
         break;
     case BatchRoute::Strip:
-        if ((hr = UploadFrameTable(n, srcs, dsts, nullptr, 0, &table))) break;
+        if ((hr = UploadFrameTable(n, srcs, dsts, nullptr, 0, stream, &table))) break;
         rp.strip.fp.dst_aligned16 = rp.aligned8 ? 1 : 0;
         start();
-        hr = CheckHip(LaunchFusedStrip(rp.strip, table.frames(), FusedFrame{nullptr, nullptr}, n, m_stream), "k_fused_strip");
+        hr = CheckHip(LaunchFusedStrip(rp.strip, table.frames(), FusedFrame{nullptr, nullptr}, n, stream), "k_fused_strip");
         break;
     case BatchRoute::FusedUp2x: {
         FusedParams fp{};
@@ -1644,14 +1452,14 @@ HRESULT CHipVideoProcessor::RunBatchRoute(BatchRoutePlan &rp, BatchRun &run)
         if (n <= 32 && !fp.jinc_tab) {
             for (int i = 0; i < n; i++) tab[i] = FusedFrame{(const uint8_t *)srcs[i], dsts[i]};
             fp.frames_host = tab;
-        } else if ((hr = UploadFrameTable(n, srcs, dsts, nullptr, 0, &table))) break;
+        } else if ((hr = UploadFrameTable(n, srcs, dsts, nullptr, 0, stream, &table))) break;
         start();
         // (LaunchFusedUp2x wants a table for n > 1; with frames_host set no kernel is handed this pointer)
-        hr = CheckHip(LaunchFusedUp2x(fp, fp.frames_host ? tab : table.frames(), FusedFrame{nullptr, nullptr}, n, m_stream), "k_fused_up2x");
+        hr = CheckHip(LaunchFusedUp2x(fp, fp.frames_host ? tab : table.frames(), FusedFrame{nullptr, nullptr}, n, stream), "k_fused_up2x");
         break;
     }
     }
-    (void)hipEventRecord(m_evStop, m_stream);
+    (void)hipEventRecord(m_evStop, stream);
     m_timed = true;
     return hr;
 }
@@ -1734,7 +1542,7 @@ HRESULT CHipVideoProcessor::ProcessBatchErrDiff(BatchRun &run)
         run.usedTables = run.usedTables || part.usedTables;
         if (hr) return hr;
         SlotLease tab;
-        if ((hr = UploadFrameTable(m, (const void *const *)mids.data(), run.dsts + at, nullptr, 0, &tab))) return hr;
+        if ((hr = UploadFrameTable(m, (const void *const *)mids.data(), run.dsts + at, nullptr, 0, m_stream, &tab))) return hr;
         if ((hr = ErrDiffPass(m, tab.frames(), FusedFrame{nullptr, nullptr}, run.rtPitch, m_stream))) return hr;
     }
     (void)hipEventRecord(m_evStop, m_stream);       // (the batch's process time includes the pass)
@@ -1752,7 +1560,7 @@ void CHipVideoProcessor::TableSlot::Release()
 // A slot of the frame-table or the Dolby Vision table ring on loan: free to be rewritten (the launches behind its last lease have completed)
 // and large enough for `bytes` (allocated for `atLeast` or more, so that batches of growing size do not reallocate one by one).  An event
 // that was never recorded counts as complete.
-HRESULT CHipVideoProcessor::AcquireSlot(TableSlot &slot, size_t bytes, size_t atLeast, SlotLease *lease)
+HRESULT CHipVideoProcessor::AcquireSlot(TableSlot &slot, size_t bytes, size_t atLeast, hipStream_t stream, SlotLease *lease)
 {
     HRESULT hr = slot.done ? CheckHip(hipEventSynchronize(slot.done), "table slot wait")
                            : CheckHip(hipEventCreateWithFlags(&slot.done, hipEventDisableTiming), "table slot event");
@@ -1765,19 +1573,19 @@ HRESULT CHipVideoProcessor::AcquireSlot(TableSlot &slot, size_t bytes, size_t at
         if ((hr = CheckHip(slot.dev.CheckCreate(cap), "table slot"))) return hr;
         slot.cap = cap;
     }
-    *lease = SlotLease(slot.dev.ptr, slot.done, m_stream);
+    *lease = SlotLease(slot.dev.ptr, slot.done, stream);
     return MPCVR_S_OK;
 }
 
-HRESULT CHipVideoProcessor::UploadFrameTable(int n, const void *const *srcs, void *const *dsts, uint8_t *dst_base, size_t dst_stride, SlotLease *lease)
+HRESULT CHipVideoProcessor::UploadFrameTable(int n, const void *const *srcs, void *const *dsts, uint8_t *dst_base, size_t dst_stride, hipStream_t stream, SlotLease *lease)
 {
     HRESULT hr;
     TableSlot &slot = m_slots[m_slotNext];
     m_slotNext = (m_slotNext + 1) % kFrameSlots;
-    if ((hr = AcquireSlot(slot, sizeof(FusedFrame) * n, sizeof(FusedFrame) * 64, lease))) return hr;
+    if ((hr = AcquireSlot(slot, sizeof(FusedFrame) * n, sizeof(FusedFrame) * 64, stream, lease))) return hr;
     FusedFrame *fr = (FusedFrame *)slot.pinned;
     for (int i = 0; i < n; i++) { fr[i].src = srcs ? (const uint8_t *)srcs[i] : nullptr; fr[i].dst = dsts ? dsts[i] : (void *)(dst_base + (size_t)i * dst_stride); }
-    if ((hr = CheckHip(hipMemcpyAsync(slot.dev.ptr, fr, sizeof(FusedFrame) * n, hipMemcpyHostToDevice, m_stream), "frame table"))) return hr;
+    if ((hr = CheckHip(hipMemcpyAsync(slot.dev.ptr, fr, sizeof(FusedFrame) * n, hipMemcpyHostToDevice, stream), "frame table"))) return hr;
     m_tableUploads++;
     return MPCVR_S_OK;
 }
@@ -1887,7 +1695,7 @@ HRESULT CHipVideoProcessor::ProcessBatchLaunches(const BatchRun &run, const Fuse
     // m_batchPost), then ONE k_hdr10_tonemap launch per chunk writes the render targets (:3359-3367)
     SlotLease postTab;
     if (hdr) {
-        if ((hr = UploadFrameTable(chunk, nullptr, nullptr, (uint8_t *)m_batchPost.ptr, postStride, &postTab))) return hr;
+        if ((hr = UploadFrameTable(chunk, nullptr, nullptr, (uint8_t *)m_batchPost.ptr, postStride, run.on.stream, &postTab))) return hr;
         df.lastTab = postTab.frames();
         aligned = true;             // the slots of m_batchPost start on 256-byte boundaries
     }
@@ -1898,11 +1706,11 @@ HRESULT CHipVideoProcessor::ProcessBatchLaunches(const BatchRun &run, const Fuse
         conv.store.dst = m_batchConv.ptr;
         const BatchRun part = run.Slice(at, m);
         if (part.dvTab) { conv.conv.dovi = part.dvTab; conv.dovi_cm = part.dvCm; }       // (the chunk's slice of the per-frame RPU tables)
-        if ((hr = CheckHip(LaunchConvertBlocks(conv, table + at, FusedFrame{nullptr, nullptr}, m, m_stream, m_convBytes), "k_convert_blocks"))) return hr;
+        if ((hr = CheckHip(LaunchConvertBlocks(conv, table + at, FusedFrame{nullptr, nullptr}, m, run.on.stream, m_convBytes), "k_convert_blocks"))) return hr;
         df.n = m;
         df.rtTab = table + at;
         if (!hdr) df.lastTab = df.rtTab;
-        if ((hr = ResizeShaderPass(nullptr, run.dsts[0], run.rtPitch, df))) return hr;
+        if ((hr = ResizeShaderPass(nullptr, run.dsts[0], run.rtPitch, df, run.on))) return hr;
     }
     return MPCVR_S_OK;
 }
@@ -1939,20 +1747,20 @@ HRESULT CHipVideoProcessor::ApplyDoviFrame(const DoviFrameState &f)
 
 // DoviParams[n] followed by cm[12 n], staged through one of two pinned / device slots (a slot is rewritten only after the launches
 // that read it have completed: the lease, which ProcessBatchDovi keeps until the run is queued); fills run->dvTab / dvCm
-HRESULT CHipVideoProcessor::UploadDoviTables(BatchRun *run, SlotLease *lease)
+HRESULT CHipVideoProcessor::UploadDoviTables(BatchRun *run, hipStream_t stream, SlotLease *lease)
 {
     const int n = run->n;
     HRESULT hr;
     TableSlot &slot = m_dvSlots[m_dvSlotNext++ % 2];
     const size_t each = sizeof(DoviParams) + 12 * sizeof(float), need = each * n;
-    if ((hr = AcquireSlot(slot, need, each * 64, lease))) return hr;
+    if ((hr = AcquireSlot(slot, need, each * 64, stream, lease))) return hr;
     DoviParams *tp = (DoviParams *)slot.pinned;
     float *tc = (float *)(tp + n);
     for (int i = 0; i < n; i++) {
         tp[i] = run->dvFrames[i].p;
         std::memcpy(tc + (size_t)12 * i, run->dvFrames[i].cm, 12 * sizeof(float));
     }
-    if ((hr = CheckHip(hipMemcpyAsync(slot.dev.ptr, slot.pinned, need, hipMemcpyHostToDevice, m_stream), "dovi tables upload"))) return hr;
+    if ((hr = CheckHip(hipMemcpyAsync(slot.dev.ptr, slot.pinned, need, hipMemcpyHostToDevice, stream), "dovi tables upload"))) return hr;
     run->dvTab = (const DoviParams *)slot.dev.ptr;
     run->dvCm = (const float *)(run->dvTab + n);
     return MPCVR_S_OK;
@@ -1985,7 +1793,7 @@ HRESULT CHipVideoProcessor::ProcessBatchDovi(int n, const void *const *srcs, voi
         const int len = j - i;
         BatchRun run{len, srcs + i, dsts + i, rtPitch, fs.data() + i};
         SlotLease tables;           // (until the run is queued)
-        if (len > 1 && !m_plan.hdr_tonemap) hr = UploadDoviTables(&run, &tables);
+        if (len > 1 && !m_plan.hdr_tonemap) hr = UploadDoviTables(&run, m_stream, &tables);       // (a run with RPUs stays on the context stream: ProcessBatchRoutes)
         if (!hr) hr = RunBatch(run);
         m_dvLastInfo += (m_dvLastInfo.empty() ? "" : ",") + std::to_string(len) + (run.usedTables ? ":tables" : ":frames");
         // the context's own copy of the constants: the run's last frame (a whole-batch route did not touch it)
@@ -2017,9 +1825,8 @@ HRESULT CHipVideoProcessor::Render(int /*field*/)
     const bool fresh = m_BackBuffer.size < bytes || !m_BackBuffer.ptr;
     if ((hr = CheckHip(m_BackBuffer.CheckCreate(bytes), "back buffer"))) return hr;
     // ClearRenderTargetView to black (:2622) — only the letterbox area survives Process
-    m_clearOnRun = (fresh || m_videoRect != CRect(0, 0, w, h)) ? bytes : 0;     // queued by Process on the stream the frame runs on
-    hr = Process(m_BackBuffer.ptr, w * 4, nullptr, nullptr, false);
-    m_clearOnRun = 0;
+    const size_t clearBytes = (fresh || m_videoRect != CRect(0, 0, w, h)) ? bytes : 0;     // queued on the stream the frame runs on
+    hr = ProcessFrame(m_BackBuffer.ptr, w * 4, nullptr, nullptr, clearBytes, false);
     if (hr >= 0) { m_backW = w; m_backH = h; m_backFmt = m_cfg.output_format; }        // what GetDisplayedImage will find there
     return hr;
 }
@@ -2117,9 +1924,7 @@ HRESULT CHipVideoProcessor::GetCurentImage(void *hostBGRA, size_t *size)
     if (m_hdrOutput) { m_hdrOutput = false; m_blobOverride = false; SetShaderConvertColorParams(); UpdateHdrToneMapParams(); }
     m_videoRect = CRect(0, 0, w, h); m_windowRect = m_videoRect; m_cfg.output_format = MPCVR_OUT_BGRA8;
     m_planDirty = true;
-    m_noLanesOnce = true;                    // the read-back below follows on the context stream
-    hr = Process(m_Snapshot.ptr, w * 4, nullptr, nullptr, false);
-    m_noLanesOnce = false;
+    hr = ProcessFrame(m_Snapshot.ptr, w * 4, nullptr, nullptr, 0, true);     // (off the lanes: the read-back below follows on the context stream)
     m_videoRect = backupVid; m_windowRect = backupWnd; m_cfg.output_format = backupOut;
     if (backupHdr) {
         m_hdrOutput = true; SetShaderConvertColorParams(); UpdateHdrToneMapParams();

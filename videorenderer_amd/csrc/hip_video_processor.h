@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/mpcvr.h"
+#include "vp_lanes.h"
 #include "vp_launch.h"
 #include "vp_params.h"
 #include "vp_plan.h"
@@ -62,7 +63,7 @@ public:
     HRESULT SetProcAmpValues(uint32_t flags, float b, float c, float h, float s); // :4506
 
     HRESULT CopySample(const void *data, int pitch, int memKind);             // :2202 / MemCopyToTexSrcVideo :1213
-    HRESULT Process(void *pRenderTarget, int rtPitch, const CRect *srcRect, const CRect *dstRect, bool second); // :3285
+    HRESULT Process(void *rt, int rtPitch, const CRect *srcRect, const CRect *dstRect, bool /*second*/) { return ProcessFrame(rt, rtPitch, srcRect, dstRect, 0, false); }     // :3285
     HRESULT Render(int field);                                                // :2599 minus Present
     HRESULT GetBackBuffer(void **ptr, int *pitch, int *w, int *h);
     HRESULT GetCurentImage(void *hostBGRA, size_t *size);                     // :3493
@@ -98,9 +99,12 @@ private:
     void SetShaderConvertColorParams();                  // :813
     void SetShaderLuminanceParams();                     // :889
     HRESULT UpdatePlan();                                // UpdateTexures/UpdatePostScaleTexures/Update*scalingShaders
-    HRESULT ConvertColorPass(const uint8_t *sample);     // :3048
-    FusedParams ConvertOutputParams(const uint8_t *sample, void *out) const;          // the block convert into m_TexConvertOutput
-    // what ResizeShaderPass draws through, frame z of each surface at its pointer + z * its stride: one frame (the m_run* surfaces, no
+    // Where a frame or a batch is queued, handed down by value from Process / ProcessBatchRoutes to every launch: the stream (the context's,
+    // or a frame lane's) and, for single-frame launches, how many frames the host keeps side by side (FusedParams::inflight)
+    struct RunOn { hipStream_t stream = nullptr; int inflight = 1; };
+    HRESULT ConvertColorPass(const uint8_t *sample, const RunOn &on);     // :3048
+    FusedParams ConvertOutputParams(const uint8_t *sample, void *out, int inflight = 1) const;          // the block convert into m_TexConvertOutput
+    // what ResizeShaderPass draws through, frame z of each surface at its pointer + z * its stride: one frame (the context's surfaces, no
     // tables, zero strides — what every launcher takes a null ResizeBatch for) or a chunk of a batch (ProcessBatchLaunches)
     struct DrawFrames {
         void *conv = nullptr, *mid = nullptr, *post = nullptr;     // m_TexConvertOutput, m_TexResize, the post-scale texture
@@ -110,8 +114,11 @@ private:
         const FusedFrame *rtTab = nullptr;     // the HDR10 step's render targets
         int aligned = 1;                       // with a table: every lastTab target on a 16-byte boundary (one frame: its target's address decides)
     };
-    HRESULT ResizeShaderPass(const uint8_t *sample, void *rt, int rtPitch, const DrawFrames &df);     // :3103 (+ FinalPass :3189 fused into the last draw)
-    HRESULT ProcessOne(const uint8_t *sample, void *rt, int rtPitch);
+    HRESULT ResizeShaderPass(const uint8_t *sample, void *rt, int rtPitch, const DrawFrames &df, const RunOn &on);     // :3103 (+ FinalPass :3189 fused into the last draw)
+    HRESULT ProcessOne(const uint8_t *sample, void *rt, int rtPitch, const RunOn &on);
+    // Process with what Render and the snapshot add: clearBytes of the back buffer are cleared in front of the frame, on whatever stream it
+    // runs on; onContextStream: the frame stays off the lanes (a read-back follows on the context stream)
+    HRESULT ProcessFrame(void *pRenderTarget, int rtPitch, const CRect *srcRect, const CRect *dstRect, size_t clearBytes, bool onContextStream);
     HRESULT UploadTaps(const HostAxisTaps &h, DevBuffer &bi, DevBuffer &bw, DevBuffer &bs, DevBuffer &bb, const std::vector<int32_t> &other, AxisTaps *out);
     HRESULT UploadIndex(const std::vector<int32_t> &v, DevBuffer &b);
     bool ConvertEnabled() const;                       // m_PSConvColorData.bEnable (:849-853)
@@ -119,11 +126,12 @@ private:
     HRESULT PrepareSample(const uint8_t *dev_sample, const uint8_t **tex);   // device sample -> source texture
     void FillConvertParams(const uint8_t *sample, ConvertParams *P) const;
     StoreParams MakeStore(void *dst, int pitch, int dstFmt, bool rt) const;
-    void FillFusedParams(const uint8_t *sample, void *rt, int rtPitch, FusedParams *fp) const;
+    // (inflight: only a single frame on the lanes passes more than 1 — plan probes, ClassifyBatch and the batch routes take the default)
+    void FillFusedParams(const uint8_t *sample, void *rt, int rtPitch, FusedParams *fp, int inflight = 1) const;
 
     bool m_bInit = false;
     int m_device = 0;
-    hipStream_t m_stream = nullptr;
+    hipStream_t m_stream = nullptr;         // the context stream, everywhere (Init / SetStream): what a call runs on travels as a RunOn
     bool m_ownStream = false;
     hipEvent_t m_evStart = nullptr, m_evStop = nullptr;
     bool m_timed = false;
@@ -167,8 +175,8 @@ private:
     };
     void SaveDoviWalk(DoviWalkState *s) const;
     void RestoreDoviWalk(const DoviWalkState &s);
-    // One batch call in flight, handed down by reference from ProcessBatch / ProcessBatchDovi to the launches: the frames and, for a run of
-    // ProcessBatchDovi, its per-frame RPU state.  Nothing of it outlives the call.
+    // One batch call in flight, handed down by reference from ProcessBatch / ProcessBatchDovi to the launches: the frames, for a run of
+    // ProcessBatchDovi its per-frame RPU state, and the stream ProcessBatchRoutes put it on.  Nothing of it outlives the call.
     struct BatchRun {
         int n = 0;
         const void *const *srcs = nullptr;
@@ -179,6 +187,7 @@ private:
         const float *dvCm = nullptr;
         bool started = false;                          // m_evStart is in place already (error diffusion: in front of the first chunk)
         bool usedTables = false;                       // out: a whole-batch route read dvTab / dvCm
+        RunOn on;                                      // where the launches go: decided by ProcessBatchRoutes (until then: no stream)
         BatchRun Slice(int at, int m) const {          // the frames [at, at + m), every per-frame pointer advanced together
             BatchRun r = *this;
             r.n = m; r.srcs += at; r.dsts += at;
@@ -202,10 +211,10 @@ private:
     // a slot of a table ring (the frame tables of a batch, the Dolby Vision tables of a run): pinned host copy, device copy of `cap` bytes, and
     // the event behind the last launch that reads it (SlotLease)
     struct TableSlot { void *pinned = nullptr; size_t cap = 0; DevBuffer dev; hipEvent_t done = nullptr; void Release(); };
-    HRESULT AcquireSlot(TableSlot &slot, size_t bytes, size_t atLeast, SlotLease *lease);
+    HRESULT AcquireSlot(TableSlot &slot, size_t bytes, size_t atLeast, hipStream_t stream, SlotLease *lease);
     TableSlot m_dvSlots[2];
     unsigned m_dvSlotNext = 0;
-    HRESULT UploadDoviTables(BatchRun *run, SlotLease *lease);
+    HRESULT UploadDoviTables(BatchRun *run, hipStream_t stream, SlotLease *lease);
     HRESULT ApplyDoviFrame(const DoviFrameState &f);
     std::string m_dvLastInfo;                         // the runs of the last batch call, if it was a ProcessBatchDovi (GetLastBatchInfo: ";dovi_runs=3:tables,1:frames")
     unsigned m_laneFrames = 0;                        // frames queued on the frame lanes (the timing pair is recorded on every n-th)
@@ -291,59 +300,20 @@ private:
     TableSlot m_slots[kFrameSlots];
     int m_slotNext = 0;
     uint16_t m_ditherHost[1024];
-    // mpcvr_process frame after frame (the reference's own call pattern, Render -> Process, DX11VideoProcessor.cpp:2730): a single 4K
-    // frame is one round of waves on this part, so a kernel's ramp-up and drain cost a third of its time when frames run strictly one
-    // after the other.  Frames are independent (a D3D11 driver overlaps draws into different render targets as well): a context that
-    // owns its stream deals consecutive frames to four lanes whose kernels overlap; everything that can observe a result
-    // (mpcvr_synchronize, the snapshot, a batch, a plan change, a new stream) joins them first.  The lane streams are BLOCKING streams
-    // like the context's own (Init), so work on the legacy default stream stays ordered against them.
-    static constexpr int kFrameLanes = 8;         // built; FrameLaneCount() of them are used (4 unless MPCVR_FRAME_LANES says otherwise)
-    static int FrameLaneCount();
-    // every frame queued on a lane leaves (render target, completion event) in the lane's ring; a slot is reused only after its frame has
-    // completed, which also bounds how far the host runs ahead (kFrameLanes x kLaneDepth frames)
-    static constexpr int kLaneDepth = 8;
-    // what a frame in flight writes: the bytes [lo, hi) from the first pixel of its render target to the last pixel of its last row (the padding
-    // of the rows in between counts as written: rows of two targets that interleave in one surface are ordered like rows that overlap)
-    struct RtSpan { uintptr_t lo = 0, hi = 0; bool Overlaps(const RtSpan &o) const { return lo < o.hi && o.lo < hi; } };
-    RtSpan TargetSpan(const void *rt, int rtPitch) const;
-    static void SortAndMergeSpans(std::vector<RtSpan> &v);
-    static bool SpansOverlap(const std::vector<RtSpan> &sorted, const RtSpan &s);
-    struct LaneFrame { RtSpan rt; hipEvent_t done = nullptr; bool pending = false; };
-    // (round 6) WHOLE BATCHES take turns on the first two lanes as well (ProcessBatch on a context that owns its stream, a plan that is one
-    // launch per batch with no intermediate surface): two launches in flight fill each other's ramp-up and tail — same box, 32-frame batches:
-    // 4K -> 8K 22.6 k -> 23.5 k frames/s, 1080p -> 1440p 99.4 k -> 115.6 k (profiles/r06/final4/bench_workloads.jsonl).  batchSpans: the bytes the render targets of
-    // the lane's batches still in flight cover (sorted, disjoint: spans that touch are merged), batchDone: the event behind the last of them.
-    struct FrameLane { hipStream_t stream = nullptr; LaneFrame ring[kLaneDepth]; int head = 0; hipEvent_t last = nullptr; unsigned seenGen = 0;
-                       std::vector<RtSpan> batchSpans; hipEvent_t batchDone = nullptr; bool batchPending = false; };
-    static constexpr int kBatchLanes = 2;
-    int m_blaneNext = 0;
+    // Frames and whole batches of a context that owns its stream overlap on the frame lanes (vp_lanes.h: the streams, what is in flight on
+    // them and what orders it).  What may take a lane is decided here, from the plan: FrameLanesUsable, the onLane rule of ProcessBatchRoutes
+    FrameLanes m_lanes;
     int m_lastBatchWaits = 0;                 // writers still in flight on other lanes the last batch was ordered behind (GetLastBatchInfo)
-    std::vector<RtSpan> m_batchSpans;         // the batch being queued (PickBatchLane fills it, NoteLaneBatch files it)
-    FrameLane *PickBatchLane(int n, void *const *dsts, int rtPitch);
-    void NoteLaneBatch(FrameLane *fl);
-    // work queued on the CONTEXT stream (a batch, a frame that ran off the lanes, a sample copy / repack, a read-back) since a lane last
-    // waited for it: every such call bumps m_streamGen; a lane whose seenGen is behind waits for an event recorded on the context stream
-    // (m_evStreamMark, recorded once per generation) before its next frame — a lane frame into the render target, or out of the sample, that
-    // the context stream is still writing or reading can then neither overtake nor overlap it (mpcvr.h: frames into overlapping memory stay in order)
-    unsigned m_streamGen = 0, m_markGen = ~0u;
-    hipEvent_t m_evStreamMark = nullptr;
-    void NoteStreamWork() { m_streamGen++; }
-    void LaneWaitsForStream(FrameLane *fl);
-    FrameLane m_flanes[kFrameLanes];
-    int m_flaneNext = 0;
-    int m_inflight = 1;                       // FusedParams::inflight of the frame being queued
-    size_t m_clearOnRun = 0;                  // Render: bytes of the back buffer to clear in front of the frame, on whatever stream it runs
-    bool m_noLanesOnce = false;               // the snapshot's Process stays on the context stream
     hipStream_t m_lastRun = nullptr;          // the stream the current sample's last Process ran on (MarkConsumed records there)
     bool FrameLanesUsable() const;
-    FrameLane *PickFrameLane(const RtSpan &rt);
-    HRESULT JoinFrameLanes(bool host_wait);
-    void NoteLaneFrame(FrameLane *fl, const RtSpan &rt);
+    // what a frame written through `rt` covers (RtSpan, vp_spans.h): the window's rows at this pitch
+    RtSpan TargetSpan(const void *rt, int rtPitch) const { return RtSpan{(uintptr_t)rt, (uintptr_t)rt + (size_t)std::max(m_windowRect.Height() - 1, 0) * (size_t)rtPitch + (size_t)m_windowRect.Width() * 4}; }
+    // host_wait: block until the lanes are idle; otherwise the context stream waits for them (work queued on it afterwards runs behind
+    // every frame in flight)
+    HRESULT JoinFrameLanes(bool host_wait) { return CheckHip(m_lanes.Join(host_wait, m_stream), "frame lane sync"); }
+    // work is about to be queued on the context stream: behind whatever the lanes hold, and what the lanes are given next behind it (LaneWaitsForStream)
+    void OrderOnContextStream() { (void)JoinFrameLanes(false); m_lanes.NoteStreamWork(); }
     size_t m_convBytes = 0, m_midBytes = 0, m_postBytes = 0;
-    // resources of the frame being processed: the context stream's, or (Process) a frame lane's stream with the context's surfaces
-    hipStream_t m_run = nullptr;
-    void *m_runConv = nullptr, *m_runMid = nullptr, *m_runPost = nullptr;
-    void UseContextResources();
     // whole-batch launches of the pass-per-kernel path (block convert + folded resize kernels with a frame dimension)
     DevBuffer m_batchConv, m_batchMid;
     DevBuffer m_batchPost;         // HDR10 tone-mapping step of a batch: the frames' m_TexsPostScale copies side by side
@@ -366,7 +336,7 @@ private:
     HRESULT ProcessBatchErrDiff(BatchRun &run);
     size_t PostStride() const { return (m_postBytes + 255) & ~(size_t)255; }
     // a frame table in a slot of the ring (pinned copy + device copy): frame i = {srcs ? srcs[i] : null, dsts ? dsts[i] : dst_base + i * dst_stride}
-    HRESULT UploadFrameTable(int n, const void *const *srcs, void *const *dsts, uint8_t *dst_base, size_t dst_stride, SlotLease *lease);
+    HRESULT UploadFrameTable(int n, const void *const *srcs, void *const *dsts, uint8_t *dst_base, size_t dst_stride, hipStream_t stream, SlotLease *lease);
     DevBuffer m_batchTex;          // interleaved RGB / v210 batches: the frames' m_TexSrcVideo copies side by side (ProcessBatch)
     bool m_texSrcZeroed = false, m_batchTexZeroed = false;     // the texels the RGB copy loops never write have been cleared for the current media type
     // Jinc2m phase tables of the first / second draw (null: weights per pixel)
@@ -383,7 +353,7 @@ private:
     StripPlan m_stripPlan;
     DevBuffer m_stripTab;          // yrange | xstrip | xi_t | xw_t | yi | yw, word offsets in m_stripOff
     size_t m_stripOff[6] = {0, 0, 0, 0, 0, 0};
-    bool FillStripParams(const uint8_t *sample, void *dst, int dstPitch, const StoreParams &store, FusedStripParams *sp) const;
+    bool FillStripParams(const uint8_t *sample, void *dst, int dstPitch, const StoreParams &store, FusedStripParams *sp, int inflight = 1) const;
     bool FillStripTables(const StoreParams &store, int perForce, FusedStripParams *sp) const;     // what the two above share
     // periodic-phase variant of the same launch (vp_fused_period.h): vertical ratio 4:3 / 3:2 / 2:3 / 1:2 / 3:1, tables behind the strip kernel's in m_stripTab
     PeriodPlan m_periodPlan;       // P == 0: not a periodic geometry
