@@ -153,7 +153,15 @@ int32_t mpcvr_synchronize(mpcvr_ctx *ctx);
 /* VerifyMediaType + InitMediaType — DX11VideoProcessor.cpp:1569,1742.
  * cformat: ColorFormat_t value; width/height: biWidth/|biHeight|; pitch: bytes per luma row of the
  * samples that will be handed to mpcvr_copy_sample (0 => the reference's rule, :1789-1803; negative for an RGB format
- * = bottom-up DIB, the way m_srcPitch goes negative for BI_RGB with biHeight > 0, :1801-1803);
+ * = bottom-up DIB, the way m_srcPitch goes negative for BI_RGB with biHeight > 0, :1801-1803).
+ *   Pitch rules (anything else: E_INVALIDARG) — |pitch| is at least one row of pixels (width * bytes per pixel; v210: whole 16-byte groups
+ *   of six pixels); even for 16-bit samples; a multiple of 4 for 32-bit texels (Y410, r210) and v210; the two chroma planes of a three-plane
+ *   format lie at pitch / div_w (integer division, div_w = 2 for 4:2:0 and 4:2:2) behind pitch * height bytes of luma, and for 16-bit samples
+ *   that chroma pitch must be even too (YUV420P10/16, YUV422P10/16: a luma pitch that is a multiple of 4).  A sample is pitch * lines bytes
+ *   (mpcvr_get_frame_bytes).  Bytes of a row behind its pixels, and bytes behind the last plane, are never read into a pixel: they may hold
+ *   anything.  For the interleaved RGB formats the pitch, not the width, drives the reference's copy loops (Helper.cpp:446-482, 541-565):
+ *   RGB48 fills whole groups of four texels of |pitch| / 6 and RGB24 one texel of a remainder of three of |pitch| / 3, so the last texels of
+ *   a row whose width is no multiple of 4 are black or filled depending on the pitch — as in the reference;
  * src_rect: rcSource (NULL or empty => whole frame, :1821-1823);
  * extfmt: DXVA2_ExtendedFormat.value from the media type (0 fields are defaulted per
  * SpecifyExtendedFormat, Helper.cpp:1169-1211).  Returns S_OK, or E_INVALIDARG/E_NOTIMPL. */

@@ -216,6 +216,9 @@ HRESULT CHipVideoProcessor::InitMediaType(int cformat, int width, int height, in
         return Fail(MPCVR_E_INVALIDARG, "v210 pitch smaller than a row of 16-byte groups");
     if (f->bytes == 2 && (pitch & 1)) return Fail(MPCVR_E_INVALIDARG, "16-bit formats need an even pitch");
     if (f->bytes == 4 && (pitch & 3)) return Fail(MPCVR_E_INVALIDARG, "32-bit texels need a pitch that is a multiple of 4");
+    // the chroma planes of a three-plane format lie at pitch / div_w (MemCopyToTexSrcVideo :1230-1241): 16-bit samples there need that pitch even as well
+    if (f->planes == 3 && f->bytes == 2 && ((pitch / f->div_w) & 1))
+        return Fail(MPCVR_E_INVALIDARG, "three-plane 16-bit formats need an even chroma pitch (pitch / 2): a luma pitch that is a multiple of 4");
     CRect r = srcRect ? *srcRect : CRect();
     if (r.IsRectNull()) r = CRect(0, 0, width, height);                        // :1821-1823
     if (r.left < 0 || r.top < 0 || r.right > width || r.bottom > height || r.Width() <= 0 || r.Height() <= 0)

@@ -775,9 +775,11 @@ hipError_t LaunchRepackRgb(int kind, const uint8_t *src, int src_pitch, uint8_t 
 {
     const int ap = src_pitch < 0 ? -src_pitch : src_pitch;
     const int bpp = kind == RPK_RGB24 ? 3 : (kind == RPK_RGB48 || kind == RPK_BGR48) ? 6 : (kind == RPK_BGRA64 || kind == RPK_B64A) ? 8 : 4;
-    int n_px = ap / bpp;                                   // line_pixels of the reference loops
+    // line_pixels of the reference loops: the PITCH decides how many texels of a row they fill, the width only where the row ends
+    int n_px = ap / bpp;
+    if (kind == RPK_RGB48) n_px &= ~3;                     // CopyFrameRGB48 has no remainder branch (:549-560): a padded pitch fills what a tight one leaves black
+    if (kind == RPK_RGB24 && (n_px & 3) == 3) n_px -= 2;   // CopyFrameRGB24 tells a remainder of 1 / 3 from 2 by its parity (:467-477): one texel of three
     if (n_px > width) n_px = width;                        // the texture row holds `width` texels
-    if (kind == RPK_RGB48) n_px &= ~3;                     // CopyFrameRGB48 has no remainder branch (:552-563)
     if (n_px <= 0) return hipSuccess;
     if (!srcs) {
         hipLaunchKernelGGL(k_repack_rgb, dim3((n_px + 255) / 256, lines, 1), dim3(256, 1, 1), 0, s,
