@@ -454,6 +454,23 @@ int32_t mpcvr_plan_strip(int32_t kind_x, int32_t method_x, int32_t kind_y, int32
  * 4:3 / 3:2 / 2:3 / 1:2 / 3:1 or the table's tap rows are not the periodic pattern the kernel hard-codes. */
 int32_t mpcvr_plan_period(int32_t method, int32_t src_w, int32_t src_h, int32_t out_w, int32_t out_h, uint32_t flags,
                           int32_t out6[6], int32_t *xi_t, float *xw_t, float *yw, int32_t *xstrip, int32_t *strip_w);
+/* Every table the resize draws of one plan read, as a context fresh from mpcvr_set_input (default ProcAmp, no HDR output, no Dolby Vision)
+ * with these settings, source, rects, rotation and flip would build and upload them.  src_rect NULL: the whole frame.  Two-call size
+ * protocol: buf = NULL stores the byte size in *size.  buf holds 4-byte words: a header of MPCVR_DRAW_TABLES_HEADER_WORDS int32, then the
+ * first draw's axis pack, the second draw's, and the strip pack.  Header (offsets within a pack in words, -1: the pack has no such table):
+ *   [0] header words  [1] screen axis of the first draw's taps  [2] first draw swaps the texture axes (rotation 90 / 270)
+ *   [3] / [4] first / second draw runs the 2-D Jinc2m shader (no tables)  [5] strip tables planned  [6] [7] periodic rows P : Q (0: none)
+ *   [8 + 16 a ...], a = 0 / 1 (first / second draw): pack offset in buf, pack words (0: no tables), ntaps, normalise, n_out, blk_span,
+ *       blk8_span, blk32_span, other_identity, then the offsets of idx [n_out][ntaps], w, wsum [n_out], other, the block pack
+ *       (blk_lo | pad to 64 words | idx_t [ntaps][n_out] | w_t | blk8_lo | blk32_lo), and the entries of `other`
+ *   [40 ...]: strip pack offset in buf, words, the offsets of yrange | xstrip | xi_t | xw_t | yi | yw, of the periodic kernel's
+ *       xi_t | xw_t | yw | xstrip, then the strip plan's {taps, pixels per lane, strip width, ring, columns} and the periodic plan's
+ *       {taps, columns, strip width, lane ownership}
+ * Every table of an axis pack starts on a 256-byte boundary of the pack.  MPCVR_E_NOTIMPL: a resize ratio outside the supported range. */
+#define MPCVR_DRAW_TABLES_HEADER_WORDS 64
+int32_t mpcvr_plan_draw_tables(const mpcvr_settings *s, int32_t cformat, int32_t src_w, int32_t src_h, const mpcvr_rect *src_rect,
+                               const mpcvr_rect *video_rect, int32_t window_w, int32_t window_h, int32_t rotation, int32_t flip,
+                               void *buf, size_t *size);
 /* HDRParamsConstantBuffer_t as SetHDR10ShaderParams fills it (DX11VideoProcessor.cpp:907-923: defaults and clamps of the HDR10
  * metadata, the display's peak and the tone-mapping operator): five floats + the selection as words */
 int32_t mpcvr_plan_hdr10_params(float min_mastering, float max_mastering, float max_cll, float max_fall, float display_max,

@@ -2761,6 +2761,53 @@ def test_context_reuse_across_geometries_and_batches(mpcvr, torch_cuda):
     vp.close()
 
 
+def test_context_reuse_walks_through_plan_tables(mpcvr, torch_cuda):
+    """One context walks through plans whose tables differ in kind, each step leaving behind what the next must not read: a reversed row
+    map, no tap tables at all, periodic tables, a first draw that is a Y shader, one pass, normalising taps (wsum), a flipped 4:3, exact 2x
+    without tables, and back to the first.  Window = video rect throughout.  At every step one Process and one ProcessBatch of 3 frames
+    equal a fresh context's bit for bit, and so does GetVPInfo."""
+    torch = torch_cuda
+    from videorenderer_amd import api, synth
+    w, h = 96, 72
+    frames = [torch.from_numpy(synth.make_frame(2, w, h, "noise", seed=1200 + i)[0]).cuda() for i in range(3)]
+    L3, J2 = api.UPSCALE_Lanczos3, api.UPSCALE_Jinc2
+
+    def run(vp, settings, dst_wh, rotation, flip):
+        vp.Configure(settings)
+        vp.SetRotation(rotation); vp.SetFlip(flip)
+        vp.SetWindowRect((0, 0) + dst_wh); vp.SetVideoRect((0, 0) + dst_wh)
+        outs = [torch.zeros((dst_wh[1], dst_wh[0], 4), dtype=torch.uint8, device="cuda") for _ in range(4)]
+        vp.CopySample(frames[0], w * 2); vp.Process(outs[0], dst_wh[0] * 4)
+        vp.ProcessBatch(frames, outs[1:], dst_wh[0] * 4)
+        vp.Synchronize()
+        return outs, vp.GetVPInfo()
+
+    #        upscaling, target, rotation, flip, what GetVPInfo must name
+    steps = [(L3, (144, 108), 180, False, ":surface("),          # strip kernel on the convert output, reversed row map
+             (J2, (144, 108), 0, False, "passes:convert,resizeX"),      # no tap tables
+             (L3, (144, 108), 0, False, "kernel=fused_period(rows=3:2"),
+             (L3, (108, 144), 90, False, ";rot90"),              # the first draw is a Y shader
+             (L3, (96, 100), 0, False, "passes:convert,resizeY"),       # one pass
+             (L3, (64, 48), 0, False, "kernel=fused_strip("),    # ps_convolution: normalising taps
+             (L3, (128, 96), 0, True, "kernel=fused_period(rows=4:3"),  # the X table read from the other end
+             (L3, (192, 144), 0, False, "fused_up2x")]           # exact 2x: no tables
+    steps.append(steps[0])
+    vp = api.VideoProcessor(api.default_settings(iUpscaling=L3, bInterpolateAt50pct=0))
+    vp.InitMediaType(2, w, h)
+    for i, (up, dst_wh, rotation, flip, route) in enumerate(steps):
+        settings = api.default_settings(iUpscaling=up, bInterpolateAt50pct=0)
+        got, info = run(vp, settings, dst_wh, rotation, flip)
+        fresh = api.VideoProcessor(settings)
+        fresh.InitMediaType(2, w, h)
+        want, want_info = run(fresh, settings, dst_wh, rotation, flip)
+        fresh.close()
+        print(i + 1, info)
+        assert info == want_info and route in info, (i + 1, info, want_info, route)
+        for k in range(4):
+            assert torch.equal(got[k], want[k]), (i + 1, k, info)
+    vp.close()
+
+
 def test_c_abi_demo_program(mpcvr, oracle, torch_cuda, tmp_path):
     """examples/c_abi_demo.c — plain C, host memory in, host memory out — against the oracle on the same frame."""
     import subprocess

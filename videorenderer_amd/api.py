@@ -162,7 +162,7 @@ EXPORTS = [
     "mpcvr_get_last_process_ms", "mpcvr_get_last_timings",
     "mpcvr_plan_frame_layout", "mpcvr_plan_color_matrix", "mpcvr_plan_gamut_2020_to_709", "mpcvr_plan_pq_lut",
     "mpcvr_plan_upscale_weights", "mpcvr_plan_axis_taps", "mpcvr_plan_describe", "mpcvr_plan_final_pass_multiplier",
-    "mpcvr_plan_strip", "mpcvr_plan_pq_eotf_table", "mpcvr_plan_pq_eotf_lut", "mpcvr_bandwidth_probe", "mpcvr_plan_period", "mpcvr_plan_hdr10_params",
+    "mpcvr_plan_strip", "mpcvr_plan_pq_eotf_table", "mpcvr_plan_pq_eotf_lut", "mpcvr_bandwidth_probe", "mpcvr_plan_period", "mpcvr_plan_hdr10_params", "mpcvr_plan_draw_tables",
     "mpcvr_eval_transcendental", "mpcvr_eval_transcendental_host", "mpcvr_bandwidth_probe_up2x", "mpcvr_eval_dovi_tail",
 ]
 
@@ -258,6 +258,7 @@ def load_library():
         "mpcvr_eval_dovi_tail": [i32, C.c_void_p, C.c_void_p, C.c_size_t, P(f), P(f), i32, f, C.c_void_p],
         "mpcvr_eval_transcendental_host": [i32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t],
         "mpcvr_plan_describe": [P(Settings), i32, i32, i32, P(Rect), i32, i32, C.c_char_p, C.c_size_t],
+        "mpcvr_plan_draw_tables": [P(Settings), i32, i32, i32, P(Rect), P(Rect), i32, i32, i32, i32, C.c_void_p, P(C.c_size_t)],
     }
     for name, args in sig.items():
         if lib_path != LIB_PATH and not hasattr(L, name):
@@ -405,6 +406,38 @@ def plan_period(method, src_w, src_h, out_w, out_h, flags=0):
     if hr != 0:
         raise MpcvrError(hr, "mpcvr_plan_period")
     return dict(strip_w=sw.value, P=Pn, Q=Qn, taps=nt, strips=strips, acols=acols, rows_per_body=pb, xi_t=xi, xw_t=xw, yw=yw, xstrip=xs)
+
+
+def plan_draw_tables(settings, cformat, src_w, src_h, src_rect, video_rect, window_w, window_h, rotation=0, flip=False):
+    """Every table the resize draws of one plan read, as the processor builds and uploads them (include/mpcvr.h:
+    mpcvr_plan_draw_tables; no device).  dict: the header's scalars, `x` / `y` = the first / second draw's axis pack (None: the draw
+    has no tables) and `strip` (None: not planned).  An axis pack: its scalars, `words` (the pack as int32), `off` (word offsets of
+    idx / w / wsum / other / blk inside it, None where absent) and `n_other`; the strip pack: `words`, `off` (six), `period_off`
+    (four, None without a periodic plan) and both plans' scalars."""
+    import numpy as np
+    L = load_library()
+    size = C.c_size_t(0)
+    src = C.byref(Rect(*src_rect)) if src_rect is not None else None
+    args = (C.byref(settings), cformat, src_w, src_h, src, C.byref(Rect(*video_rect)), window_w, window_h, rotation, 1 if flip else 0)
+    hr = L.mpcvr_plan_draw_tables(*args, None, C.byref(size))
+    if hr != 0:
+        raise MpcvrError(hr, "mpcvr_plan_draw_tables")
+    buf = np.zeros(size.value // 4, np.int32)
+    hr = L.mpcvr_plan_draw_tables(*args, buf.ctypes.data, C.byref(size))
+    if hr != 0:
+        raise MpcvrError(hr, "mpcvr_plan_draw_tables")
+    h = [int(v) for v in buf[:int(buf[0])]]
+    out = dict(first_axis=h[1], first_swap=h[2], first_jinc=h[3], second_jinc=h[4], strip_planned=h[5], P=h[6], Q=h[7])
+    for a, name in enumerate("xy"):
+        o = h[8 + 16 * a:24 + 16 * a]
+        out[name] = None if o[1] == 0 else dict(
+            words=buf[o[0]:o[0] + o[1]], ntaps=o[2], normalise=o[3], n_out=o[4], blk_span=o[5], blk8_span=o[6], blk32_span=o[7],
+            other_identity=o[8], off=dict(zip(("idx", "w", "wsum", "other", "blk"), (None if v < 0 else v for v in o[9:14]))), n_other=o[14])
+    o = h[40:61]
+    out["strip"] = None if not h[5] else dict(
+        words=buf[o[0]:o[0] + o[1]], off=o[2:8], period_off=o[8:12] if h[6] else None, taps=o[12], px_per_lane=o[13], strip_w=o[14],
+        ring=o[15], acols=o[16], period_taps=o[17], period_acols=o[18], period_strip_w=o[19], period_own=o[20])
+    return out
 
 
 def plan_pq_eotf_lut():

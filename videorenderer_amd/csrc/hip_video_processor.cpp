@@ -61,7 +61,7 @@ CHipVideoProcessor::~CHipVideoProcessor()
     (void)hipSetDevice(m_device);
     if (m_stream) (void)hipStreamSynchronize(m_stream);
     for (DevBuffer *b : {&m_batchConv, &m_batchMid, &m_batchPost, &m_edPost, &m_edHandoff, &m_batchTex, &m_jincFirst, &m_jincSecond, &m_jincFused, &m_TexSrcVideo, &m_TexRaw, &m_TexPost, &m_TexConvertOutput, &m_TexResize, &m_BackBuffer, &m_Snapshot, &m_dither,
-                         &m_pqLut, &m_hlgLut, &m_eotfLut, &m_stripTab, &m_tapsXi, &m_tapsXw, &m_tapsXs, &m_tapsYi, &m_tapsYw, &m_tapsYs, &m_otherX, &m_otherY, &m_tapsXb, &m_tapsYb})
+                         &m_pqLut, &m_hlgLut, &m_eotfLut, &m_stripTab, &m_axisX, &m_axisY})
         b->Release();
     for (UploadSlot &u : m_up) {
         u.dev.Release();
@@ -447,80 +447,21 @@ HRESULT CHipVideoProcessor::SetProcAmpValues(uint32_t flags, float b, float c, f
 static size_t SurfBytesPerPixel(int fmt) { return fmt == SF_RGBA16F ? 8 : 4; }
 static int RgbTexFmt(const FmtConvParams &f);
 
-HRESULT CHipVideoProcessor::UploadTaps(const HostAxisTaps &h, DevBuffer &bi, DevBuffer &bw, DevBuffer &bs, DevBuffer &bb,
-                                       const std::vector<int32_t> &other, AxisTaps *out)
+// the plan's tables onto the device: one copy per axis pack and one for the strip pack.  The views are set from the packs alone: a table
+// this plan does not have reads as null, whatever the buffers still hold
+HRESULT CHipVideoProcessor::UploadPlanTables(const PlanTables &t)
 {
     HRESULT hr;
-    if ((hr = CheckHip(bi.CheckCreate(h.idx.size() * sizeof(int32_t)), "taps alloc"))) return hr;
-    if ((hr = CheckHip(bw.CheckCreate(h.w.size() * sizeof(float)), "taps alloc"))) return hr;
-    if ((hr = CheckHip(hipMemcpy(bi.ptr, h.idx.data(), h.idx.size() * sizeof(int32_t), hipMemcpyHostToDevice), "taps upload"))) return hr;
-    if ((hr = CheckHip(hipMemcpy(bw.ptr, h.w.data(), h.w.size() * sizeof(float), hipMemcpyHostToDevice), "taps upload"))) return hr;
-    out->idx = (const int32_t *)bi.ptr; out->w = (const float *)bw.ptr; out->wsum = nullptr;
-    if (h.normalise) {
-        if ((hr = CheckHip(bs.CheckCreate(h.wsum.size() * sizeof(float)), "taps alloc"))) return hr;
-        if ((hr = CheckHip(hipMemcpy(bs.ptr, h.wsum.data(), h.wsum.size() * sizeof(float), hipMemcpyHostToDevice), "taps upload"))) return hr;
-        out->wsum = (const float *)bs.ptr;
+    const std::pair<const std::vector<int32_t> *, DevBuffer *> packs[] = {{&t.x.words, &m_axisX}, {&t.y.words, &m_axisY}, {&t.stripPack.words, &m_stripTab}};
+    for (const auto &p : packs) {
+        if (p.first->empty()) continue;
+        const size_t bytes = p.first->size() * sizeof(int32_t);
+        if ((hr = CheckHip(p.second->CheckCreate(bytes), "plan tables alloc"))) return hr;
+        if ((hr = CheckHip(hipMemcpy(p.second->ptr, p.first->data(), bytes, hipMemcpyHostToDevice), "plan tables upload"))) return hr;
     }
-    out->ntaps = h.ntaps; out->normalise = h.normalise;
-    // hints for the folded resize kernels: the source window of every block of 64 outputs, and whether the unfiltered
-    // coordinate maps 1:1
-    out->blk_lo = nullptr; out->blk_span = 0; out->idx_t = nullptr; out->w_t = nullptr; out->n_out = 0;
-    out->blk8_lo = nullptr; out->blk8_span = 0; out->blk32_lo = nullptr; out->blk32_span = 0;
-    const size_t nOut = h.ntaps > 0 ? h.idx.size() / (size_t)h.ntaps : 0;
-    if (nOut > 0) {
-        std::vector<int32_t> lo((nOut + 63) / 64);
-        int span = 0;
-        for (size_t b = 0; b < lo.size(); b++) {
-            const size_t first = b * 64 * (size_t)h.ntaps, last = std::min(nOut, (b + 1) * 64) * (size_t)h.ntaps;
-            const auto mm = std::minmax_element(h.idx.begin() + first, h.idx.begin() + last);
-            lo[b] = *mm.first;
-            span = std::max(span, *mm.second - *mm.first + 1);
-        }
-        std::vector<int32_t> lo8((nOut + 7) / 8);
-        int span8 = 0;
-        for (size_t b = 0; b < lo8.size(); b++) {
-            const size_t first = b * 8 * (size_t)h.ntaps, last = std::min(nOut, (b + 1) * 8) * (size_t)h.ntaps;
-            const auto mm = std::minmax_element(h.idx.begin() + first, h.idx.begin() + last);
-            lo8[b] = *mm.first;
-            span8 = std::max(span8, *mm.second - *mm.first + 1);
-        }
-        std::vector<int32_t> lo32((nOut + 31) / 32);
-        int span32 = 0;
-        for (size_t b = 0; b < lo32.size(); b++) {
-            const size_t first = b * 32 * (size_t)h.ntaps, last = std::min(nOut, (b + 1) * 32) * (size_t)h.ntaps;
-            const auto mm = std::minmax_element(h.idx.begin() + first, h.idx.begin() + last);
-            lo32[b] = *mm.first;
-            span32 = std::max(span32, *mm.second - *mm.first + 1);
-        }
-        // tap-major copies of both tables and the 8- / 32-output block tables behind the block table, in the same buffer
-        const size_t off = (lo.size() + 63) / 64 * 64, cnt = h.idx.size();
-        std::vector<int32_t> pack(off + 2 * cnt + lo8.size() + lo32.size());
-        std::copy(lo8.begin(), lo8.end(), pack.begin() + off + 2 * cnt);
-        std::copy(lo32.begin(), lo32.end(), pack.begin() + off + 2 * cnt + lo8.size());
-        std::copy(lo.begin(), lo.end(), pack.begin());
-        for (size_t f = 0; f < nOut; f++)
-            for (int k = 0; k < h.ntaps; k++) {
-                pack[off + (size_t)k * nOut + f] = h.idx[f * h.ntaps + k];
-                std::memcpy(&pack[off + cnt + (size_t)k * nOut + f], &h.w[f * h.ntaps + k], sizeof(float));
-            }
-        if ((hr = CheckHip(bb.CheckCreate(pack.size() * sizeof(int32_t)), "taps alloc"))) return hr;
-        if ((hr = CheckHip(hipMemcpy(bb.ptr, pack.data(), pack.size() * sizeof(int32_t), hipMemcpyHostToDevice), "taps upload"))) return hr;
-        out->blk_lo = (const int32_t *)bb.ptr; out->blk_span = span;
-        out->idx_t = out->blk_lo + off; out->w_t = (const float *)(out->idx_t + cnt); out->n_out = (int)nOut;
-        out->blk8_lo = out->idx_t + 2 * cnt; out->blk8_span = span8;
-        out->blk32_lo = out->blk8_lo + lo8.size(); out->blk32_span = span32;
-    }
-    out->other_identity = 1;
-    for (size_t i = 0; i < other.size(); i++)
-        if (other[i] != (int32_t)i) { out->other_identity = 0; break; }
+    m_tapsX = t.x.View(m_axisX.ptr); m_otherX = t.x.Other(m_axisX.ptr);
+    m_tapsY = t.y.View(m_axisY.ptr); m_otherY = t.y.Other(m_axisY.ptr);
     return MPCVR_S_OK;
-}
-
-HRESULT CHipVideoProcessor::UploadIndex(const std::vector<int32_t> &v, DevBuffer &b)
-{
-    HRESULT hr;
-    if ((hr = CheckHip(b.CheckCreate(v.size() * sizeof(int32_t)), "index alloc"))) return hr;
-    return CheckHip(hipMemcpy(b.ptr, v.data(), v.size() * sizeof(int32_t), hipMemcpyHostToDevice), "index upload");
 }
 
 // UpdateTexures (:2869-2892) + UpdatePostScaleTexures (:2894-2912) + the per-axis shader choice of
@@ -533,6 +474,7 @@ HRESULT CHipVideoProcessor::UpdatePlan()
     (void)hipStreamSynchronize(m_stream);    // resources below may still be in use
     const int w1 = m_srcRectWidth, h1 = m_srcRectHeight;
     const int w2 = m_videoRect.Width(), h2 = m_videoRect.Height();
+    // 1. the plan
     {
         const PlanGeometry g{w1, h1, m_videoRect.left, m_videoRect.top, m_videoRect.right, m_videoRect.bottom,
                              m_windowRect.Width(), m_windowRect.Height(), m_iRotation, m_bFlip ? 1 : 0,
@@ -545,6 +487,7 @@ HRESULT CHipVideoProcessor::UpdatePlan()
             return Fail(MPCVR_E_NOTIMPL, why);
     }
 
+    // 2. the surfaces
     HRESULT hr;
     if (m_plan.hdr_tonemap &&
         (hr = CheckHip(m_TexPost.CheckCreate((size_t)w2 * SurfBytesPerPixel(m_plan.internal_fmt) * h2), "m_TexsPostScale"))) return hr;
@@ -555,124 +498,37 @@ HRESULT CHipVideoProcessor::UpdatePlan()
     if ((hr = CheckHip(m_TexConvertOutput.CheckCreate(convPitch * h1), "m_TexConvertOutput"))) return hr;
     m_convBytes = convPitch * h1;
 
-    HostAxisTaps hx, hy;
-    std::vector<int32_t> ox, oy;
-    if (m_plan.two_pass || m_plan.one_pass) {
-        // The rotation-carrying draw (TextureResizeShader / TextureCopyRect with FillVertices' rotation and flip,
-        // :130-179): which texture coordinate runs along which screen axis, and in which direction
-        //     rot   0: U = l + a(r-l)  V = t + b(bm-t)      rot  90: U = l + b(r-l)  V = bm - a(bm-t)
-        //     rot 180: U = r - a(r-l)  V = bm - b(bm-t)     rot 270: U = r - b(r-l)  V = t + a(bm-t)     flip: l <-> r
-        const int rot = m_plan.rotation;
-        const bool swap = rot == 90 || rot == 270;
-        const int tax = swap ? 1 : 0;                               // texture axis run through by screen x
-        bool rev_u = rot == 180 || rot == 270;
-        const bool rev_v = rot == 90 || rot == 180;
-        if (m_plan.flip) rev_u = !rev_u;
-        const bool rev_x = tax == 0 ? rev_u : rev_v, rev_y = tax == 0 ? rev_v : rev_u;
-        const int len_x = tax == 0 ? w1 : h1, len_y = tax == 0 ? h1 : w1;       // extent of the source rect along x / y
-        // source of the draw: the convert output (rect at the origin) or, with the convert draw disabled, the source
-        // texture itself with rSrc = srcRect (:3321-3323); clamp addressing covers the whole texture
-        const bool fromTex = !m_plan.convert;
-        const int ol = fromTex ? m_srcRect.left : 0, ot = fromTex ? m_srcRect.top : 0;
-        const int tw = fromTex ? m_srcWidth : w1, th = fromTex ? m_srcHeight : h1;
-        const int org_x = tax == 0 ? ol : ot, org_y = tax == 0 ? ot : ol;
-        const int tex_x = tax == 0 ? tw : th, tex_y = tax == 0 ? th : tw;
-        const int outW = w2, outH = m_plan.two_pass ? m_plan.mid_h : h2;
-        const int a = m_plan.first_tex_axis;
-        // scale[AXIS] as TextureResizeShader sets it: srcRect/dstRect of the same-named screen dimension (:351-354)
-        const float cscale = a == 0 ? (float)w1 / (float)outW : (float)h1 / (float)outH;
-        const bool taps_on_x = (a < 0) || (tax == a);               // ps_simple: a 1-tap table along x
-        const Resizer rs = a < 0 ? Resizer{RS_NONE, 0} : m_plan.first_rs;
-        m_firstJinc = rs.kind == RS_UP && rs.method == MPCVR_UPSCALE_Jinc2;
-        m_firstCoords = DrawCoords{org_x, len_x, rev_x ? 1 : 0, (float)len_x / (float)outW,
-                                   org_y, len_y, rev_y ? 1 : 0, (float)len_y / (float)outH, swap ? 1 : 0, tex_x, tex_y, outW, outH};
-        bool ok = true;
-        if (m_firstJinc) {
-            // the 2-D shader needs no tables
-        } else
-        if (taps_on_x) {
-            ok = BuildAxisTaps(rs, org_x, len_x, outW, tex_x, m_cfg.flags, &hx, rev_x, a < 0 ? 0.0f : cscale);
-            BuildPointIndex(org_y, len_y, outH, tex_y, &ox, rev_y);
-        } else {
-            ok = BuildAxisTaps(rs, org_y, len_y, outH, tex_y, m_cfg.flags, &hx, rev_y, cscale);
-            BuildPointIndex(org_x, len_x, outW, tex_x, &ox, rev_x);
-        }
-        if (!ok) return Fail(MPCVR_E_NOTIMPL, "resize ratio outside the supported range");
-        m_firstAxis = taps_on_x ? 0 : 1;
-        m_firstSwap = swap;
-        if (!m_firstJinc) {
-            if ((hr = UploadTaps(hx, m_tapsXi, m_tapsXw, m_tapsXs, m_tapsXb, ox, &m_tapsX))) return hr;
-            if ((hr = UploadIndex(ox, m_otherX))) return hr;
-        }
-        m_jincFirstTab = nullptr; m_jincFirstCtr = nullptr;
-        if (m_firstJinc && (hr = UploadJincPhases(m_firstCoords, m_jincFirst, &m_jincFirstTab, &m_jincFirstCtr))) return hr;
-    }
     if (m_plan.two_pass) {
-        // m_TexResize: fp16, dst width x (source extent along screen y) (:3143-3160); the second draw is unrotated
-        const int mh = m_plan.mid_h;
-        if ((hr = CheckHip(m_TexResize.CheckCreate((size_t)w2 * 8 * mh), "m_TexResize"))) return hr;
-        m_midBytes = (size_t)w2 * 8 * mh;
-        m_secondJinc = m_plan.ry.kind == RS_UP && m_plan.ry.method == MPCVR_UPSCALE_Jinc2;
-        m_secondCoords = DrawCoords{0, w2, 0, 1.0f, 0, mh, 0, (float)mh / (float)h2, 0, w2, mh, w2, h2};
-        m_jincSecondTab = nullptr; m_jincSecondCtr = nullptr;
-        if (m_secondJinc && (hr = UploadJincPhases(m_secondCoords, m_jincSecond, &m_jincSecondTab, &m_jincSecondCtr))) return hr;
-        if (!m_secondJinc) {
-            if (!BuildAxisTaps(m_plan.ry, 0, mh, h2, mh, m_cfg.flags, &hy))
-                return Fail(MPCVR_E_NOTIMPL, "resize ratio outside the supported range");
-            BuildPointIndex(0, w2, w2, w2, &oy);     // Y pass: columns map 1:1
-            if ((hr = UploadTaps(hy, m_tapsYi, m_tapsYw, m_tapsYs, m_tapsYb, oy, &m_tapsY))) return hr;
-            if ((hr = UploadIndex(oy, m_otherY))) return hr;
-        }
+        // m_TexResize: fp16, dst width x (source extent along screen y) (:3143-3160)
+        if ((hr = CheckHip(m_TexResize.CheckCreate((size_t)w2 * 8 * m_plan.mid_h), "m_TexResize"))) return hr;
+        m_midBytes = (size_t)w2 * 8 * m_plan.mid_h;
     }
 
-    // the arbitrary-ratio fused kernel takes an unrotated two-pass resize whose tables fit it: straight from the raw sample for
-    // 4:2:0 sources (m_strip, decided below), else from the convert kernel's output / the RGB source texture (m_stripSurf).
-    // A horizontal flip (FillVertices swaps src_l and src_r, DX11VideoProcessor.cpp:167-169) is the X draw's table read from the other end — per-column tap
-    // indices and weights are what these kernels read anyway — so a flipped frame stays on the fused path.  Rotation 180 also
-    // reverses the first draw's ROW map (m_otherX), which the surface variant reads row by row: a frame turned upside down goes
-    // convert kernel -> m_TexConvertOutput -> k_fused_strip:surface.  90 / 270 turn the first draw into a Y shader and stay per draw
-    m_strip = m_stripSurf = m_stripPlanned = false;
+    // 3. + 4. the tables (vp_plan_tables.h): built as one value, uploaded, then the context's replaced whole
+    {
+        static const bool no_strip_env = [] { const char *e = std::getenv("MPCVR_NO_STRIP"); return e && *e && *e != '0'; }();
+        const PlanTablesInput in{m_srcRect.left, m_srcRect.top, w1, h1, m_srcWidth, m_srcHeight, w2, h2, m_cfg.iUpscaling, m_cfg.flags,
+                                 m_tail == TAIL_PQ_TO_SDR || m_tail == TAIL_HLG_TO_SDR, no_strip_env};
+        PlanTables tables;
+        std::string why;
+        if (!BuildPlanTables(m_plan, in, &tables, &why)) return Fail(MPCVR_E_NOTIMPL, why);
+        if ((hr = UploadPlanTables(tables))) return hr;
+        m_tables = std::move(tables);
+    }
+
+    // 5. Jinc2m phase tables of the draws that run the 2-D shader (their builders live beside the kernels)
+    m_jincFirstTab = m_jincSecondTab = nullptr; m_jincFirstCtr = m_jincSecondCtr = nullptr;
+    if (m_tables.firstJinc && (hr = UploadJincPhases(m_tables.firstCoords, m_jincFirst, &m_jincFirstTab, &m_jincFirstCtr))) return hr;
+    if (m_tables.secondJinc && (hr = UploadJincPhases(m_tables.secondCoords, m_jincSecond, &m_jincSecondTab, &m_jincSecondCtr))) return hr;
+
+    // the arbitrary-ratio fused kernel, where the tables fit it: straight from the raw sample for 4:2:0 sources (m_strip; the probes below
+    // have the last word), else from the convert kernel's output / the RGB source texture (m_stripSurf): a frame turned upside down goes
+    // convert kernel -> m_TexConvertOutput -> k_fused_strip:surface
+    m_stripSurf = false;
     m_stripRan = -1;
-    m_periodPlan.P = 0;
-    static const bool no_strip_env = [] { const char *e = std::getenv("MPCVR_NO_STRIP"); return e && *e && *e != '0'; }();
-    if (!no_strip_env && m_plan.two_pass && !m_firstJinc && !m_secondJinc && m_firstAxis == 0 && !m_firstSwap && (m_plan.rotation == 0 || m_plan.rotation == 180) &&
-        !(m_cfg.flags & (MPCVR_FLAG_NO_FUSED | MPCVR_FLAG_NO_FAST_CONVERT | MPCVR_FLAG_NO_STRIP)) &&
-        PlanFusedStrip(hx, hy, w2, h2, m_plan.convert ? w1 : m_srcWidth, m_plan.mid_h, &m_stripPlan)) {
-        // one buffer: yrange | xstrip | xi_t | xw_t | yi | yw  (all 4-byte words)
-        const StripPlan &sp = m_stripPlan;
-        std::vector<int32_t> pack;
-        auto put = [&pack](const void *src, size_t words) {
-            const size_t at = pack.size();
-            pack.resize(at + words);
-            std::memcpy(pack.data() + at, src, words * 4);
-            return at;
-        };
-        m_stripOff[0] = put(sp.yrange.data(), sp.yrange.size());
-        m_stripOff[1] = put(sp.xstrip.data(), sp.xstrip.size());
-        m_stripOff[2] = put(sp.xi_t.data(), sp.xi_t.size());
-        m_stripOff[3] = put(sp.xw_t.data(), sp.xw_t.size());
-        m_stripOff[4] = put(sp.yi.data(), sp.yi.size());
-        m_stripOff[5] = put(sp.yw.data(), sp.yw.size());
-        // periodic vertical ratio (1080p -> 1440p, 720p -> 1080p, 4K -> 1440p, 4K -> 1080p ...): the register-window kernel's tables
-        m_periodPlan.P = 0;
-        const bool q1 = m_plan.rx.kind == RS_UP && m_plan.ry.kind == RS_UP && m_cfg.iUpscaling == MPCVR_UPSCALE_Lanczos3 && !(m_cfg.flags & MPCVR_FLAG_LANCZOS3_FIXED);
-        // (an interleaved RGB sample without a convert draw is read in place: the X tables then index the whole texture's columns)
-        if (m_plan.rx.kind == RS_UP && m_plan.ry.kind == RS_UP &&
-            PlanFusedPeriod(hx, hy, w2, h2, m_plan.convert ? w1 : m_srcWidth, m_plan.mid_h, q1, &m_periodPlan, m_tail == TAIL_PQ_TO_SDR || m_tail == TAIL_HLG_TO_SDR)) {
-            const PeriodPlan &pp = m_periodPlan;
-            m_periodOff[0] = put(pp.xi_t.data(), pp.xi_t.size());
-            m_periodOff[1] = put(pp.xw_t.data(), pp.xw_t.size());
-            while (pack.size() & 7) pack.push_back(0);                      // the weight rows (32 bytes each) are read with scalar multi-dword loads
-            m_periodOff[2] = put(pp.yw.data(), pp.yw.size());
-            m_periodOff[3] = put(pp.xstrip.data(), pp.xstrip.size());
-        }
-        if ((hr = CheckHip(m_stripTab.CheckCreate(pack.size() * sizeof(int32_t)), "strip tables"))) return hr;
-        if ((hr = CheckHip(hipMemcpy(m_stripTab.ptr, pack.data(), pack.size() * sizeof(int32_t), hipMemcpyHostToDevice), "strip tables upload"))) return hr;
-        m_stripPlanned = true;
-        m_strip = m_plan.convert && !m_doviValid && m_plan.internal_fmt != SF_RGBA16F && m_plan.rotation == 0;
-    }
+    m_strip = m_tables.stripPlanned && m_plan.convert && !m_doviValid && m_plan.internal_fmt != SF_RGBA16F && m_plan.rotation == 0;
 
-    // PQ -> SDR table: the fused kernel's tone-map stage and the folded convert kernel's
+    // 6. the LUTs and the exact-2x kernel's baked image.  PQ -> SDR table: the fused kernel's tone-map stage and the folded convert kernel's
     if (m_tail == TAIL_PQ_TO_SDR) {
         if (!m_blobOverride) BuildPqSdrLut(m_lumScale, m_pqLutHost);
         if ((hr = CheckHip(m_pqLut.CheckCreate(sizeof(m_pqLutHost)), "pq lut"))) return hr;
@@ -715,6 +571,7 @@ HRESULT CHipVideoProcessor::UpdatePlan()
             m_jincFusedTab = (const float *)m_jincFused.ptr;
         }
     }
+    // 7. the exact-2x weights
     if (m_plan.fused_up2x) {
         if (!m_plan.fused_jinc && (!m_blobOverride || m_upX.ntaps == 0)) {
             float w[6];
@@ -736,6 +593,7 @@ HRESULT CHipVideoProcessor::UpdatePlan()
         static const bool no_up2x_env = [] { const char *e = std::getenv("MPCVR_NO_UP2X"); return e && *e && *e != '0'; }();
         if (no_up2x_env && m_strip) m_plan.fused_up2x = false;
     }
+    // 8. the launch-time probes
     m_period = false;
     // the store the resize draws will meet: the render target, or m_TexsPostScale in front of the HDR10 tone-mapping step (:3359-3367)
     const StoreParams probeStore = m_plan.hdr_tonemap ? MakeStore(nullptr, (int)(w2 * SurfBytesPerPixel(m_plan.internal_fmt)), m_plan.internal_fmt, false)
@@ -745,7 +603,7 @@ HRESULT CHipVideoProcessor::UpdatePlan()
         m_strip = FillStripParams(nullptr, nullptr, probeStore.dst_pitch, probeStore, &sp);
         m_period = m_strip && FusedPeriodTakes(sp);
     }
-    if (m_stripPlanned && !m_strip) {
+    if (m_tables.stripPlanned && !m_strip) {
         FusedStripParams sp{};
         const Surface probe = m_plan.convert ? Surface{nullptr, (int)(w1 * SurfBytesPerPixel(m_plan.internal_fmt)), w1, h1, m_plan.internal_fmt}
                                              : Surface{nullptr, TexPitch(), m_srcWidth, m_srcHeight, RgbTexFmt(*m_srcParams)};
@@ -780,15 +638,7 @@ HRESULT CHipVideoProcessor::UploadJincPhases(const DrawCoords &dc, DevBuffer &bu
     return MPCVR_S_OK;
 }
 
-// m_PSConvColorData.bEnable — DX11VideoProcessor.cpp:849-853: interleaved RGB skips the convert draw unless brightness
-// or contrast are set (hue / saturation do not count)
-bool CHipVideoProcessor::ConvertEnabled() const
-{
-    const FmtConvParams &f = *m_srcParams;
-    if (m_doviValid) return true;                                              // :834
-    if (f.CSType == CST_YUV || f.CSType == CST_GRAY || (f.CSType == CST_RGB && f.planes == 3)) return true;
-    return std::fabs(m_procAmp.brightness / 255) > 1e-4f || std::fabs(m_procAmp.contrast - 1.0f) > 1e-4f;
-}
+bool CHipVideoProcessor::ConvertEnabled() const { return ConvertDrawEnabled(*m_srcParams, m_procAmp, m_doviValid); }
 
 int CHipVideoProcessor::TexPitch() const
 {
@@ -1045,23 +895,23 @@ HRESULT CHipVideoProcessor::ResizeShaderPass(const uint8_t *sample, void *rt, in
         if (df.lastTab) ssp.fp.dst_aligned16 = df.aligned;
         const FusedFrame one = df.lastTab ? FusedFrame{nullptr, nullptr} : FusedFrame{(const uint8_t *)conv.ptr, last.dst};
         hr = CheckHip(LaunchFusedStrip(ssp, df.lastTab, one, df.n, on.stream), "k_fused_strip<surface>");
-    } else if (m_plan.two_pass && !plain && !m_firstJinc && !m_secondJinc && m_firstAxis == 0 && !m_firstSwap &&
+    } else if (m_plan.two_pass && !plain && !m_tables.firstJinc && !m_tables.secondJinc && m_tables.firstAxis == 0 && !m_tables.firstSwap &&
         Resize2DSupported(conv, m_tapsX, m_tapsY, last)) {
         // both draws in one LDS-tiled kernel: m_TexResize stays on chip
-        hr = CheckHip(LaunchResize2D(conv, m_tapsX, m_tapsY, (const int32_t *)m_otherX.ptr, m_plan.mid_h, w2, h2, last, on.stream, &b), "k_resize_2d");
+        hr = CheckHip(LaunchResize2D(conv, m_tapsX, m_tapsY, m_otherX, m_plan.mid_h, w2, h2, last, on.stream, &b), "k_resize_2d");
     } else if (m_plan.two_pass) {
         Surface mid{df.mid, w2 * 8, w2, m_plan.mid_h, SF_RGBA16F};
         StoreParams st = MakeStore(mid.ptr, mid.pitch, SF_RGBA16F, false);
         ResizeBatch b1; b1.n = df.n; b1.in_stride = df.convStride; b1.dst_stride = df.midStride;
-        if (m_firstJinc) hr = CheckHip(LaunchJinc2(conv, m_firstCoords, w2, m_plan.mid_h, st, on.stream, m_jincFirstTab, jfast, &b1, m_jincFirstCtr), "k_jinc2");
-        else hr = CheckHip(LaunchResize(m_firstAxis, m_firstSwap, conv, m_tapsX, (const int32_t *)m_otherX.ptr, w2, m_plan.mid_h, st, on.stream, plain, &b1), "k_resize<first>");
+        if (m_tables.firstJinc) hr = CheckHip(LaunchJinc2(conv, m_tables.firstCoords, w2, m_plan.mid_h, st, on.stream, m_jincFirstTab, jfast, &b1, m_jincFirstCtr), "k_jinc2");
+        else hr = CheckHip(LaunchResize(m_tables.firstAxis, m_tables.firstSwap, conv, m_tapsX, m_otherX, w2, m_plan.mid_h, st, on.stream, plain, &b1), "k_resize<first>");
         if (hr) return hr;
         ResizeBatch b2 = b; b2.in_stride = df.midStride;
-        if (m_secondJinc) hr = CheckHip(LaunchJinc2(mid, m_secondCoords, w2, h2, last, on.stream, m_jincSecondTab, jfast, &b2, m_jincSecondCtr), "k_jinc2");
-        else hr = CheckHip(LaunchResize(1, false, mid, m_tapsY, (const int32_t *)m_otherY.ptr, w2, h2, last, on.stream, plain, &b2), "k_resize<Y>");
+        if (m_tables.secondJinc) hr = CheckHip(LaunchJinc2(mid, m_tables.secondCoords, w2, h2, last, on.stream, m_jincSecondTab, jfast, &b2, m_jincSecondCtr), "k_jinc2");
+        else hr = CheckHip(LaunchResize(1, false, mid, m_tapsY, m_otherY, w2, h2, last, on.stream, plain, &b2), "k_resize<Y>");
     } else if (m_plan.one_pass) {
-        if (m_firstJinc) hr = CheckHip(LaunchJinc2(conv, m_firstCoords, w2, h2, last, on.stream, m_jincFirstTab, jfast, &b, m_jincFirstCtr), "k_jinc2");
-        else hr = CheckHip(LaunchResize(m_firstAxis, m_firstSwap, conv, m_tapsX, (const int32_t *)m_otherX.ptr, w2, h2, last, on.stream, plain, &b), "k_resize<one>");
+        if (m_tables.firstJinc) hr = CheckHip(LaunchJinc2(conv, m_tables.firstCoords, w2, h2, last, on.stream, m_jincFirstTab, jfast, &b, m_jincFirstCtr), "k_jinc2");
+        else hr = CheckHip(LaunchResize(m_tables.firstAxis, m_tables.firstSwap, conv, m_tapsX, m_otherX, w2, h2, last, on.stream, plain, &b), "k_resize<one>");
     } else {
         drawn = false;
         if (!m_plan.convert) {    // the next step reads the source rect of the texture (pTex = pInputTexture, :3352)
@@ -1086,16 +936,18 @@ bool CHipVideoProcessor::FillStripTables(const StoreParams &store, int perForce,
 {
     sp->fp.store = store;
     sp->ran_period = &m_stripRan;
+    if (!m_tables.stripPlanned) return false;
     const int32_t *tab = (const int32_t *)m_stripTab.ptr;
-    sp->yrange = tab + m_stripOff[0]; sp->xstrip = tab + m_stripOff[1];
-    sp->xi_t = tab + m_stripOff[2]; sp->xw_t = tab + m_stripOff[3];
-    sp->yi = tab + m_stripOff[4]; sp->yw = tab + m_stripOff[5];
+    const size_t *so = m_tables.stripPack.stripOff, *po = m_tables.stripPack.periodOff;
+    sp->yrange = tab + so[0]; sp->xstrip = tab + so[1];
+    sp->xi_t = tab + so[2]; sp->xw_t = tab + so[3];
+    sp->yi = tab + so[4]; sp->yw = tab + so[5];
     sp->out_w = m_videoRect.Width(); sp->out_h = m_videoRect.Height();
-    sp->nt = m_stripPlan.nt; sp->pxl = m_stripPlan.pxl; sp->strip_w = m_stripPlan.strip_w; sp->ring = m_stripPlan.ring; sp->acols = m_stripPlan.acols;
+    sp->nt = m_tables.strip.nt; sp->pxl = m_tables.strip.pxl; sp->strip_w = m_tables.strip.strip_w; sp->ring = m_tables.strip.ring; sp->acols = m_tables.strip.acols;
     sp->per_P = 0;
-    if (m_periodPlan.P && !(m_cfg.flags & MPCVR_FLAG_NO_PERIOD)) {
-        sp->per_P = m_periodPlan.P; sp->per_Q = m_periodPlan.Q; sp->per_nt = m_periodPlan.nt; sp->per_acols = m_periodPlan.acols; sp->per_strip_w = m_periodPlan.strip_w; sp->per_own = m_periodPlan.own; sp->per_force = perForce;
-        sp->per_xi_t = tab + m_periodOff[0]; sp->per_xw_t = tab + m_periodOff[1]; sp->per_yw = tab + m_periodOff[2]; sp->per_xstrip = tab + m_periodOff[3];
+    if (m_tables.period.P && !(m_cfg.flags & MPCVR_FLAG_NO_PERIOD)) {
+        sp->per_P = m_tables.period.P; sp->per_Q = m_tables.period.Q; sp->per_nt = m_tables.period.nt; sp->per_acols = m_tables.period.acols; sp->per_strip_w = m_tables.period.strip_w; sp->per_own = m_tables.period.own; sp->per_force = perForce;
+        sp->per_xi_t = tab + po[0]; sp->per_xw_t = tab + po[1]; sp->per_yw = tab + po[2]; sp->per_xstrip = tab + po[3];
     }
     return FusedStripSupported(*sp) && FusedStripLdsBytes(*sp) <= DeviceLdsLimit();
 }
@@ -1118,7 +970,7 @@ bool CHipVideoProcessor::FillStripSurfParams(const Surface &src, const StorePara
     sp->fp.dst_aligned16 = (((uintptr_t)store.dst) & 7) == 0;
     sp->surface_mode = 1;
     sp->surf = src;
-    sp->other = m_otherX.ptr && !m_tapsX.other_identity ? (const int32_t *)m_otherX.ptr : nullptr;
+    sp->other = m_tapsX.other_identity ? nullptr : m_otherX;
     sp->mid_h = m_plan.mid_h;
     return FillStripTables(store, 1, sp);      // (per_force: with a periodic vertical ratio the register-window kernel reads the surface as well)
 }
@@ -2114,9 +1966,9 @@ std::string CHipVideoProcessor::GetPathInfo()
     if (m_planDirty && UpdatePlan() != MPCVR_S_OK) return "error: " + m_lastError;
     if ((!m_strip && !m_stripSurf) || m_plan.fused_up2x) return m_plan.describe();
     if ((m_strip || m_stripSurf) && (m_stripRan >= 0 ? m_stripRan == 1 : m_period))
-        return m_plan.describe() + (m_strip ? ";kernel=fused_period(rows=" : ";kernel=fused_period:surface(rows=") + std::to_string(m_periodPlan.P) + ":" + std::to_string(m_periodPlan.Q) + ",taps=" + std::to_string(m_periodPlan.nt) + ",px_per_lane=2,strip=" + std::to_string(m_periodPlan.strip_w) + ",window=6 rows in registers)";
-    return m_plan.describe() + (m_strip ? ";kernel=fused_strip(taps=" : ";kernel=fused_strip:surface(taps=") + std::to_string(m_stripPlan.nt) + ",px_per_lane=" + std::to_string(m_stripPlan.pxl) +
-           ",strip=" + std::to_string(m_stripPlan.strip_w) + ",ring=" + std::to_string(m_stripPlan.ring) + ")";
+        return m_plan.describe() + (m_strip ? ";kernel=fused_period(rows=" : ";kernel=fused_period:surface(rows=") + std::to_string(m_tables.period.P) + ":" + std::to_string(m_tables.period.Q) + ",taps=" + std::to_string(m_tables.period.nt) + ",px_per_lane=2,strip=" + std::to_string(m_tables.period.strip_w) + ",window=6 rows in registers)";
+    return m_plan.describe() + (m_strip ? ";kernel=fused_strip(taps=" : ";kernel=fused_strip:surface(taps=") + std::to_string(m_tables.strip.nt) + ",px_per_lane=" + std::to_string(m_tables.strip.pxl) +
+           ",strip=" + std::to_string(m_tables.strip.strip_w) + ",ring=" + std::to_string(m_tables.strip.ring) + ")";
 }
 
 // FrameStats.h:145-173: copyticks (:2594), paintticks (:2790) and the snapshot's read-back; -1 = not timed yet

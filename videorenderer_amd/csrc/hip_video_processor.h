@@ -14,6 +14,7 @@
 #include "vp_launch.h"
 #include "vp_params.h"
 #include "vp_plan.h"
+#include "vp_plan_tables.h"
 
 namespace mpcvr {
 
@@ -119,8 +120,7 @@ private:
     // Process with what Render and the snapshot add: clearBytes of the back buffer are cleared in front of the frame, on whatever stream it
     // runs on; onContextStream: the frame stays off the lanes (a read-back follows on the context stream)
     HRESULT ProcessFrame(void *pRenderTarget, int rtPitch, const CRect *srcRect, const CRect *dstRect, size_t clearBytes, bool onContextStream);
-    HRESULT UploadTaps(const HostAxisTaps &h, DevBuffer &bi, DevBuffer &bw, DevBuffer &bs, DevBuffer &bb, const std::vector<int32_t> &other, AxisTaps *out);
-    HRESULT UploadIndex(const std::vector<int32_t> &v, DevBuffer &b);
+    HRESULT UploadPlanTables(const PlanTables &t);     // one copy per axis pack, one for the strip pack; sets the views below
     bool ConvertEnabled() const;                       // m_PSConvColorData.bEnable (:849-853)
     int TexPitch() const;                              // row pitch of the source texture (differs from the sample's for v210)
     HRESULT PrepareSample(const uint8_t *dev_sample, const uint8_t **tex);   // device sample -> source texture
@@ -228,10 +228,6 @@ private:
     HRESULT RunBatch(BatchRun &run);                  // a validated batch: the plan, then error diffusion or the routes
     HRESULT ProcessBatchRoutes(BatchRun &run);
     bool ToneMapActive() const;
-    int m_firstAxis = 0;           // screen axis the first draw's tap table runs along
-    bool m_firstSwap = false;      // rotation 90/270: taps address the other texture axis
-    bool m_firstJinc = false, m_secondJinc = false;    // the draw runs the 2-D Jinc2m shader
-    DrawCoords m_firstCoords{}, m_secondCoords{};
 
     // input
     const FmtConvParams *m_srcParams = nullptr;
@@ -293,8 +289,12 @@ private:
     const float *m_fusedTabLut = nullptr;           // the device table its tone-map part was baked from (null: none)
     bool m_fusedTabValid = false;
     HRESULT UploadFusedTables();
-    DevBuffer m_tapsXi, m_tapsXw, m_tapsXs, m_tapsYi, m_tapsYw, m_tapsYs, m_otherX, m_otherY, m_tapsXb, m_tapsYb;
+    // The current plan's tables (vp_plan_tables.h), replaced whole by UpdatePlan, and their copies on the device: one buffer per axis
+    // pack and m_stripTab.  m_tapsX / m_tapsY / m_otherX / m_otherY are views of those copies: null where the plan has no such table
+    PlanTables m_tables;
+    DevBuffer m_axisX, m_axisY;
     AxisTaps m_tapsX{}, m_tapsY{};
+    const int32_t *m_otherX = nullptr, *m_otherY = nullptr;
     // ring of frame-table slots for mpcvr_process_batch (pinned host copy + device copy + completion event)
     static constexpr int kFrameSlots = 4;
     TableSlot m_slots[kFrameSlots];
@@ -348,18 +348,13 @@ private:
     // arbitrary-ratio fused kernel (vp_fused_strip.hip): geometry planned with the tap tables (UpdatePlan)
     bool m_strip = false;          // raw 4:2:0 sample -> render target in one kernel
     bool m_stripSurf = false;      // any other source: the convert kernel's output (or the RGB source texture) -> render target through the same kernel, no convert stage
-    bool m_stripPlanned = false;
     bool FillStripSurfParams(const Surface &src, const StoreParams &store, FusedStripParams *sp) const;
-    StripPlan m_stripPlan;
-    DevBuffer m_stripTab;          // yrange | xstrip | xi_t | xw_t | yi | yw, word offsets in m_stripOff
-    size_t m_stripOff[6] = {0, 0, 0, 0, 0, 0};
+    DevBuffer m_stripTab;          // m_tables.stripPack on the device
     bool FillStripParams(const uint8_t *sample, void *dst, int dstPitch, const StoreParams &store, FusedStripParams *sp, int inflight = 1) const;
     bool FillStripTables(const StoreParams &store, int perForce, FusedStripParams *sp) const;     // what the two above share
-    // periodic-phase variant of the same launch (vp_fused_period.h): vertical ratio 4:3 / 3:2 / 2:3 / 1:2 / 3:1, tables behind the strip kernel's in m_stripTab
-    PeriodPlan m_periodPlan;       // P == 0: not a periodic geometry
+    // periodic-phase variant of the same launch (vp_fused_period.h): vertical ratio 4:3 / 3:2 / 2:3 / 1:2 / 3:1, tables behind the strip kernel's in m_stripTab (m_tables.period)
     mutable int m_stripRan = -1;   // which kernel the last strip launch of this plan really ran (1 = k_fused_period, 0 = k_fused_strip, -1 = none yet): the plan-time
                                    // probe uses a null, aligned target — a real target with an odd pitch or offset sends the launch to k_fused_strip (GetPathInfo reports what ran)
-    size_t m_periodOff[4] = {0, 0, 0, 0};     // xi_t | xw_t | yw | xstrip
     bool m_period = false;         // the planned launch (window-sized target) takes the periodic kernel: what GetVPInfo reports
     // the route of a mpcvr_process_batch call, in order of precedence (ClassifyBatch), and what its launches need
     enum class BatchRoute { DirectConvert, RgbSurfaceStrip, StripToneMap, FrameByFrame, WholeBatchLaunches, Strip, FusedUp2x };

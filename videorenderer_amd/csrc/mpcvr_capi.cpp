@@ -209,6 +209,7 @@ int32_t mpcvr_get_last_timings(mpcvr_ctx *ctx, float *copy_host_ms, float *uploa
 // What the reference computes on the CPU before it ever touches the device: format table, extended
 // format defaults, colour / gamut matrices, resize weights, tap tables and the pass plan.
 #include "vp_plan.h"
+#include "vp_plan_tables.h"
 
 extern "C" {
 
@@ -341,18 +342,35 @@ int32_t mpcvr_plan_axis_taps(int32_t kind, int32_t method, int32_t src_l, int32_
     return MPCVR_S_OK;
 }
 
+// the tables of an unrotated two-pass resize of a converted src_w x src_h frame, from the planner the processor runs (BuildPlanTables): X from
+// the convert output (rect at the origin), Y from m_TexResize (src_h rows).  The routing flags do not reach it: these entry points describe
+// the kernels' geometry, whichever path a context with those flags would take
+static bool TwoPassTables(mpcvr::Resizer rx, mpcvr::Resizer ry, int src_w, int src_h, int out_w, int out_h, int iUpscaling, uint32_t flags, mpcvr::PlanTables *t)
+{
+    mpcvr::PassPlan plan;
+    plan.two_pass = true;
+    plan.rx = plan.first_rs = rx; plan.ry = ry;
+    plan.first_tex_axis = 0;
+    plan.mid_h = src_h;
+    mpcvr::PlanTablesInput in;
+    in.srcRectW = in.texW = src_w; in.srcRectH = in.texH = src_h;
+    in.outW = out_w; in.outH = out_h;
+    in.iUpscaling = iUpscaling;
+    in.flags = flags & ~(uint32_t)(MPCVR_FLAG_NO_FUSED | MPCVR_FLAG_NO_FAST_CONVERT | MPCVR_FLAG_NO_STRIP);
+    in.heavyConvert = true;
+    std::string why;
+    return mpcvr::BuildPlanTables(plan, in, t, &why) && t->stripPlanned;
+}
+
 int32_t mpcvr_plan_strip(int32_t kind_x, int32_t method_x, int32_t kind_y, int32_t method_y, int32_t src_w, int32_t src_h,
                          int32_t out_w, int32_t out_h, uint32_t flags, int32_t out8[8], int32_t *yrange, int32_t *xstrip,
                          int32_t *xi_t, float *xw_t, int32_t *yi, float *yw)
 {
     if (!out8) return MPCVR_E_POINTER;
     if (src_w <= 0 || src_h <= 0 || out_w <= 0 || out_h <= 0) return MPCVR_E_INVALIDARG;
-    mpcvr::HostAxisTaps hx, hy;
-    // the draws as UpdatePlan builds them: X from the convert output (rect at the origin), Y from m_TexResize (src_h rows)
-    if (!mpcvr::BuildAxisTaps(mpcvr::Resizer{kind_x, method_x}, 0, src_w, out_w, src_w, flags, &hx)) return MPCVR_E_NOTIMPL;
-    if (!mpcvr::BuildAxisTaps(mpcvr::Resizer{kind_y, method_y}, 0, src_h, out_h, src_h, flags, &hy)) return MPCVR_E_NOTIMPL;
-    mpcvr::StripPlan sp;
-    if (!mpcvr::PlanFusedStrip(hx, hy, out_w, out_h, src_w, src_h, &sp)) return MPCVR_E_NOTIMPL;
+    mpcvr::PlanTables t;
+    if (!TwoPassTables(mpcvr::Resizer{kind_x, method_x}, mpcvr::Resizer{kind_y, method_y}, src_w, src_h, out_w, out_h, method_x, flags, &t)) return MPCVR_E_NOTIMPL;
+    const mpcvr::StripPlan &sp = t.strip;
     const int strips = (out_w + sp.strip_w - 1) / sp.strip_w;
     const int per_wave = 2 * sp.acols * 8 + sp.ring * 64 * (sp.pxl == 2 ? 12 : 8);
     const int32_t o[8] = {sp.nt, sp.pxl, sp.strip_w, sp.ring, sp.acols, strips, per_wave, 0};
@@ -371,12 +389,10 @@ int32_t mpcvr_plan_period(int32_t method, int32_t src_w, int32_t src_h, int32_t 
 {
     if (!out6) return MPCVR_E_POINTER;
     if (src_w <= 0 || src_h <= 0 || out_w <= 0 || out_h <= 0) return MPCVR_E_INVALIDARG;
-    mpcvr::HostAxisTaps hx, hy;
-    if (!mpcvr::BuildAxisTaps(mpcvr::Resizer{mpcvr::RS_UP, method}, 0, src_w, out_w, src_w, flags, &hx)) return MPCVR_E_NOTIMPL;
-    if (!mpcvr::BuildAxisTaps(mpcvr::Resizer{mpcvr::RS_UP, method}, 0, src_h, out_h, src_h, flags, &hy)) return MPCVR_E_NOTIMPL;
-    const bool q1 = method == MPCVR_UPSCALE_Lanczos3 && !(flags & MPCVR_FLAG_LANCZOS3_FIXED);
-    mpcvr::PeriodPlan pp;
-    if (!mpcvr::PlanFusedPeriod(hx, hy, out_w, out_h, src_w, src_h, q1, &pp)) return MPCVR_E_NOTIMPL;
+    mpcvr::PlanTables t;
+    const mpcvr::Resizer up{mpcvr::RS_UP, method};
+    if (!TwoPassTables(up, up, src_w, src_h, out_w, out_h, method, flags, &t) || !t.period.P) return MPCVR_E_NOTIMPL;
+    const mpcvr::PeriodPlan &pp = t.period;
     const int32_t o[6] = {pp.P, pp.Q, pp.nt, (out_w + pp.strip_w - 1) / pp.strip_w, pp.acols, 6 * pp.P / pp.Q};
     if (strip_w) *strip_w = pp.strip_w;
     std::memcpy(out6, o, sizeof(o));
@@ -384,6 +400,69 @@ int32_t mpcvr_plan_period(int32_t method, int32_t src_w, int32_t src_h, int32_t 
     if (xw_t) std::memcpy(xw_t, pp.xw_t.data(), pp.xw_t.size() * sizeof(float));
     if (yw) std::memcpy(yw, pp.yw.data(), pp.yw.size() * sizeof(float));
     if (xstrip) std::memcpy(xstrip, pp.xstrip.data(), pp.xstrip.size() * sizeof(int32_t));
+    return MPCVR_S_OK;
+}
+
+int32_t mpcvr_plan_draw_tables(const mpcvr_settings *s, int32_t cformat, int32_t src_w, int32_t src_h, const mpcvr_rect *src_rect,
+                               const mpcvr_rect *video_rect, int32_t window_w, int32_t window_h, int32_t rotation, int32_t flip,
+                               void *buf, size_t *size)
+{
+    if (!s || !video_rect || !size) return MPCVR_E_POINTER;
+    const mpcvr::FmtConvParams *f = mpcvr::GetFmtConvParams(cformat);
+    if (!f) return MPCVR_E_NOTIMPL;
+    const mpcvr_rect whole{0, 0, src_w, src_h};
+    const mpcvr_rect r = src_rect ? *src_rect : whole;
+    const int w1 = r.right - r.left, h1 = r.bottom - r.top;
+    if (src_w <= 0 || src_h <= 0 || r.left < 0 || r.top < 0 || r.right > src_w || r.bottom > src_h || w1 <= 0 || h1 <= 0 ||
+        video_rect->right <= video_rect->left || video_rect->bottom <= video_rect->top || window_w <= 0 || window_h <= 0 ||
+        (rotation != 0 && rotation != 90 && rotation != 180 && rotation != 270)) return MPCVR_E_INVALIDARG;
+    // a context fresh from mpcvr_set_input: default ProcAmp, the extended format's defaults, no HDR output, no Dolby Vision
+    const mpcvr::PlanGeometry g{w1, h1, video_rect->left, video_rect->top, video_rect->right, video_rect->bottom, window_w, window_h,
+                                rotation, flip ? 1 : 0, mpcvr::ConvertDrawEnabled(*f, mpcvr::ProcAmp(), false) ? 1 : 0, 0, 0};
+    mpcvr::PassPlan plan;
+    std::string why;
+    if (!mpcvr::DecidePlan(s->iTexFormat, s->iChromaScaling, s->iUpscaling, s->iDownscaling, s->bInterpolateAt50pct,
+                           s->bUseDither, s->output_format, s->flags, *f, g, &plan, &why)) return MPCVR_E_NOTIMPL;
+    int tail = 0; float gamma = 1.0f;
+    mpcvr::SelectTail(mpcvr::SpecifyExtendedFormat(mpcvr::ExtFmt{0}, *f, w1, h1), s->bConvertToSdr != 0, &tail, &gamma);
+    const mpcvr::PlanTablesInput in{r.left, r.top, w1, h1, src_w, src_h, video_rect->right - video_rect->left, video_rect->bottom - video_rect->top,
+                                    s->iUpscaling, s->flags, tail == mpcvr::TAIL_PQ_TO_SDR || tail == mpcvr::TAIL_HLG_TO_SDR, false};
+    mpcvr::PlanTables t;
+    if (!mpcvr::BuildPlanTables(plan, in, &t, &why)) return MPCVR_E_NOTIMPL;
+
+    int32_t h[MPCVR_DRAW_TABLES_HEADER_WORDS] = {0};
+    size_t at = MPCVR_DRAW_TABLES_HEADER_WORDS;
+    h[0] = MPCVR_DRAW_TABLES_HEADER_WORDS;
+    h[1] = t.firstAxis; h[2] = t.firstSwap; h[3] = t.firstJinc; h[4] = t.secondJinc; h[5] = t.stripPlanned; h[6] = t.period.P; h[7] = t.period.Q;
+    const mpcvr::AxisPack *axes[2] = {&t.x, &t.y};
+    for (int a = 0; a < 2; a++) {
+        const mpcvr::AxisPack &p = *axes[a];
+        int32_t *o = h + 8 + 16 * a;
+        o[0] = (int32_t)at; o[1] = (int32_t)p.words.size();
+        o[2] = p.ntaps; o[3] = p.normalise; o[4] = p.n_out; o[5] = p.blk_span; o[6] = p.blk8_span; o[7] = p.blk32_span; o[8] = p.other_identity;
+        o[9] = (int32_t)p.offIdx; o[10] = (int32_t)p.offW; o[11] = p.normalise ? (int32_t)p.offWsum : -1; o[12] = (int32_t)p.offOther;
+        o[13] = p.n_out > 0 ? (int32_t)p.offBlk : -1; o[14] = (int32_t)p.nOther;
+        at += p.words.size();
+    }
+    int32_t *o = h + 40;
+    o[0] = (int32_t)at; o[1] = (int32_t)t.stripPack.words.size();
+    for (int i = 0; i < 6; i++) o[2 + i] = (int32_t)t.stripPack.stripOff[i];
+    for (int i = 0; i < 4; i++) o[8 + i] = (int32_t)t.stripPack.periodOff[i];
+    o[12] = t.strip.nt; o[13] = t.strip.pxl; o[14] = t.strip.strip_w; o[15] = t.strip.ring; o[16] = t.strip.acols;
+    o[17] = t.period.nt; o[18] = t.period.acols; o[19] = t.period.strip_w; o[20] = t.period.own;
+    at += t.stripPack.words.size();
+
+    const size_t need = at * sizeof(int32_t);
+    if (!buf) { *size = need; return MPCVR_S_OK; }
+    if (*size < need) { *size = need; return MPCVR_E_INVALIDARG; }
+    int32_t *out = (int32_t *)buf;
+    std::memcpy(out, h, sizeof(h));
+    out += MPCVR_DRAW_TABLES_HEADER_WORDS;
+    for (const std::vector<int32_t> *w : {&t.x.words, &t.y.words, &t.stripPack.words}) {
+        if (!w->empty()) std::memcpy(out, w->data(), w->size() * sizeof(int32_t));
+        out += w->size();
+    }
+    *size = need;
     return MPCVR_S_OK;
 }
 
