@@ -275,6 +275,15 @@ int32_t mpcvr_set_procamp(mpcvr_ctx *ctx, uint32_t flags, float brightness, floa
  * targets, mpcvr_render, the snapshot): its slot is reused behind all of them.
  * MPCVR_MEM_DEVICE: zero-copy — the pointer is used in place and must stay valid until
  * the following process/render call has completed (mirrors the IMediaSampleD3D11 branch :2528-2569).
+ * Which bits of a sample are read (the same on every route, tier and mem_kind; tests/test_sample_bits*.py):
+ *   8- and 16-bit components (NV12, YV12 .. YUV444P16, P016 / P216, Y216, Y416, GBRP8 / 16, Y8 / Y16, RGB24 / 48, BGR48): every bit;
+ *   P010, P210, Y210: all 16 bits of a word, the six under the 10-bit code included (the reference's texture is 16-bit UNORM);
+ *   YUV420P10 / 422P10 / 444P10, GBRP10, Y10: bits 0..9 of a word — bits 10..15 are dropped, a word of 1024 + k reads as k
+ *     (CopyPlane10to16 stores word << 6 into 16 bits, Helper.cpp:789-803);
+ *   Y410, r210, v210: the three 10-bit fields of a dword; Y410's alpha bits, r210's two pad bits, bits 30..31 of a v210 dword and the
+ *     v210 fields past the width in a row's last six-pixel group are ignored;
+ *   AYUV, Y416, XRGB32 / ARGB32, BGRA64, b64a: the three colour components; the A / X component is ignored.
+ *   Bytes between a row's pixels and the pitch are never read into a pixel.
  * Refusals — a NULL data: MPCVR_E_POINTER; a pitch that is not the media type's: MPCVR_E_UNEXPECTED (:2545); a mem_kind
  * that is none of the three: MPCVR_E_INVALIDARG — are answered before anything is touched: the sample handed over
  * before stays current and the next mpcvr_process draws it.  After mpcvr_flush there is no current sample

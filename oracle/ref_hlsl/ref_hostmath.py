@@ -8,6 +8,7 @@ oracle/_ref/libref_hostmath.so holds, compiled from the text of /root/reference 
   SetDolbyVisionDynamicParams                     DX11VideoProcessor.cpp:953-960    DoViDynamicConstantsBuffer_t
   SpecifyExtendedFormat                           Helper.cpp:1169-1211
   CopyFrameV210                                   Helper.cpp:709-748
+  CopyPlane10to16                                 Helper.cpp:789-803
   CopyPlaneAsIs, CopyFrameRGB24 / R210 / RGB48 / BGR48 / BGRA64 / B64A   Helper.cpp:414-483,541-566,600-677,769-787 (interleaved RGB uploads)
 
 The extraction is MECHANICAL, like hlsl2cpp.py's: this file knows where a region starts and ends (an anchor line each) and what
@@ -82,6 +83,7 @@ def generate():
         _braces(hp, "void CopyFrameBGRA64("),
         _braces(hp, "void CopyFrameB64A("),
         _braces(hp, "void CopyFrameR210("),
+        _braces(hp, "void CopyPlane10to16("),
     ])
     # member functions, cut where the D3D buffer plumbing starts
     poly = _cut(vp, "PS_DOVI_POLY_CURVE polyCurves[3] = {};", "HRESULT hr;", after=vp.index("CDX11VideoProcessor::SetShaderDoviCurvesPoly()"))
@@ -211,6 +213,10 @@ void ref_copy_frame_v210(unsigned lines, unsigned char* dst, unsigned dst_pitch,
 {{
     CopyFrameV210(lines, dst, dst_pitch, src, src_pitch);
 }}
+void ref_copy_plane_10to16(unsigned lines, unsigned char* dst, unsigned dst_pitch, const unsigned char* src, int src_pitch)
+{{
+    CopyPlane10to16(lines, dst, dst_pitch, src, src_pitch);
+}}
 // kind: 0 CopyPlaneAsIs, 1 CopyFrameRGB24, 2 CopyFrameR210, 3 CopyFrameRGB48, 4 CopyFrameBGR48, 5 CopyFrameBGRA64, 6 CopyFrameB64A
 // (the order of the oracle's RPK_* codes)
 void ref_copy_frame_rgb(int kind, unsigned lines, unsigned char* dst, unsigned dst_pitch, const unsigned char* src, int src_pitch)
@@ -255,6 +261,9 @@ def lib():
                 return None
             build()
         L = C.CDLL(LIB)
+        if not hasattr(L, "ref_copy_plane_10to16") and have_reference():        # a library built before the function was added
+            build()
+            L = C.CDLL(LIB)
         L.ref_dovi_curves.restype = C.c_int
         L.ref_dovi_curves.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.ref_dovi_levels.restype = C.c_int
@@ -263,6 +272,8 @@ def lib():
         L.ref_specify_extfmt.restype = C.c_uint
         L.ref_specify_extfmt.argtypes = [C.c_uint, C.c_int, C.c_int, C.c_uint, C.c_uint]
         L.ref_copy_frame_v210.argtypes = [C.c_uint, C.c_void_p, C.c_uint, C.c_void_p, C.c_int]
+        if hasattr(L, "ref_copy_plane_10to16"):
+            L.ref_copy_plane_10to16.argtypes = [C.c_uint, C.c_void_p, C.c_uint, C.c_void_p, C.c_int]
         L.ref_copy_frame_rgb.argtypes = [C.c_int, C.c_uint, C.c_void_p, C.c_uint, C.c_void_p, C.c_int]
         _lib = L
     return _lib

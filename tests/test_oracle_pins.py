@@ -715,6 +715,28 @@ def test_rgb_upload_copies_against_reference_code(oracle):
         assert got == rec["sha256"], rec
 
 
+def test_copy_plane_10to16_drops_the_bits_above_the_tenth(oracle):
+    """CopyPlane10to16 (Helper.cpp:789-803: dst16[i] = src16[i] << 6, a uint16_t store) over all 65,536 words: (uint16_t)(v << 6), so a word of
+    1024 + k is the word k — the oracle's restatement always, the reference's own function where oracle/_ref/libref_hostmath.so holds it (the
+    tests of tests/test_sample_bits*.py rest on it)."""
+    import sys
+    words = np.arange(65536, dtype=np.uint16)
+    want = (words.astype(np.uint32) << 6).astype(np.uint16)
+    assert np.array_equal(want[1024:2048], want[:1024]) and want[1023] == 0xffc0
+    L = oracle.lib()
+    L.orc_copy_plane_10to16.argtypes = [C.c_uint, C.c_void_p, C.c_uint, C.c_void_p, C.c_int]
+    fns = [L.orc_copy_plane_10to16]
+    sys.path.insert(0, os.path.join(os.path.dirname(HERE), "oracle", "ref_hlsl"))
+    import ref_hostmath
+    R = ref_hostmath.lib()
+    if R is not None and hasattr(R, "ref_copy_plane_10to16"):
+        fns.append(R.ref_copy_plane_10to16)
+    for fn in fns:
+        dst = np.zeros(65536, dtype=np.uint16)
+        fn(64, dst.ctypes.data, 2048, words.ctypes.data, 2048)          # 64 lines of 1,024 words
+        assert np.array_equal(dst, want)
+
+
 def test_hostmath_fixture_is_what_the_reference_code_returns_live():
     """Where oracle/_ref/libref_hostmath.so exists (or can be built from the mounted reference): the recorded fixture is regenerated
     in memory and must be identical — so the pins above are the reference code's, not a stale file."""

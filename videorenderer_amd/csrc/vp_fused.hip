@@ -508,6 +508,8 @@ void FillFusedArgs(const FusedParams &P, FusedArgs &a, int resize_follows)
         a.xdy = maxc / py; a.xry = (1.0f / maxc) * py;            // exact scalings by a power of two
         a.xdc = maxc / pc; a.xrc = (1.0f / maxc) * pc;
     }
+    // ... and what the uint16_t store of (code << shift) drops: the words' bits at and above 16 - shift (three-plane and gray 16-bit samples)
+    a.raw_mask = (c.fmt.bytes == 2 && !c.fmt.bits10 && c.fmt.planes != 2 && c.fmt.shift) ? (0xffffu >> c.fmt.shift) * 0x10001u : 0xffffffffu;
     a.dovi = c.dovi; a.eotf_lut = P.eotf_lut; a.sy = sy; a.sc = sc;
     a.dovi_cm = dv ? P.dovi_cm : nullptr; a.dovi_per_frame = a.dovi_cm ? 1 : 0;
     ChromaCatmullWeights(c.chroma_loc, a.crx, a.cry);

@@ -64,6 +64,10 @@ struct FusedArgs {
     int exact_cv;
     float xm[9], xc[3];
     float xdy, xry, xdc, xrc;
+    // CopyPlane10to16 (Helper.cpp:789-803) stores src16[i] << 6 into a uint16_t: bits 10..15 of a word of the LSB-aligned 10-bit planes
+    // (YUV420P10 / 422P10 / 444P10, GBRP10, Y10) fall off the top, and the scale folded into m / xd above covers the ten bits that stay.
+    // raw_mask = 0xffff >> shift in both halves of a dword (0x03ff03ff), all ones for every other format: raw_codes() below.
+    uint32_t raw_mask;
 };
 
 namespace {
@@ -277,6 +281,18 @@ __device__ __forceinline__ void make_raw_addr(const FusedArgs &P, int Xg, RawAdd
     for (int i = 0; i < 3; i++) ra.coff[i] = (uint32_t)(cb * clampi(c0 - 1 + i, 0, P.cw - 1));
 }
 
+// a dword of raw codes (two luma words, or U | V << 16) of the planar loaders, cut to the bits the reference's upload keeps
+// (FusedArgs::raw_mask): one AND per loaded dword; the bi-planar and 8-bit loaders carry no shift and are left as they were.
+// SRC_GENERIC pays the AND with an all-ones mask for everything else it serves behind the planar branch (8-bit planar behind a tail,
+// 16-bit planar, gray, MPEG-1 sited bi-planar): what that costs on those routes, and what the mask costs on the 10-bit planar ones,
+// has not been measured.
+template <int SRC>
+__device__ __forceinline__ uint32_t raw_codes(const FusedArgs &P, uint32_t d)
+{
+    if constexpr (SRC == SRC_PLANAR16 || SRC == SRC_GENERIC) return d & P.raw_mask;
+    else return d;
+}
+
 // chroma texel as U | V << 16 (raw codes); pu/pv = row bases
 template <int SRC>
 __device__ __forceinline__ uint32_t ld_uv(const FusedArgs &P, gcptr pu, gcptr pv, uint32_t off)
@@ -368,8 +384,8 @@ __device__ __forceinline__ void load_raw(const FusedArgs &P, gcptr py, const Raw
         }
         return;
     }
-    r.y[0] = src_wide<SRC>(P) ? ld_u32(ry0 + opaque(ra.yoff)) : ld_u16(ry0 + opaque(ra.yoff));
-    r.y[1] = src_wide<SRC>(P) ? ld_u32(ry1 + opaque(ra.yoff)) : ld_u16(ry1 + opaque(ra.yoff));
+    r.y[0] = raw_codes<SRC>(P, src_wide<SRC>(P) ? ld_u32(ry0 + opaque(ra.yoff)) : ld_u16(ry0 + opaque(ra.yoff)));
+    r.y[1] = raw_codes<SRC>(P, src_wide<SRC>(P) ? ld_u32(ry1 + opaque(ra.yoff)) : ld_u16(ry1 + opaque(ra.yoff)));
     if (SRC == SRC_GENERIC && P.gray) {            // float4 color = tex.Sample of an R8 / R16 texture (Shaders.cpp:184): no chroma
 #pragma unroll
         for (int i = 0; i < 3; i++) r.c[0][i] = r.c[1][i] = 0;
@@ -381,8 +397,8 @@ __device__ __forceinline__ void load_raw(const FusedArgs &P, gcptr py, const Raw
 #pragma unroll
     for (int i = 0; i < 3; i++) {
         if (i == 0 && !src_center<SRC>(P)) { r.c[0][0] = r.c[1][0] = 0; continue; }
-        r.c[0][i] = ld_uv<SRC>(P, pu + oA, pv + oA, opaque(ra.coff[i]));
-        r.c[1][i] = ld_uv<SRC>(P, pu + oB, pv + oB, opaque(ra.coff[i]));
+        r.c[0][i] = raw_codes<SRC>(P, ld_uv<SRC>(P, pu + oA, pv + oA, opaque(ra.coff[i])));
+        r.c[1][i] = raw_codes<SRC>(P, ld_uv<SRC>(P, pu + oB, pv + oB, opaque(ra.coff[i])));
     }
 }
 
@@ -998,15 +1014,15 @@ __device__ __forceinline__ void load_raw_cr(const FusedArgs &P, gcptr py, const 
 {
     const int sy0 = P.rect_t + y0, sy1 = P.rect_t + y1;
     const gcptr ry0 = py + (uint32_t)sy0 * (uint32_t)P.pitch_y, ry1 = py + (uint32_t)sy1 * (uint32_t)P.pitch_y;
-    r.y[0] = src_wide<SRC>(P) ? ld_u32(ry0 + opaque(ra.yoff)) : ld_u16(ry0 + opaque(ra.yoff));
-    r.y[1] = src_wide<SRC>(P) ? ld_u32(ry1 + opaque(ra.yoff)) : ld_u16(ry1 + opaque(ra.yoff));
+    r.y[0] = raw_codes<SRC>(P, src_wide<SRC>(P) ? ld_u32(ry0 + opaque(ra.yoff)) : ld_u16(ry0 + opaque(ra.yoff)));
+    r.y[1] = raw_codes<SRC>(P, src_wide<SRC>(P) ? ld_u32(ry1 + opaque(ra.yoff)) : ld_u16(ry1 + opaque(ra.yoff)));
     const int base = (sy0 >> 1) - 1;
     const gcptr pu = py + P.off_u, pv = src_biplanar<SRC>(P) ? pu : py + P.off_v;
 #pragma unroll
     for (int j = 0; j < 5; j++) {
         const uint32_t o = (uint32_t)clampi(base + j, 0, P.ch - 1) * (uint32_t)P.pitch_c;
 #pragma unroll
-        for (int i = 0; i < 4; i++) r.c[j][i] = ld_uv<SRC>(P, pu + o, pv + o, opaque(ra.coff[i]));
+        for (int i = 0; i < 4; i++) r.c[j][i] = raw_codes<SRC>(P, ld_uv<SRC>(P, pu + o, pv + o, opaque(ra.coff[i])));
     }
 }
 // exact form (FusedArgs::exact_cv, see convert_block_exact): code_Bicubic_UV (Shaders.cpp:74-79) on 0..1 texels, the four products of a row

@@ -88,11 +88,11 @@ __device__ __forceinline__ void raw_unseen_arrived(int t)
                  "3:" : : "s"(t), "n"(L + 8), "n"(L + 4), "n"(L) : "memory", "scc");
     __builtin_amdgcn_sched_barrier(0);
 }
-// what load_raw does with the loaded codes, behind the wait
+// what load_raw does with the loaded codes, behind the wait (raw_codes: the three-plane 16-bit loader alone cuts its dwords to P.raw_mask)
 template <int SRC>
-__device__ __forceinline__ void raw_unseen_finish(const RawUnseen<raw_unseen_loads<SRC>()> &u, Raw &r)
+__device__ __forceinline__ void raw_unseen_finish(const FusedArgs &P, const RawUnseen<raw_unseen_loads<SRC>()> &u, Raw &r)
 {
-    r.y[0] = u.v[0]; r.y[1] = u.v[1];
+    r.y[0] = raw_codes<SRC>(P, u.v[0]); r.y[1] = raw_codes<SRC>(P, u.v[1]);
     r.c[0][0] = r.c[1][0] = 0;
 #pragma unroll
     for (int i = 0; i < 2; i++)
@@ -101,7 +101,7 @@ __device__ __forceinline__ void raw_unseen_finish(const RawUnseen<raw_unseen_loa
             const uint32_t d = u.v[2 + 2 * i + rr];
             if constexpr (SRC == SRC_P01X) r.c[rr][1 + i] = d;
             else if constexpr (SRC == SRC_NV12) r.c[rr][1 + i] = (d & 0xffu) | ((d >> 8) << 16);
-            else r.c[rr][1 + i] = d | (u.v[6 + 2 * i + rr] << 16);
+            else r.c[rr][1 + i] = raw_codes<SRC>(P, d | (u.v[6 + 2 * i + rr] << 16));
         }
 }
 

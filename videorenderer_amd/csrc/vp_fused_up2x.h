@@ -180,7 +180,7 @@ __device__ __forceinline__ void fused_up2x_body(const FusedArgs &P, const FusedF
         f2 rc[2][3];
         if constexpr (UNSEEN) {
             raw_unseen_arrived<NL>(tw);
-            raw_unseen_finish<SRC>(pend2[b], raw2[b]);
+            raw_unseen_finish<SRC>(P, pend2[b], raw2[b]);
         }
         convert_block<TAIL, SRC, DV_NONE, XC, XC == XC_ALWAYS ? OUT_CODE_F : OUT_NORM>(P, MM, GG, CC, raw2[b], P.rect_t + clampi(ar, 0, H - 1), P.rect_t + clampi(ar + 1, 0, H - 1), T, rc);
         prefetch(ar + 4, b);
