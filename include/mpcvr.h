@@ -253,6 +253,57 @@ int32_t mpcvr_correction_pass(int32_t kind, const void *src, int32_t src_pitch, 
  * row-major) and convert_matrix_2020_to_709 of convert/colorspace_gamut_conversion.hlsl (3x3) */
 int32_t mpcvr_plan_correction_matrices(float fix_bt2020_16[16], float fix_ycgco_16[16], float gamut9[9]);
 
+/* EXTENSION — rendered frames as NV12 / P010 for a video encoder or a 4:2:0 pipeline.  There is no reference line to cite: the reference
+ * ends in a swap chain and has no RGB -> YCbCr path at all.  The pass is defined here, in integers, and anchored to this library's own
+ * colour code: the sample it writes is the one mpcvr_set_input(NV12 | P010, extfmt) converts back to the same picture (to within the
+ * quantisation of the codes; tests/test_encode.py measures it through the oracle).  tests/encode_model.py is the bit-exact model.
+ *   Input: a DEVICE surface of w x h 32-bit texels, src_fmt = MPCVR_OUT_BGRA8 or MPCVR_OUT_RGB10A2; the channel codes R, G, B are integers
+ *     in [0, maxin], maxin = 255 or 1023; the A / X bits are ignored.  w and h even, 2 .. 32768.
+ *   Output: out_cformat = MPCVR_CF_NV12 (depth d = 8, one byte per component) or MPCVR_CF_P010 (d = 10, the code stored as code << 6 in 16
+ *     bits, low six bits zero — this library's P010 reader takes all 16 bits): a Y plane of h rows and an interleaved (U, V) plane of h / 2
+ *     rows, each with its own pointer and pitch.
+ *   Colour description: extfmt is a DXVA2_ExtendedFormat value, defaulted by SpecifyExtendedFormat exactly as mpcvr_set_input defaults
+ *     it for a w x h frame of out_cformat (mpcvr_plan_encode has no size: it defaults the matrix as for a frame of at most 1024 x 576,
+ *     BT.601 — name the matrix to plan what a larger surface gets); its matrix, nominal-range and chroma-siting fields mean what they mean
+ *     there.  A description that plans as RGB (value == 0 after the defaults) is MPCVR_E_INVALIDARG.
+ *   Coefficients: M, c (3x3, 3) = what mpcvr_plan_color_matrix returns for (out_cformat, extfmt) with a neutral ProcAmp; T = 255 for NV12,
+ *     65535 / 64 for P010.  On the host, in double, N = inverse(M) by the adjugate;
+ *       coef[i][j] = rint(N[i][j] * T / maxin * 2^S),   off[i] = rint(-(N c)[i] * T * 2^S),   S = 16.
+ *     Everything on the device is 32-bit integer arithmetic, shifts are arithmetic.
+ *   Luma, one per pixel:   Y = clamp((coef[0] . (R, G, B) + off[0] + 2^(S-1)) >> S, 0, 2^d - 1).
+ *   Chroma, one (U, V) pair per 2x2 block (2i, 2j): weighted sums SR, SG, SB of the codes by siting, taps beyond the surface replicating the
+ *     edge texel —
+ *       siting 0, centre (MPEG-1):        the four texels of the block, W = 4;
+ *       siting 1, left (MPEG-2):          horizontal [1 2 1] centred on column 2i, over rows 2j and 2j + 1, W = 8;
+ *       siting 2, top-left (co-sited):    [1 2 1] x [1 2 1] centred on (2i, 2j), W = 16;
+ *     C = clamp((coef[k] . (SR, SG, SB) + W * off[k] + (W << (S-1))) >> (S + log2 W), 0, 2^d - 1), k = 1 (U), 2 (V).
+ *     The chroma field of extfmt selects the siting as the convert path reads it for 4:2:0 input (csrc/hip_video_processor.cpp,
+ *     P->chroma_loc, Shaders.cpp:121-137): 7 -> top-left, 1 -> centre, anything else -> left.
+ *   Range of the arithmetic: the largest accumulator is 1.07e9 (P010 out, top-left siting, full range), under 2^31 - 1 for every
+ *     matrix x range x format pair (tests/test_encode.py computes the bound from the planned integers), so S = 16 holds for all of them.
+ *   No dithering: an RGB10A2 surface written as NV12 is rounded. */
+/* the integers above, usable without a GPU.  coef9: rows Y, U, V, columns R, G, B.  Any out pointer may be NULL.  MPCVR_E_INVALIDARG for
+ * an out_cformat that is neither NV12 nor P010 (RGB and gray formats included), another src_fmt, or an RGB description. */
+int32_t mpcvr_plan_encode(int32_t out_cformat, int32_t src_fmt, uint32_t extfmt, int32_t coef9[9], int32_t off3[3], int32_t *shift,
+                          int32_t *siting, uint32_t *extfmt_out);
+/* One standalone pass over one device surface, like mpcvr_correction_pass; stream = a hipStream_t or NULL.  One kernel launch
+ * (k_encode420, csrc/vp_encode.hip).  src, y_plane, uv_plane and the three pitches must be multiples of 4 (the render-target rule of
+ * mpcvr_process; 8-byte stores and 16-byte loads are taken where pointers and pitches allow them), src_pitch >= 4 w, y_pitch and uv_pitch
+ * >= one row of components (w bytes for NV12, 2 w for P010).  No byte outside the planes' pixels is written: not the pitch padding, nothing
+ * in front of or behind a plane.  Refusals, with nothing launched: a NULL pointer MPCVR_E_POINTER; MPCVR_E_INVALIDARG for odd or
+ * out-of-range w / h, the formats and descriptions mpcvr_plan_encode refuses, a pointer or pitch that breaks the rules above, and planes
+ * that overlap each other or the source (a plane counts as the bytes from its first pixel to the last pixel of its last row). */
+int32_t mpcvr_encode_pass(const void *src, int32_t src_pitch, int32_t src_fmt, int32_t w, int32_t h, int32_t out_cformat, uint32_t extfmt,
+                          void *y_plane, int32_t y_pitch, void *uv_plane, int32_t uv_pitch, void *stream);
+/* mpcvr_render, then the pass over the whole window: Process into the context-owned back buffer with the letterbox cleared to black, the
+ * encode queued behind it in stream order (a frame rendered this way runs on the context stream, not on a frame lane; the pixels are the
+ * same).  The planes are complete after mpcvr_synchronize; mpcvr_get_backbuffer and mpcvr_get_displayed_image afterwards see the RGB frame
+ * a plain mpcvr_render leaves.  The source format is the context's output_format.  An odd window width or height, and everything
+ * mpcvr_encode_pass refuses about the planes, is answered (MPCVR_E_INVALIDARG / MPCVR_E_POINTER) before anything is drawn.  S_FALSE, with
+ * nothing drawn or written, when there is no sample (as mpcvr_render). */
+int32_t mpcvr_render_yuv(mpcvr_ctx *ctx, int32_t field, int32_t out_cformat, uint32_t extfmt, void *y_plane, int32_t y_pitch,
+                         void *uv_plane, int32_t uv_pitch);
+
 /* Configure — DX11VideoProcessor.cpp:3800-4050: diff each field, rebuild only what changed. */
 int32_t mpcvr_configure(mpcvr_ctx *ctx, const mpcvr_settings *settings);
 

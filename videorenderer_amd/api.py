@@ -164,6 +164,7 @@ EXPORTS = [
     "mpcvr_plan_upscale_weights", "mpcvr_plan_axis_taps", "mpcvr_plan_describe", "mpcvr_plan_final_pass_multiplier",
     "mpcvr_plan_strip", "mpcvr_plan_pq_eotf_table", "mpcvr_plan_pq_eotf_lut", "mpcvr_bandwidth_probe", "mpcvr_plan_period", "mpcvr_plan_hdr10_params", "mpcvr_plan_draw_tables",
     "mpcvr_eval_transcendental", "mpcvr_eval_transcendental_host", "mpcvr_bandwidth_probe_up2x", "mpcvr_eval_dovi_tail",
+    "mpcvr_plan_encode", "mpcvr_encode_pass", "mpcvr_render_yuv",
 ]
 
 _lib = None
@@ -259,6 +260,9 @@ def load_library():
         "mpcvr_eval_transcendental_host": [i32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t],
         "mpcvr_plan_describe": [P(Settings), i32, i32, i32, P(Rect), i32, i32, C.c_char_p, C.c_size_t],
         "mpcvr_plan_draw_tables": [P(Settings), i32, i32, i32, P(Rect), P(Rect), i32, i32, i32, i32, C.c_void_p, P(C.c_size_t)],
+        "mpcvr_plan_encode": [i32, i32, u32, P(i32), P(i32), P(i32), P(i32), P(u32)],
+        "mpcvr_encode_pass": [vp, i32, i32, i32, i32, i32, u32, vp, i32, vp, i32, vp],
+        "mpcvr_render_yuv": [vp, i32, i32, u32, vp, i32, vp, i32],
     }
     for name, args in sig.items():
         if lib_path != LIB_PATH and not hasattr(L, name):
@@ -354,6 +358,28 @@ def correction_pass(kind, src, src_pitch, src_fmt, dst, dst_pitch, dst_fmt, w, h
                                               C.c_void_p(stream) if stream else None)
     if hr:
         raise MpcvrError(hr, "mpcvr_correction_pass")
+
+
+def plan_encode(out_cformat, src_fmt, extfmt=0):
+    """(extension) The integers of the RGB -> NV12 / P010 pass (include/mpcvr.h: mpcvr_plan_encode): dict(coef = 3x3 int32 with rows
+    Y, U, V and columns R, G, B, off = 3 int32, shift, siting (0 centre, 1 left, 2 top-left), extfmt = the description after its defaults).  No GPU needed."""
+    import numpy as np
+    coef, off = (C.c_int32 * 9)(), (C.c_int32 * 3)()
+    shift, siting, ex = C.c_int32(), C.c_int32(), C.c_uint32()
+    hr = load_library().mpcvr_plan_encode(int(out_cformat), int(src_fmt), int(extfmt), coef, off, C.byref(shift), C.byref(siting), C.byref(ex))
+    if hr:
+        raise MpcvrError(hr, "mpcvr_plan_encode")
+    return dict(coef=np.array(coef, dtype=np.int32).reshape(3, 3), off=np.array(off, dtype=np.int32), shift=shift.value,
+                siting=siting.value, extfmt=ex.value)
+
+
+def encode_pass(src, src_pitch, src_fmt, w, h, out_cformat, extfmt, y_plane, y_pitch, uv_plane, uv_pitch, stream=None):
+    """(extension) One device surface of 32-bit RGB texels (src_fmt: 0 = BGRA8, 1 = RGB10A2) written as NV12 / P010 planes."""
+    hr = load_library().mpcvr_encode_pass(C.c_void_p(_ptr(src)), int(src_pitch), int(src_fmt), int(w), int(h), int(out_cformat), int(extfmt),
+                                          C.c_void_p(_ptr(y_plane)), int(y_pitch), C.c_void_p(_ptr(uv_plane)), int(uv_pitch),
+                                          C.c_void_p(stream) if stream else None)
+    if hr:
+        raise MpcvrError(hr, "mpcvr_encode_pass")
 
 
 def plan_upscale_weights(method, t):
@@ -549,6 +575,7 @@ class VideoProcessor:
         return self._check(self._L.mpcvr_set_video_rect(self._ctx, C.byref(Rect(*rect))))
 
     def SetWindowRect(self, rect):
+        self._window = tuple(int(v) for v in rect)
         return self._check(self._L.mpcvr_set_window_rect(self._ctx, C.byref(Rect(*rect))))
 
     def SetRotation(self, value):
@@ -613,6 +640,27 @@ class VideoProcessor:
 
     def Render(self, field=1):
         return self._check(self._L.mpcvr_render(self._ctx, field))
+
+    def RenderYuv(self, out_cformat, extfmt=0, field=1):
+        """(extension) Render, then the back buffer as NV12 (uint8) or P010 (int16: the code in the top ten bits) planes: returns the
+        (y, uv) device tensors of (h, w) and (h / 2, w) components (views of pitch-padded rows where w is no multiple of 4), complete after Synchronize."""
+        import torch
+        if getattr(self, "_window", None) is not None:
+            ww, wh = self._window[2] - self._window[0], self._window[3] - self._window[1]
+        else:                                      # (the window was not set through this object: the last Render knows it)
+            ww, wh = self.GetBackBuffer()[2:]
+        ten = out_cformat == CF_P010
+        dt = torch.int16 if ten else torch.uint8
+        cols = ww if ten else (ww + 3) & ~3        # a plane's pitch is a multiple of 4 bytes: NV12 rows of w = 2 (mod 4) are padded
+        with torch.cuda.device(self.device):
+            y = torch.empty((wh, cols), dtype=dt, device="cuda")
+            uv = torch.empty((wh // 2, cols), dtype=dt, device="cuda")
+        row = cols * (2 if ten else 1)
+        self._check(self._L.mpcvr_render_yuv(self._ctx, field, int(out_cformat), int(extfmt), C.c_void_p(y.data_ptr()), row,
+                                             C.c_void_p(uv.data_ptr()), row))
+        if cols != ww:
+            y, uv = y[:, :ww], uv[:, :ww]
+        return y, uv
 
     def GetBackBuffer(self):
         p, pitch, w, h = C.c_void_p(), C.c_int32(), C.c_int32(), C.c_int32()

@@ -44,6 +44,7 @@ SOURCES = [
     ("vp_jinc.hip", []),
     ("vp_fused_jinc.hip", []),
     ("vp_errdiff.hip", []),
+    ("vp_encode.hip", []),
     ("vp_probe.hip", []),
 ]
 

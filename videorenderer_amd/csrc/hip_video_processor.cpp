@@ -1669,7 +1669,7 @@ std::string CHipVideoProcessor::GetLastBatchInfo() const
 }
 
 // Render minus Present — DX11VideoProcessor.cpp:2599-2813
-HRESULT CHipVideoProcessor::Render(int /*field*/)
+HRESULT CHipVideoProcessor::RenderBackBuffer(bool onContextStream)
 {
     if (!m_bInit || !m_srcParams) return Fail(MPCVR_E_NOT_VALID_STATE, "InitMediaType has not been called");
     if (!m_curSample) return MPCVR_S_FALSE;          // nothing to draw (cf. :2603-2606)
@@ -1681,9 +1681,69 @@ HRESULT CHipVideoProcessor::Render(int /*field*/)
     if ((hr = CheckHip(m_BackBuffer.CheckCreate(bytes), "back buffer"))) return hr;
     // ClearRenderTargetView to black (:2622) — only the letterbox area survives Process
     const size_t clearBytes = (fresh || m_videoRect != CRect(0, 0, w, h)) ? bytes : 0;     // queued on the stream the frame runs on
-    hr = ProcessFrame(m_BackBuffer.ptr, w * 4, nullptr, nullptr, clearBytes, false);
+    hr = ProcessFrame(m_BackBuffer.ptr, w * 4, nullptr, nullptr, clearBytes, onContextStream);
     if (hr >= 0) { m_backW = w; m_backH = h; m_backFmt = m_cfg.output_format; }        // what GetDisplayedImage will find there
     return hr;
+}
+
+// ------------------------------------------------------------------------------------------------
+// EXTENSION — the frame as NV12 / P010 for an encoder (include/mpcvr.h: mpcvr_encode_pass, mpcvr_render_yuv; kernel: vp_encode.hip).
+// No reference line: the reference has no RGB -> YUV path.
+// ------------------------------------------------------------------------------------------------
+HRESULT EncodeSurface(const void *src, int srcPitch, int srcFmt, int w, int h, int outCformat, uint32_t extfmt, void *yPlane, int yPitch,
+                      void *uvPlane, int uvPitch, hipStream_t stream, bool checkOnly, const char **why)
+{
+    const char *dummy;
+    if (!why) why = &dummy;
+    if ((!src && !checkOnly) || !yPlane || !uvPlane) { *why = "null surface or plane"; return MPCVR_E_POINTER; }      // (checkOnly: a source still to be allocated)
+    if (w < 2 || h < 2 || ((w | h) & 1) || w > 32768 || h > 32768) { *why = "width and height must be even, 2 .. 32768"; return MPCVR_E_INVALIDARG; }
+    EncodePlan plan;
+    if (!PlanEncode(outCformat, srcFmt, extfmt, w, h, &plan)) { *why = "output NV12 or P010 with a YCbCr description, source BGRA8 or RGB10A2"; return MPCVR_E_INVALIDARG; }
+    const int rowBytes = plan.out10 ? 2 * w : w;        // of the Y plane and of the UV plane alike (w / 2 pairs)
+    if (srcPitch < 4 * w || yPitch < rowBytes || uvPitch < rowBytes) { *why = "pitch smaller than a row"; return MPCVR_E_INVALIDARG; }
+    if (((uintptr_t)src | (uintptr_t)yPlane | (uintptr_t)uvPlane | (uintptr_t)srcPitch | (uintptr_t)yPitch | (uintptr_t)uvPitch) & 3) {
+        *why = "surface, planes and pitches must be multiples of 4"; return MPCVR_E_INVALIDARG;
+    }
+    // a plane counts as the bytes from its first pixel to the last pixel of its last row
+    const uintptr_t s0 = (uintptr_t)src, s1 = s0 + (size_t)(h - 1) * srcPitch + (size_t)4 * w;
+    const uintptr_t y0 = (uintptr_t)yPlane, y1 = y0 + (size_t)(h - 1) * yPitch + rowBytes;
+    const uintptr_t c0 = (uintptr_t)uvPlane, c1 = c0 + (size_t)(h / 2 - 1) * uvPitch + rowBytes;
+    if ((y0 < c1 && c0 < y1) || (src && ((y0 < s1 && s0 < y1) || (c0 < s1 && s0 < c1)))) { *why = "the planes overlap each other or the source"; return MPCVR_E_INVALIDARG; }
+    if (checkOnly) return MPCVR_S_OK;
+    EncodeParams p{};
+    p.src = (const uint8_t *)src; p.src_pitch = srcPitch;
+    p.y = (uint8_t *)yPlane; p.y_pitch = yPitch;
+    p.uv = (uint8_t *)uvPlane; p.uv_pitch = uvPitch;
+    p.w = w; p.h = h;
+    std::memcpy(p.coef, plan.coef, sizeof(p.coef));
+    std::memcpy(p.off, plan.off, sizeof(p.off));
+    p.src16 = ((s0 | (uintptr_t)srcPitch) & 15) == 0;
+    p.dst8 = ((y0 | c0 | (uintptr_t)yPitch | (uintptr_t)uvPitch) & 7) == 0;
+    if (LaunchEncode420(p, plan.in10, plan.out10, plan.siting, stream) != hipSuccess) { *why = "k_encode420 launch failed"; return MPCVR_E_FAIL; }
+    return MPCVR_S_OK;
+}
+
+// Render, then the pass over the whole window behind it.  The frame stays off the lanes (like the snapshot's): the pass reads the back
+// buffer, and the lanes' bookkeeping orders WRITES into the same memory — a following Render on another lane would not wait for a reader.
+// On the context stream everything queued later, lanes included (NoteStreamWork), runs behind the pass.
+HRESULT CHipVideoProcessor::RenderYuv(int /*field*/, int outCformat, uint32_t extfmt, void *yPlane, int yPitch, void *uvPlane, int uvPitch)
+{
+    if (!m_bInit || !m_srcParams) return Fail(MPCVR_E_NOT_VALID_STATE, "InitMediaType has not been called");
+    (void)hipSetDevice(m_device);
+    const int w = m_windowRect.Width(), h = m_windowRect.Height();
+    if (w < 2 || h < 2 || ((w | h) & 1)) return Fail(MPCVR_E_INVALIDARG, "a 4:2:0 frame needs an even window width and height");
+    if (!m_curSample) return MPCVR_S_FALSE;          // nothing to draw, as Render
+    // everything about the planes is answered before anything is drawn (a back buffer Render has yet to allocate cannot overlap them)
+    const bool have = m_BackBuffer.ptr && m_BackBuffer.size >= (size_t)w * 4 * h;
+    HRESULT hr;
+    const char *why = "";
+    if ((hr = EncodeSurface(have ? m_BackBuffer.ptr : nullptr, w * 4, m_cfg.output_format, w, h, outCformat, extfmt, yPlane, yPitch, uvPlane, uvPitch, nullptr, true, &why)))
+        return Fail(hr, why);
+    if ((hr = RenderBackBuffer(true)) != MPCVR_S_OK) return hr;
+    hr = EncodeSurface(m_BackBuffer.ptr, w * 4, m_cfg.output_format, w, h, outCformat, extfmt, yPlane, yPitch, uvPlane, uvPitch, m_stream, false, &why);
+    m_launches++;
+    m_lanes.NoteStreamWork();
+    return hr ? Fail(hr, why) : MPCVR_S_OK;
 }
 
 HRESULT CHipVideoProcessor::GetBackBuffer(void **ptr, int *pitch, int *w, int *h)

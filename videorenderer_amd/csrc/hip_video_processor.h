@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/mpcvr.h"
+#include "vp_encode.h"
 #include "vp_lanes.h"
 #include "vp_launch.h"
 #include "vp_params.h"
@@ -39,6 +40,12 @@ struct DevBuffer {
     void Release();
 };
 
+// EXTENSION (mpcvr_encode_pass, include/mpcvr.h): checks every argument, then — unless checkOnly — launches k_encode420 on `stream`.
+// MPCVR_E_POINTER / MPCVR_E_INVALIDARG with nothing launched; *why (optional) names the refusal.  checkOnly takes src = nullptr for a source
+// that is still to be allocated (it cannot overlap the planes)
+HRESULT EncodeSurface(const void *src, int srcPitch, int srcFmt, int w, int h, int outCformat, uint32_t extfmt, void *yPlane, int yPitch,
+                      void *uvPlane, int uvPitch, hipStream_t stream, bool checkOnly, const char **why = nullptr);
+
 class CHipVideoProcessor {
 public:
     CHipVideoProcessor();
@@ -65,7 +72,9 @@ public:
 
     HRESULT CopySample(const void *data, int pitch, int memKind);             // :2202 / MemCopyToTexSrcVideo :1213
     HRESULT Process(void *rt, int rtPitch, const CRect *srcRect, const CRect *dstRect, bool /*second*/) { return ProcessFrame(rt, rtPitch, srcRect, dstRect, 0, false); }     // :3285
-    HRESULT Render(int field);                                                // :2599 minus Present
+    HRESULT Render(int field) { return RenderBackBuffer(false); }             // :2599 minus Present
+    // EXTENSION (mpcvr_render_yuv): Render, then the back buffer written as NV12 / P010 (vp_encode.h) behind it in stream order
+    HRESULT RenderYuv(int field, int outCformat, uint32_t extfmt, void *yPlane, int yPitch, void *uvPlane, int uvPitch);
     HRESULT GetBackBuffer(void **ptr, int *pitch, int *w, int *h);
     HRESULT GetCurentImage(void *hostBGRA, size_t *size);                     // :3493
     HRESULT GetDisplayedImage(void *hostPixels, size_t *size, bool deepColor, int *width, int *height, int *bits);     // :3610
@@ -94,6 +103,7 @@ public:
 
 private:
     HRESULT Fail(HRESULT hr, const std::string &msg);
+    HRESULT RenderBackBuffer(bool onContextStream);
     HRESULT CheckHip(hipError_t e, const char *what);
 
     // mirrors of the reference's private helpers

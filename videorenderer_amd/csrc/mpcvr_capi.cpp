@@ -133,6 +133,13 @@ int32_t mpcvr_process_frames(mpcvr_ctx *ctx, int32_t n, const void *const *sampl
 
 int32_t mpcvr_render(mpcvr_ctx *ctx, int32_t field) { CTX_OR_FAIL(); return ctx->vp.Render(field); }
 
+int32_t mpcvr_render_yuv(mpcvr_ctx *ctx, int32_t field, int32_t out_cformat, uint32_t extfmt, void *y_plane, int32_t y_pitch, void *uv_plane, int32_t uv_pitch)
+{
+    CTX_OR_FAIL();
+    if (!y_plane || !uv_plane) return MPCVR_E_POINTER;
+    return ctx->vp.RenderYuv(field, out_cformat, extfmt, y_plane, y_pitch, uv_plane, uv_pitch);
+}
+
 int32_t mpcvr_get_backbuffer(mpcvr_ctx *ctx, void **dev_ptr, int32_t *pitch, int32_t *width, int32_t *height)
 {
     CTX_OR_FAIL();
@@ -282,6 +289,26 @@ int32_t mpcvr_correction_pass(int32_t kind, const void *src, int32_t src_pitch, 
     const hipError_t e = mpcvr::LaunchCorrection(kind, in, out, kind == MPCVR_CORR_FIX_YCGCO ? fixycgco : fix2020, gamut,
                                                  10000.0f / (float)sdr_nits, (hipStream_t)stream);
     return e == hipSuccess ? MPCVR_S_OK : MPCVR_E_FAIL;
+}
+
+// EXTENSION: RGB -> NV12 / P010 for an encoder (include/mpcvr.h; PlanEncode vp_plan.cpp, k_encode420 vp_encode.hip)
+int32_t mpcvr_plan_encode(int32_t out_cformat, int32_t src_fmt, uint32_t extfmt, int32_t coef9[9], int32_t off3[3], int32_t *shift,
+                          int32_t *siting, uint32_t *extfmt_out)
+{
+    mpcvr::EncodePlan plan;
+    if (!mpcvr::PlanEncode(out_cformat, src_fmt, extfmt, 0, 0, &plan)) return MPCVR_E_INVALIDARG;      // (no size: the matrix default of a small frame)
+    if (coef9) std::memcpy(coef9, plan.coef, sizeof(plan.coef));
+    if (off3) std::memcpy(off3, plan.off, sizeof(plan.off));
+    if (shift) *shift = plan.shift;
+    if (siting) *siting = plan.siting;
+    if (extfmt_out) *extfmt_out = plan.extfmt;
+    return MPCVR_S_OK;
+}
+
+int32_t mpcvr_encode_pass(const void *src, int32_t src_pitch, int32_t src_fmt, int32_t w, int32_t h, int32_t out_cformat, uint32_t extfmt,
+                          void *y_plane, int32_t y_pitch, void *uv_plane, int32_t uv_pitch, void *stream)
+{
+    return mpcvr::EncodeSurface(src, src_pitch, src_fmt, w, h, out_cformat, extfmt, y_plane, y_pitch, uv_plane, uv_pitch, (hipStream_t)stream, false);
 }
 
 int32_t mpcvr_plan_dovi(const mpcvr_dovi_metadata *md, int32_t display_nits, float *cb705, int32_t *has_mmr,

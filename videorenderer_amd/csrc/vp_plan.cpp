@@ -7,6 +7,7 @@
 #include <cstring>
 
 #include "../../include/mpcvr.h"
+#include "vp_encode.h"
 #include "vp_crmath.h"      // the shaders' sin / cos as defined functions (the weights the resize shaders compute per pixel are computed here, once)
 
 namespace mpcvr {
@@ -214,6 +215,56 @@ void ComputeColorMatrix(const ExtFmt &ex, const FmtConvParams &f, const ProcAmp 
     }
     for (int i = 0; i < 3; i++)
         for (int j = 0; j < 3; j++) out[i * 3 + j] = m.v[i][j];
+}
+
+// ------------------------------------------------------------------------------------------------
+// EXTENSION — RGB -> NV12 / P010 (include/mpcvr.h: mpcvr_encode_pass).  No reference line: the reference never goes from RGB to YUV.
+// rgb = M yuv + c is what the convert pass does to a sample of (out_cformat, extfmt), yuv and rgb normalised to [0, 1]; the encoder
+// inverts it: yuv = N (rgb - c), N = inverse(M), with rgb = code_in / maxin and code_out = yuv * T (T = 255: one byte per component;
+// 65535 / 64: the 10-bit code sits in the top of a 16-bit word, of which this library's P010 reader takes all 16 bits).
+// ------------------------------------------------------------------------------------------------
+bool PlanEncode(int out_cformat, int src_fmt, uint32_t extfmt, int w, int h, EncodePlan *plan)
+{
+    if (out_cformat != MPCVR_CF_NV12 && out_cformat != MPCVR_CF_P010) return false;
+    if (src_fmt != MPCVR_OUT_BGRA8 && src_fmt != MPCVR_OUT_RGB10A2) return false;
+    const FmtConvParams *f = GetFmtConvParams(out_cformat);
+    if (!f || f->CSType != CST_YUV) return false;
+    const ExtFmt ex = SpecifyExtendedFormat(ExtFmt{extfmt}, *f, w, h);
+    if (ex.value == 0) return false;                    // set_colorspace would plan RGB (Helper.cpp:953-957): nothing to invert towards
+    float cm[12];
+    ComputeColorMatrix(ex, *f, ProcAmp(), cm);
+    double a[3][3], n[3][3];
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) a[i][j] = (double)cm[i * 3 + j];
+    // the adjugate: n[i][j] = cofactor(j, i)
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) {
+            const int r0 = (j + 1) % 3, r1 = (j + 2) % 3, c0 = (i + 1) % 3, c1 = (i + 2) % 3;
+            n[i][j] = a[r0][c0] * a[r1][c1] - a[r0][c1] * a[r1][c0];
+        }
+    const double det = a[0][0] * n[0][0] + a[0][1] * n[1][0] + a[0][2] * n[2][0];
+    if (!(std::fabs(det) > 1e-12)) return false;
+    plan->in10 = src_fmt == MPCVR_OUT_RGB10A2;
+    plan->out10 = out_cformat == MPCVR_CF_P010;
+    const double maxin = plan->in10 ? 1023.0 : 255.0, T = plan->out10 ? 65535.0 / 64.0 : 255.0;
+    const double one = (double)(1 << kEncodeShift);
+    for (int i = 0; i < 3; i++) {
+        double nc = 0;
+        for (int j = 0; j < 3; j++) {
+            n[i][j] /= det;
+            plan->coef[i * 3 + j] = (int32_t)std::rint(n[i][j] * T / maxin * one);
+            nc += n[i][j] * (double)cm[9 + j];
+        }
+        plan->off[i] = (int32_t)std::rint(-nc * T * one);
+    }
+    plan->shift = kEncodeShift;
+    switch (ex.VideoChromaSubsampling()) {              // the mapping the convert path uses for 4:2:0 input (hip_video_processor.cpp: P->chroma_loc, Shaders.cpp:121-137)
+    case dxva::Chroma_Cosited: plan->siting = ENC_TOPLEFT; break;
+    case dxva::Chroma_MPEG1: plan->siting = ENC_CENTRE; break;
+    default: plan->siting = ENC_LEFT; break;
+    }
+    plan->extfmt = ex.value;
+    return true;
 }
 
 // ------------------------------------------------------------------------------------------------
