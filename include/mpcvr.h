@@ -420,6 +420,42 @@ int32_t mpcvr_process_batch(mpcvr_ctx *ctx, int32_t n, const void *const *srcs, 
 int32_t mpcvr_process_batch_dovi(mpcvr_ctx *ctx, int32_t n, const void *const *srcs, void *const *dsts,
                                  int32_t dst_pitch, const mpcvr_dovi_metadata *rpus);
 
+/* EXTENSION — a batch written as NV12 / P010 (mpcvr_process_batch for a transcoder; the pass itself: mpcvr_encode_pass above).
+ * The planes of frame i hold, byte for byte, what
+ *     mpcvr_process_batch(srcs -> n window-sized RGB targets of the context's output_format, black outside the video rect), then
+ *     mpcvr_encode_pass(target i, output_format, window_w, window_h, out_cformat, extfmt, y_planes[i], y_pitch, uv_planes[i], uv_pitch)
+ * leave — without the host owning the RGB memory, and with ONE k_encode420 launch per chunk of frames (its frame dimension) where the
+ * composition takes n.  The RGB frames live in a context-owned surface laid out by mpcvr_plan_batch_yuv:
+ *     surface_pitch    = (4 window_w + 15) & ~15          (every lane of the pass with four columns takes its 16-byte load)
+ *     frame_stride     = surface_pitch * window_h rounded up to 256
+ *     frames_per_chunk = clamp(budget_bytes / frame_stride, 1, n),      chunks = ceil(n / frames_per_chunk)
+ * budget_bytes = 0 means the default, MPCVR_BATCH_YUV_DEFAULT_BUDGET (4 GiB: what a sweep over 256 MiB, 1 GiB and 4 GiB favours — 32 frames
+ * of 8K in one chunk run 6-7 % ahead of four chunks and 23-24 % ahead of sixteen; profiles/r13/batch_yuv.txt).  mpcvr_plan_batch_yuv needs no GPU; any out pointer may be NULL;
+ * MPCVR_E_INVALIDARG for n <= 0 or a window width / height that is odd or outside 2 .. 32768.
+ * mpcvr_set_batch_yuv_budget: the bytes one such surface may take (0 = the default again; the library's other batched
+ * intermediates stop at 4 GiB, and nothing above that was measured).  A context that owns its stream keeps one surface per batch lane it uses.
+ * Each chunk runs what mpcvr_process_batch runs for its frames (every route, bUseDither = 2 included; a context holding one Dolby Vision
+ * RPU works as there, one RPU per frame is not offered) into the surface, then the pass, on the same stream.  The letterbox is black as in
+ * mpcvr_render_yuv: the surface is cleared when it is allocated and when the window or the video rect changes, not per call.
+ * Order: on a caller's stream (mpcvr_set_stream), with MPCVR_FLAG_NO_FRAME_LANES or MPCVR_NO_BATCH_LANES=1, and for chunks whose route
+ * is no lane route, everything runs in stream order on the context stream.  On a context that owns its stream the chunks whose route
+ * mpcvr_process_batch would put on a lane take turns on the two batch lanes, across the chunks of a call and across calls, each lane with
+ * a surface of its own: the render of one chunk runs beside the pass of the one before.  The planes count as the bytes written (first
+ * pixel to the last pixel of the last row, as for render targets): single frames, RGB batches and further calls that write memory a plane
+ * in flight covers stay behind it in the order they were queued.  The lanes order WRITES, not readers: the planes are complete after
+ * mpcvr_synchronize, and a caller that feeds them back as samples synchronises first.
+ * Refusals, answered before anything is drawn, allocated or written: MPCVR_E_NOT_VALID_STATE before mpcvr_set_input; MPCVR_E_POINTER for
+ * a NULL array or entry; MPCVR_E_INVALIDARG for n <= 0, an odd window width or height, whatever mpcvr_encode_pass refuses about formats,
+ * description, pitches and pointers, and any two planes of the batch (2 n of them) that overlap each other.
+ * mpcvr_get_last_batch_info afterwards: "launches" counts the passes too, and ";yuv_chunks=<k>;yuv_lanes=<lane,lane,...>" follow (the lane
+ * of each chunk, -1 = the context stream; the first 64 chunks). */
+#define MPCVR_BATCH_YUV_DEFAULT_BUDGET ((size_t)4 << 30)
+int32_t mpcvr_plan_batch_yuv(int32_t window_w, int32_t window_h, int32_t n, size_t budget_bytes,
+                             int32_t *surface_pitch, size_t *frame_stride, int32_t *frames_per_chunk, int32_t *chunks);
+int32_t mpcvr_set_batch_yuv_budget(mpcvr_ctx *ctx, size_t bytes);
+int32_t mpcvr_process_batch_yuv(mpcvr_ctx *ctx, int32_t n, const void *const *srcs, int32_t out_cformat, uint32_t extfmt,
+                                void *const *y_planes, int32_t y_pitch, void *const *uv_planes, int32_t uv_pitch);
+
 /* Multi-GPU: the parameter blob (colour matrix, luminance scale, gamut matrix, resize phase weights,
  * dither table) a rank-0 context computes and every other rank adopts after an RCCL broadcast.
  * Two-call size protocol. */
@@ -449,7 +485,8 @@ int32_t mpcvr_get_path_info(mpcvr_ctx *ctx, char *buf, size_t buf_size); /* e.g.
 /* How the last mpcvr_process_batch / mpcvr_process_batch_dovi call ran: "frames=<n>;launches=<kernel launches>;lane=<lane>;waits=<n>;uploads=<frame tables copied to the device in the stream>[;dovi_runs=<frames>:<tables|frames>,...]".
  * A batch on a whole-batch route launches a handful of kernels whatever n is (one per stage and <= 4 GiB chunk of intermediates); a
  * frame-by-frame one at least n.  dovi_runs: the runs mpcvr_process_batch_dovi cut the frames into and whether a run read its RPUs from the
- * per-frame tables or went frame by frame. */
+ * per-frame tables or went frame by frame.  After mpcvr_process_batch_yuv ";yuv_chunks=<k>;yuv_lanes=<lane,lane,...>" follow and the launches
+ * include one pass per chunk; after every other batch call the string is as above. */
 int32_t mpcvr_get_last_batch_info(mpcvr_ctx *ctx, char *buf, size_t buf_size);
 const char *mpcvr_last_error(mpcvr_ctx *ctx);
 const char *mpcvr_version(void);

@@ -165,6 +165,7 @@ EXPORTS = [
     "mpcvr_plan_strip", "mpcvr_plan_pq_eotf_table", "mpcvr_plan_pq_eotf_lut", "mpcvr_bandwidth_probe", "mpcvr_plan_period", "mpcvr_plan_hdr10_params", "mpcvr_plan_draw_tables",
     "mpcvr_eval_transcendental", "mpcvr_eval_transcendental_host", "mpcvr_bandwidth_probe_up2x", "mpcvr_eval_dovi_tail",
     "mpcvr_plan_encode", "mpcvr_encode_pass", "mpcvr_render_yuv",
+    "mpcvr_plan_batch_yuv", "mpcvr_set_batch_yuv_budget", "mpcvr_process_batch_yuv",
 ]
 
 _lib = None
@@ -263,6 +264,9 @@ def load_library():
         "mpcvr_plan_encode": [i32, i32, u32, P(i32), P(i32), P(i32), P(i32), P(u32)],
         "mpcvr_encode_pass": [vp, i32, i32, i32, i32, i32, u32, vp, i32, vp, i32, vp],
         "mpcvr_render_yuv": [vp, i32, i32, u32, vp, i32, vp, i32],
+        "mpcvr_plan_batch_yuv": [i32, i32, i32, C.c_size_t, P(i32), P(C.c_size_t), P(i32), P(i32)],
+        "mpcvr_set_batch_yuv_budget": [vp, C.c_size_t],
+        "mpcvr_process_batch_yuv": [vp, i32, P(vp), i32, u32, P(vp), i32, P(vp), i32],
     }
     for name, args in sig.items():
         if lib_path != LIB_PATH and not hasattr(L, name):
@@ -380,6 +384,16 @@ def encode_pass(src, src_pitch, src_fmt, w, h, out_cformat, extfmt, y_plane, y_p
                                           C.c_void_p(stream) if stream else None)
     if hr:
         raise MpcvrError(hr, "mpcvr_encode_pass")
+
+
+def plan_batch_yuv(window_w, window_h, n, budget_bytes=0):
+    """(extension) The layout integers of mpcvr_process_batch_yuv (include/mpcvr.h: mpcvr_plan_batch_yuv): dict(surface_pitch, frame_stride,
+    frames_per_chunk, chunks) for n frames of a window under a budget of bytes (0: the default).  No GPU needed."""
+    pitch, fpc, chunks, stride = C.c_int32(), C.c_int32(), C.c_int32(), C.c_size_t()
+    hr = load_library().mpcvr_plan_batch_yuv(int(window_w), int(window_h), int(n), int(budget_bytes), C.byref(pitch), C.byref(stride), C.byref(fpc), C.byref(chunks))
+    if hr:
+        raise MpcvrError(hr, "mpcvr_plan_batch_yuv")
+    return dict(surface_pitch=pitch.value, frame_stride=stride.value, frames_per_chunk=fpc.value, chunks=chunks.value)
 
 
 def plan_upscale_weights(method, t):
@@ -692,6 +706,20 @@ class VideoProcessor:
         self._keep = b
         return self._check(self._L.mpcvr_process_batch(self._ctx, b.n, b.sa, b.da, rt_pitch))
 
+    def SetBatchYuvBudget(self, nbytes):
+        """(extension) The bytes one context-owned RGB surface of ProcessBatchYuv may take (0: the default)."""
+        return self._check(self._L.mpcvr_set_batch_yuv_budget(self._ctx, int(nbytes)))
+
+    def ProcessBatchYuv(self, srcs, out_cformat, extfmt, y_planes, y_pitch, uv_planes, uv_pitch):
+        """(extension) ProcessBatch with the frames written as NV12 / P010 planes (mpcvr_process_batch_yuv): y_planes[i] / uv_planes[i] are
+        device tensors or addresses, one pitch each for all frames; complete after Synchronize.  GetLastBatchInfo adds yuv_chunks / yuv_lanes."""
+        n = len(srcs)
+        assert n == len(y_planes) == len(uv_planes) and n > 0
+        arr = C.c_void_p * n
+        keep = (arr(*[_ptr(s) for s in srcs]), arr(*[_ptr(p) for p in y_planes]), arr(*[_ptr(p) for p in uv_planes]), (srcs, y_planes, uv_planes))
+        self._keep = keep
+        return self._check(self._L.mpcvr_process_batch_yuv(self._ctx, n, keep[0], int(out_cformat), int(extfmt), keep[1], int(y_pitch), keep[2], int(uv_pitch)))
+
     def ProcessBatchDovi(self, srcs, dsts, rt_pitch, rpus):
         """ProcessBatch with one Dolby Vision RPU per frame (mpcvr_process_batch_dovi): rpus[i] is a DoviMetadata or the dict
         DoviMetadata.from_dict takes."""
@@ -756,11 +784,14 @@ class VideoProcessor:
         return buf.value.decode()
 
     def GetLastBatchInfo(self):
-        """'frames=<n>;launches=<kernel launches>;lane=<0 | 1: the batch ran on that lane beside its predecessor, -1: on the context stream>;waits=<frames / batches still in flight on other lanes, into memory this batch's targets overlap, that it was ordered behind>[;dovi_runs=...]' of the last ProcessBatch / ProcessBatchDovi call, as a dict."""
+        """'frames=<n>;launches=<kernel launches>;lane=<0 | 1: the batch ran on that lane beside its predecessor, -1: on the context stream>;waits=<frames / batches still in flight on other lanes, into memory this batch's targets overlap, that it was ordered behind>[;dovi_runs=...]' of the last ProcessBatch / ProcessBatchDovi / ProcessBatchYuv call, as a dict; behind a ProcessBatchYuv also yuv_chunks and yuv_lanes (the lane of each chunk)."""
         buf = C.create_string_buffer(512)
         self._check(self._L.mpcvr_get_last_batch_info(self._ctx, buf, 512))
         d = dict(kv.split("=", 1) for kv in buf.value.decode().split(";"))
-        return dict(frames=int(d["frames"]), launches=int(d["launches"]), dovi_runs=d.get("dovi_runs", ""), lane=int(d.get("lane", -1)), waits=int(d.get("waits", 0)), uploads=int(d.get("uploads", -1)))
+        out = dict(frames=int(d["frames"]), launches=int(d["launches"]), dovi_runs=d.get("dovi_runs", ""), lane=int(d.get("lane", -1)), waits=int(d.get("waits", 0)), uploads=int(d.get("uploads", -1)))
+        if "yuv_chunks" in d:        # (only behind a ProcessBatchYuv: the lane of each chunk, -1 = the context stream)
+            out.update(yuv_chunks=int(d["yuv_chunks"]), yuv_lanes=[int(x) for x in d["yuv_lanes"].split(",") if x])
+        return out
 
     def GetLastProcessMs(self):
         ms = C.c_float()

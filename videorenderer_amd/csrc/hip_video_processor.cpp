@@ -63,6 +63,7 @@ CHipVideoProcessor::~CHipVideoProcessor()
     for (DevBuffer *b : {&m_batchConv, &m_batchMid, &m_batchPost, &m_edPost, &m_edHandoff, &m_batchTex, &m_jincFirst, &m_jincSecond, &m_jincFused, &m_TexSrcVideo, &m_TexRaw, &m_TexPost, &m_TexConvertOutput, &m_TexResize, &m_BackBuffer, &m_Snapshot, &m_dither,
                          &m_pqLut, &m_hlgLut, &m_eotfLut, &m_stripTab, &m_axisX, &m_axisY})
         b->Release();
+    for (YuvSurface &ys : m_yuvSurf) ys.buf.Release();
     for (UploadSlot &u : m_up) {
         u.dev.Release();
         if (u.pinned) (void)hipHostFree(u.pinned);
@@ -1070,7 +1071,7 @@ HRESULT CHipVideoProcessor::ProcessFrame(void *pRenderTarget, int rtPitch, const
 HRESULT CHipVideoProcessor::BeginBatch(int n, const void *const *srcs, void *const *dsts, int rtPitch)
 {
     m_lastBatchFrames = n; m_lastBatchLaunches = m_lastBatchUploads = 0; m_lastBatchLane = -1; m_lastBatchWaits = 0;
-    m_dvLastInfo.clear();
+    m_dvLastInfo.clear(); m_yuvLastInfo.clear();
     if (!m_bInit || !m_srcParams) return Fail(MPCVR_E_NOT_VALID_STATE, "InitMediaType has not been called");
     if (n <= 0 || !srcs || !dsts) return Fail(MPCVR_E_INVALIDARG, "empty batch");
     if (rtPitch < m_windowRect.Width() * 4) return Fail(MPCVR_E_INVALIDARG, "render-target pitch smaller than a row");
@@ -1110,12 +1111,8 @@ HRESULT CHipVideoProcessor::ProcessBatchRoutes(BatchRun &run)
     // bench_batch_lanes_call27.txt): same-size block convert +11-16 %, exact-2x kernel +2-5 % (4K -> 8K, four rounds of waves per batch) to +15 %
     // (1080p -> 4K, one round), strip / periodic kernel +11-29 % (1080p -> 1440p 99.8 k -> 116.4 k frames/s, 720p -> 1080p 190 k -> 246 k), fused
     // Jinc2m +4 %.  (An earlier table that had the strip kernels LOSE was a wall clock around 30 launches of 0.3 ms: it measured the closing synchronize.)
-    static const bool lanesOff = [] { const char *e = std::getenv("MPCVR_NO_BATCH_LANES"); return e && *e && *e != '0'; }();
-    const bool laneRoute = rp.route == BatchRoute::FusedUp2x || rp.route == BatchRoute::Strip || rp.route == BatchRoute::DirectConvert;
-    const bool onLane = laneRoute && !rp.repackSlot && !lanesOff && m_ownStream && run.n >= 2 && !m_doviValid && !run.dvFrames && !m_plan.errdiff && !m_plan.hdr_tonemap &&
-                        !(m_cfg.flags & (MPCVR_FLAG_NO_FRAME_LANES | MPCVR_FLAG_NO_FUSED | MPCVR_FLAG_NO_FAST_CONVERT | MPCVR_FLAG_NO_STRIP));
-    // (PrepareSample, ApplyDoviFrame / UploadDoviParams and UploadDoviTables queue on the context stream whatever the run says: they are reached
-    // only from routes that never take a lane — FrameByFrame is no lane route, and a run with Dolby Vision metadata fails the condition above)
+    // (the rule itself: BatchLaneEligible, shared with ProcessBatchYuv)
+    const bool onLane = BatchLaneEligible(rp, run);
     const int bl = onLane ? m_lanes.PickBatchLane(run.n, run.dsts, TargetSpan(nullptr, run.rtPitch).hi, &m_lastBatchWaits) : -1;
     run.on = RunOn{bl >= 0 ? m_lanes.Stream(bl) : m_stream};
     if (bl >= 0) {
@@ -1125,6 +1122,18 @@ HRESULT CHipVideoProcessor::ProcessBatchRoutes(BatchRun &run)
     const HRESULT hr = RunBatchRoute(rp, run);
     if (bl >= 0) m_lanes.NoteLaneBatch(bl);
     return hr;
+}
+
+// May the batch run on a batch lane?  One launch with nothing shared, on a context that owns its stream, default tier (the measurements: the
+// comment in ProcessBatchRoutes).  PrepareSample, ApplyDoviFrame / UploadDoviParams and UploadDoviTables queue on the context stream whatever
+// the run says: they are reached only from routes that never take a lane — FrameByFrame is no lane route, and a run with Dolby Vision
+// metadata fails the condition below.
+bool CHipVideoProcessor::BatchLaneEligible(const BatchRoutePlan &rp, const BatchRun &run) const
+{
+    static const bool lanesOff = [] { const char *e = std::getenv("MPCVR_NO_BATCH_LANES"); return e && *e && *e != '0'; }();
+    const bool laneRoute = rp.route == BatchRoute::FusedUp2x || rp.route == BatchRoute::Strip || rp.route == BatchRoute::DirectConvert;
+    return laneRoute && !rp.repackSlot && !lanesOff && m_ownStream && run.n >= 2 && !m_doviValid && !run.dvFrames && !m_plan.errdiff && !m_plan.hdr_tonemap &&
+           !(m_cfg.flags & (MPCVR_FLAG_NO_FRAME_LANES | MPCVR_FLAG_NO_FUSED | MPCVR_FLAG_NO_FAST_CONVERT | MPCVR_FLAG_NO_STRIP));
 }
 
 // The route of a batch, from the plan and the frames' pointers alone: nothing is launched, allocated or written here.  The pointers of
@@ -1665,6 +1674,7 @@ std::string CHipVideoProcessor::GetLastBatchInfo() const
     std::string s = "frames=" + std::to_string(m_lastBatchFrames) + ";launches=" + std::to_string(m_lastBatchLaunches) + ";lane=" + std::to_string(m_lastBatchLane) + ";waits=" + std::to_string(m_lastBatchWaits) +
                     ";uploads=" + std::to_string(m_lastBatchUploads);
     if (!m_dvLastInfo.empty()) s += ";dovi_runs=" + m_dvLastInfo;
+    s += m_yuvLastInfo;            // (";yuv_chunks=..;yuv_lanes=.." behind a ProcessBatchYuv, empty otherwise)
     return s;
 }
 
@@ -1744,6 +1754,125 @@ HRESULT CHipVideoProcessor::RenderYuv(int /*field*/, int outCformat, uint32_t ex
     m_launches++;
     m_lanes.NoteStreamWork();
     return hr ? Fail(hr, why) : MPCVR_S_OK;
+}
+
+// A batch as NV12 / P010 (include/mpcvr.h: mpcvr_process_batch_yuv).  Everything about the arguments is answered first; then the call is cut
+// into chunks of PlanBatchYuv's size, and each chunk is: the batch machinery into frames of a context-owned surface, ONE k_encode420 launch
+// with a frame dimension behind it on the same stream.  A chunk whose route may take a batch lane (BatchLaneEligible) takes the next lane in
+// turn and that lane's own surface — the lane's stream order covers the surface's write, read and reuse, and the render of the next chunk
+// runs beside this one's pass on the other lane; the lanes order the chunk on the bytes it WRITES for the caller, its planes.  Every other
+// chunk runs on the context stream into the first surface, behind whatever the lanes hold (OrderOnContextStream), the lanes' next work behind it.
+HRESULT CHipVideoProcessor::ProcessBatchYuv(int n, const void *const *srcs, int outCformat, uint32_t extfmt, void *const *yPlanes, int yPitch,
+                                            void *const *uvPlanes, int uvPitch)
+{
+    m_lastBatchFrames = n > 0 ? n : 0; m_lastBatchLaunches = m_lastBatchUploads = 0; m_lastBatchLane = -1; m_lastBatchWaits = 0;
+    m_dvLastInfo.clear(); m_yuvLastInfo.clear();
+    if (!m_bInit || !m_srcParams) return Fail(MPCVR_E_NOT_VALID_STATE, "InitMediaType has not been called");
+    if (n <= 0) return Fail(MPCVR_E_INVALIDARG, "empty batch");
+    if (!srcs || !yPlanes || !uvPlanes) return Fail(MPCVR_E_POINTER, "null array of frames or planes");
+    for (int i = 0; i < n; i++)
+        if (!srcs[i] || !yPlanes[i] || !uvPlanes[i]) return Fail(MPCVR_E_POINTER, "null frame or plane in batch");
+    const int w = m_windowRect.Width(), h = m_windowRect.Height();
+    BatchYuvLayout lay;
+    if (!PlanBatchYuv(w, h, n, m_yuvBudget, &lay)) return Fail(MPCVR_E_INVALIDARG, "a 4:2:0 frame needs an even window width and height, 2 .. 32768");
+    // what the pass refuses, per frame (the surface is still to be allocated: it cannot overlap a plane) ...
+    const char *why = "";
+    for (int i = 0; i < n; i++)
+        if (HRESULT bad = EncodeSurface(nullptr, lay.surfacePitch, m_cfg.output_format, w, h, outCformat, extfmt, yPlanes[i], yPitch, uvPlanes[i], uvPitch, nullptr, true, &why))
+            return Fail(bad, why);
+    EncodePlan plan;
+    if (!PlanEncode(outCformat, m_cfg.output_format, extfmt, w, h, &plan)) return Fail(MPCVR_E_INVALIDARG, "output NV12 or P010 with a YCbCr description");
+    // ... and the 2n planes against each other: a plane counts as the bytes from its first pixel to the last pixel of its last row
+    const size_t rowBytes = plan.out10 ? (size_t)2 * w : (size_t)w;
+    const std::vector<RtSpan> planes = BatchPlaneSpans(n, yPlanes, yPitch, uvPlanes, uvPitch, h, rowBytes);
+    if (AnyTwoSpansOverlap(planes)) return Fail(MPCVR_E_INVALIDARG, "two planes of the batch overlap");
+
+    const unsigned before = m_launches, uploadsBefore = m_tableUploads;
+    (void)hipSetDevice(m_device);
+    HRESULT hr;
+    if (m_planDirty && (hr = UpdatePlan())) return hr;
+    EncodeParams ep{};
+    ep.src_pitch = lay.surfacePitch; ep.y_pitch = yPitch; ep.uv_pitch = uvPitch;
+    ep.w = w; ep.h = h;
+    std::memcpy(ep.coef, plan.coef, sizeof(ep.coef));
+    std::memcpy(ep.off, plan.off, sizeof(ep.off));
+    ep.src16 = 1;                                       // every frame of a surface starts on 256 bytes, the pitch is a multiple of 16
+    const int most = lay.framesPerChunk;
+    std::vector<void *> frames((size_t)most);
+    auto surfaceFrames = [&](YuvSurface &s) -> HRESULT {       // the surface for `most` frames, and their addresses
+        const size_t had = s.buf.ptr ? s.buf.size : 0;
+        if (HRESULT bad = CheckHip(s.buf.CheckCreate(lay.frameStride * (size_t)most), "batch RGB surface")) return bad;
+        if (s.buf.size != had) s.cleared = false;
+        for (int i = 0; i < most; i++) frames[i] = (uint8_t *)s.buf.ptr + (size_t)i * lay.frameStride;
+        return MPCVR_S_OK;
+    };
+    std::string lanes;
+    int chunks = 0;
+    hr = MPCVR_S_OK;
+    for (int at = 0; at < n && !hr; at += most, chunks++) {
+        const int m = std::min(most, n - at);
+        BatchRun run{m, srcs + at, frames.data(), lay.surfacePitch};
+        YuvSurface *surf = &m_yuvSurf[0];
+        if ((hr = surfaceFrames(*surf))) break;
+        int bl = -1;
+        BatchRoutePlan rp;
+        if (!m_plan.errdiff) {
+            rp = ClassifyBatch(run);
+            if (BatchLaneEligible(rp, run)) {
+                int waits = 0;
+                bl = m_lanes.PickBatchLane(std::vector<RtSpan>(planes.begin() + 2 * (size_t)at, planes.begin() + 2 * (size_t)(at + m)), &waits);
+                m_lastBatchWaits += waits;
+                if (bl > 0) {                           // another lane, another surface: the route is planned for the targets it draws into
+                    surf = &m_yuvSurf[bl];
+                    if ((hr = surfaceFrames(*surf))) break;
+                    rp = ClassifyBatch(run);
+                }
+            }
+        }
+        run.on = RunOn{bl >= 0 ? m_lanes.Stream(bl) : m_stream};
+        if (bl >= 0) {
+            m_lastBatchLane = bl;
+            m_lanes.LaneWaitsForStream(bl, m_stream);
+        } else OrderOnContextStream();
+        if (chunks < 64) lanes += (chunks ? "," : "") + std::to_string(bl);
+        hr = RunYuvChunk(rp, run, *surf, ep, plan, yPlanes + at, uvPlanes + at);
+        if (bl >= 0) m_lanes.NoteLaneBatch(bl); else m_lanes.NoteStreamWork();
+    }
+    m_lastBatchLaunches = (int)(m_launches - before);
+    m_lastBatchUploads = (int)(m_tableUploads - uploadsBefore);
+    m_yuvLastInfo = ";yuv_chunks=" + std::to_string(chunks) + ";yuv_lanes=" + lanes;
+    return hr;
+}
+
+HRESULT CHipVideoProcessor::RunYuvChunk(BatchRoutePlan &rp, BatchRun &run, YuvSurface &surf, const EncodeParams &encode,
+                                        const EncodePlan &plan, void *const *yPlanes, void *const *uvPlanes)
+{
+    hipStream_t const stream = run.on.stream;
+    HRESULT hr;
+    // Process never writes the letterbox: black once per allocation and per window / video rect, in front of the first chunk that draws there
+    if (!surf.cleared || surf.window != m_windowRect || surf.video != m_videoRect) {
+        if ((hr = CheckHip(hipMemsetAsync(surf.buf.ptr, 0, surf.buf.size, stream), "clear batch RGB surface"))) return hr;
+        surf.cleared = true; surf.window = m_windowRect; surf.video = m_videoRect;
+    }
+    // (the error-diffusion plan runs its own chunks and its pass on the context stream: `run` is on it, BatchLaneEligible refuses such a plan)
+    if ((hr = m_plan.errdiff ? ProcessBatchErrDiff(run) : RunBatchRoute(rp, run))) return hr;
+    // the planes' table through the frame-table ring; the lease ends behind the pass
+    SlotLease table;
+    TableSlot &slot = m_slots[m_slotNext];
+    m_slotNext = (m_slotNext + 1) % kFrameSlots;
+    if ((hr = AcquireSlot(slot, sizeof(EncodeFrame) * run.n, sizeof(EncodeFrame) * 64, stream, &table))) return hr;
+    EncodeFrame *fr = (EncodeFrame *)slot.pinned;
+    uintptr_t bits = (uintptr_t)encode.y_pitch | (uintptr_t)encode.uv_pitch;
+    for (int i = 0; i < run.n; i++) {
+        fr[i] = EncodeFrame{(const uint8_t *)run.dsts[i], (uint8_t *)yPlanes[i], (uint8_t *)uvPlanes[i]};
+        bits |= (uintptr_t)yPlanes[i] | (uintptr_t)uvPlanes[i];
+    }
+    if ((hr = CheckHip(hipMemcpyAsync(slot.dev.ptr, fr, sizeof(EncodeFrame) * run.n, hipMemcpyHostToDevice, stream), "plane table"))) return hr;
+    m_tableUploads++;
+    EncodeParams ep = encode;
+    ep.frames = (const EncodeFrame *)table.dev;
+    ep.dst8 = (bits & 7) == 0;                          // the 8-byte stores only if every plane of the launch allows them
+    return CheckHip(LaunchEncode420(ep, plan.in10, plan.out10, plan.siting, stream, run.n), "k_encode420");
 }
 
 HRESULT CHipVideoProcessor::GetBackBuffer(void **ptr, int *pitch, int *w, int *h)

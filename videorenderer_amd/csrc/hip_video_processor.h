@@ -79,6 +79,10 @@ public:
     HRESULT GetCurentImage(void *hostBGRA, size_t *size);                     // :3493
     HRESULT GetDisplayedImage(void *hostPixels, size_t *size, bool deepColor, int *width, int *height, int *bits);     // :3610
     HRESULT ProcessBatch(int n, const void *const *srcs, void *const *dsts, int rtPitch);
+    // EXTENSION (mpcvr_process_batch_yuv): the batch in chunks through the batch machinery into a context-owned RGB surface, one k_encode420
+    // launch (its frame dimension) behind each chunk on the same stream — the context stream, or a batch lane with a surface of its own
+    HRESULT ProcessBatchYuv(int n, const void *const *srcs, int outCformat, uint32_t extfmt, void *const *yPlanes, int yPitch, void *const *uvPlanes, int uvPitch);
+    HRESULT SetBatchYuvBudget(size_t bytes) { m_yuvBudget = bytes; return MPCVR_S_OK; }
     std::string GetLastBatchInfo() const;
     HRESULT ProcessBatchDovi(int n, const void *const *srcs, void *const *dsts, int rtPitch, const mpcvr_dovi_metadata *rpus);
     void Flush();                                                             // :4074
@@ -306,12 +310,13 @@ private:
     AxisTaps m_tapsX{}, m_tapsY{};
     const int32_t *m_otherX = nullptr, *m_otherY = nullptr;
     // ring of frame-table slots for mpcvr_process_batch (pinned host copy + device copy + completion event)
-    static constexpr int kFrameSlots = 4;
+    // (eight: a chunk of mpcvr_process_batch_yuv takes up to two, its frames' and its planes' — the host queues four such chunks before it waits for the first)
+    static constexpr int kFrameSlots = 8;
     TableSlot m_slots[kFrameSlots];
     int m_slotNext = 0;
     uint16_t m_ditherHost[1024];
     // Frames and whole batches of a context that owns its stream overlap on the frame lanes (vp_lanes.h: the streams, what is in flight on
-    // them and what orders it).  What may take a lane is decided here, from the plan: FrameLanesUsable, the onLane rule of ProcessBatchRoutes
+    // them and what orders it).  What may take a lane is decided here, from the plan: FrameLanesUsable for frames, BatchLaneEligible for batches
     FrameLanes m_lanes;
     int m_lastBatchWaits = 0;                 // writers still in flight on other lanes the last batch was ordered behind (GetLastBatchInfo)
     hipStream_t m_lastRun = nullptr;          // the stream the current sample's last Process ran on (MarkConsumed records there)
@@ -376,6 +381,21 @@ private:
         FusedParams conv{}, direct{};  // WholeBatchLaunches / DirectConvert (BatchPlan)
     };
     BatchRoutePlan ClassifyBatch(const BatchRun &run) const;
+    // may a batch of this route run on a batch lane beside the one before it?  The one predicate of ProcessBatchRoutes and ProcessBatchYuv
+    bool BatchLaneEligible(const BatchRoutePlan &rp, const BatchRun &run) const;
+    // mpcvr_process_batch_yuv: one RGB surface per batch lane (a lane's chunks write, read and reuse its surface in stream order); chunks on
+    // the context stream use the first (they run behind everything the lanes hold, and the lanes' next work behind them)
+    struct YuvSurface {
+        DevBuffer buf;
+        CRect window, video;           // what it was last cleared for (the letterbox is never written by Process)
+        bool cleared = false;
+    };
+    YuvSurface m_yuvSurf[FrameLanes::kFrameLanes];
+    size_t m_yuvBudget = 0;            // SetBatchYuvBudget; 0: kBatchYuvDefaultBudget
+    std::string m_yuvLastInfo;         // ";yuv_chunks=..;yuv_lanes=.." of the last batch call, if it was a ProcessBatchYuv
+    // one chunk: rp / run.dsts name the surface's frames, run.on the stream; `encode` holds the launch's pitches, size and coefficients
+    HRESULT RunYuvChunk(BatchRoutePlan &rp, BatchRun &run, YuvSurface &surf, const EncodeParams &encode, const EncodePlan &plan,
+                        void *const *yPlanes, void *const *uvPlanes);
     HRESULT RunBatchRoute(BatchRoutePlan &rp, BatchRun &run);
     bool BatchPlan(const uint8_t *sample0, void *rt0, int rtPitch, bool aligned, bool repacked, bool src16, FusedParams *conv, FusedParams *direct) const;
     HRESULT ProcessBatchLaunches(const BatchRun &run, const FusedFrame *table, bool aligned, FusedParams conv);

@@ -167,6 +167,29 @@ int32_t mpcvr_process_batch_dovi(mpcvr_ctx *ctx, int32_t n, const void *const *s
     return ctx->vp.ProcessBatchDovi(n, srcs, dsts, dst_pitch, rpus);
 }
 
+// EXTENSION: a batch as NV12 / P010 (include/mpcvr.h; PlanBatchYuv vp_plan.cpp, CHipVideoProcessor::ProcessBatchYuv)
+static_assert(MPCVR_BATCH_YUV_DEFAULT_BUDGET == mpcvr::kBatchYuvDefaultBudget, "the header and vp_encode.h name one default budget");
+int32_t mpcvr_plan_batch_yuv(int32_t window_w, int32_t window_h, int32_t n, size_t budget_bytes,
+                             int32_t *surface_pitch, size_t *frame_stride, int32_t *frames_per_chunk, int32_t *chunks)
+{
+    mpcvr::BatchYuvLayout lay;
+    if (!mpcvr::PlanBatchYuv(window_w, window_h, n, budget_bytes, &lay)) return MPCVR_E_INVALIDARG;
+    if (surface_pitch) *surface_pitch = lay.surfacePitch;
+    if (frame_stride) *frame_stride = lay.frameStride;
+    if (frames_per_chunk) *frames_per_chunk = lay.framesPerChunk;
+    if (chunks) *chunks = lay.chunks;
+    return MPCVR_S_OK;
+}
+
+int32_t mpcvr_set_batch_yuv_budget(mpcvr_ctx *ctx, size_t bytes) { CTX_OR_FAIL(); return ctx->vp.SetBatchYuvBudget(bytes); }
+
+int32_t mpcvr_process_batch_yuv(mpcvr_ctx *ctx, int32_t n, const void *const *srcs, int32_t out_cformat, uint32_t extfmt,
+                                void *const *y_planes, int32_t y_pitch, void *const *uv_planes, int32_t uv_pitch)
+{
+    CTX_OR_FAIL();
+    return ctx->vp.ProcessBatchYuv(n, srcs, out_cformat, extfmt, y_planes, y_pitch, uv_planes, uv_pitch);
+}
+
 int32_t mpcvr_get_param_blob(mpcvr_ctx *ctx, void *buf, size_t *size) { CTX_OR_FAIL(); return ctx->vp.GetParamBlob(buf, size); }
 int32_t mpcvr_get_fused_tables(mpcvr_ctx *ctx, void *buf, size_t *size) { CTX_OR_FAIL(); return ctx->vp.GetFusedTables(buf, size); }
 int32_t mpcvr_set_param_blob(mpcvr_ctx *ctx, const void *buf, size_t size) { CTX_OR_FAIL(); return ctx->vp.SetParamBlob(buf, size); }

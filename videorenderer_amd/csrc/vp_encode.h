@@ -27,6 +27,16 @@ struct EncodePlan {
 // on it).  false: another output or source format, or a description that plans as RGB (value == 0)
 bool PlanEncode(int out_cformat, int src_fmt, uint32_t extfmt, int w, int h, EncodePlan *plan);
 
+// The layout integers of include/mpcvr.h (mpcvr_plan_batch_yuv): the context-owned RGB surface a batch is rendered into on its way to the
+// planes, and how a batch of n frames is cut into chunks under a budget of bytes.  Host only (vp_plan.cpp).  false: n <= 0 or a window
+// that is odd or outside 2 .. 32768
+struct BatchYuvLayout { int32_t surfacePitch; size_t frameStride; int32_t framesPerChunk, chunks; };
+constexpr size_t kBatchYuvDefaultBudget = (size_t)4 << 30;      // MPCVR_BATCH_YUV_DEFAULT_BUDGET (mpcvr_capi.cpp asserts they agree)
+bool PlanBatchYuv(int w, int h, int n, size_t budget, BatchYuvLayout *out);
+
+// one frame of a launch with a frame dimension: its source surface and its two planes (pitches, size and format are the launch's)
+struct EncodeFrame { const uint8_t *src; uint8_t *y, *uv; };
+
 struct EncodeParams {
     const uint8_t *src; int src_pitch;                 // w x h texels of 4 bytes
     uint8_t *y; int y_pitch;                           // h rows of w components
@@ -35,8 +45,12 @@ struct EncodeParams {
     int32_t coef[9], off[3];                           // rows Y, U, V; columns R, G, B
     int src16;                                         // source and its pitch on 16 bytes: a lane with four columns takes one 16-byte load per row
     int dst8;                                          // P010: both planes and pitches on 8 bytes: one 8-byte store per row piece (else two of 4)
+    // DEVICE table of n_frames {src, y, uv} rows, frame = blockIdx.z (the convention of the FusedFrame tables, vp_launch.h); null: one frame,
+    // src / y / uv above.  With a table src16 and dst8 hold only if EVERY frame of the launch allows them
+    const EncodeFrame *frames;
 };
-// every pointer and pitch a multiple of 4 and the planes apart from each other and from the source (the caller checks: mpcvr_encode_pass); one launch
-hipError_t LaunchEncode420(const EncodeParams &p, bool in10, bool out10, int siting, hipStream_t stream);
+// every pointer and pitch a multiple of 4 and the planes apart from each other and from the source (the caller checks: mpcvr_encode_pass,
+// mpcvr_process_batch_yuv); one launch for up to 65535 frames (the grid's z extent), one more per further 65535
+hipError_t LaunchEncode420(const EncodeParams &p, bool in10, bool out10, int siting, hipStream_t stream, int n_frames = 1);
 
 }  // namespace mpcvr

@@ -14,8 +14,12 @@
 //     integer multiply-adds, modulo 2^32 until the final value, which fits (tests/test_encode.py bounds it for every plan);
 //   * stores: NV12 one dword of Y per row and one of UV; P010 8 bytes each where both planes and pitches are on 8 bytes, else two dwords.
 //     The lane with only two columns left stores half of that; lanes past the width store nothing.
+//   * a batch (mpcvr_process_batch_yuv) is one launch: blockIdx.z is the frame, its {src, y, uv} row of EncodeParams::frames is read once per
+//     wavefront with scalar loads (the address is uniform); a single frame (no table) takes its pointers from the arguments as before,
+//     behind one uniform branch.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 
 #include "vp_encode.h"
@@ -73,7 +77,22 @@ __global__ __launch_bounds__(256) void k_encode420(EncodeParams p)
     const bool full = x0 + 4 <= p.w, any = x0 < p.w;
     const bool vec = p.src16 && full;
 
-    const uint8_t *r0 = p.src + (size_t)(2 * pr) * p.src_pitch;
+    // the frame: from the arguments, or its row of the table (uniform: blockIdx.z)
+    uintptr_t a_src = (uintptr_t)p.src, a_y = (uintptr_t)p.y, a_uv = (uintptr_t)p.uv;
+    // (the empty statement pins the arguments' pointers in scalar registers here, in front of the branch: folded into a select of
+    // addresses, the single frame's pointers would come through a second load that depends on the one of p.frames)
+    asm volatile("" : "+s"(a_src), "+s"(a_y), "+s"(a_uv));
+    if (p.frames) {
+        // (read through the constant address space: the row's address is uniform, so these are scalar loads like the arguments' own)
+        typedef const EncodeFrame __attribute__((address_space(4))) *ConstRow;
+        const ConstRow f = (ConstRow)(uintptr_t)(p.frames + blockIdx.z);
+        a_src = (uintptr_t)f->src; a_y = (uintptr_t)f->y; a_uv = (uintptr_t)f->uv;
+    }
+    // (device memory either way: named as such, so that the loads and stores below stay global ones)
+    typedef uint8_t __attribute__((address_space(1))) *GlobalBytes;
+    const uint8_t *src = (const uint8_t *)(GlobalBytes)a_src;
+    uint8_t *yp = (uint8_t *)(GlobalBytes)a_y, *uvp = (uint8_t *)(GlobalBytes)a_uv;
+    const uint8_t *r0 = src + (size_t)(2 * pr) * p.src_pitch;
     uint32_t t[2][4], left[2] = {0, 0};
     LoadRow<HALO>(r0, x0, p.w, vec, lane, t[0], left[0]);
     LoadRow<HALO>(r0 + p.src_pitch, x0, p.w, vec, lane, t[1], left[1]);
@@ -112,7 +131,7 @@ __global__ __launch_bounds__(256) void k_encode420(EncodeParams p)
         } else {
             // vertical [1 2 1] centred on the pair's first row: the row above (row 0 replicates itself)
             uint32_t ta[4], la = 0;
-            LoadRow<true>(p.src + (size_t)max(2 * pr - 1, 0) * p.src_pitch, x0, p.w, vec, lane, ta, la);
+            LoadRow<true>(src + (size_t)max(2 * pr - 1, 0) * p.src_pitch, x0, p.w, vec, lane, ta, la);
             uint32_t rb[5], g[5];
             Split<IN10>(la, rb[0], g[0]);
 #pragma unroll
@@ -145,8 +164,8 @@ __global__ __launch_bounds__(256) void k_encode420(EncodeParams p)
         for (int b = 0; b < 2; b++) cv[b][c] = Dot<IN10>(p.coef + 3 * (1 + c), srb[b], sg[b], cbias, S + LOGW, MAXV);
     }
 
-    uint8_t *yrow = p.y + (size_t)(2 * pr) * p.y_pitch;
-    uint8_t *crow = p.uv + (size_t)pr * p.uv_pitch;
+    uint8_t *yrow = yp + (size_t)(2 * pr) * p.y_pitch;
+    uint8_t *crow = uvp + (size_t)pr * p.uv_pitch;
     if (!OUT10) {
 #pragma unroll
         for (int r = 0; r < 2; r++) {
@@ -186,12 +205,19 @@ hipError_t LaunchSiting(const EncodeParams &p, int siting, dim3 grid, hipStream_
 
 }  // namespace
 
-hipError_t LaunchEncode420(const EncodeParams &p, bool in10, bool out10, int siting, hipStream_t stream)
+hipError_t LaunchEncode420(const EncodeParams &params, bool in10, bool out10, int siting, hipStream_t stream, int n_frames)
 {
-    if (p.w < 2 || p.h < 2 || ((p.w | p.h) & 1)) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)((p.w + 255) / 256), (unsigned)((p.h / 2 + 3) / 4));
-    if (in10) return out10 ? LaunchSiting<true, true>(p, siting, grid, stream) : LaunchSiting<true, false>(p, siting, grid, stream);
-    return out10 ? LaunchSiting<false, true>(p, siting, grid, stream) : LaunchSiting<false, false>(p, siting, grid, stream);
+    EncodeParams p = params;
+    if (p.w < 2 || p.h < 2 || ((p.w | p.h) & 1) || n_frames < 1 || (n_frames > 1 && !p.frames)) return hipErrorInvalidValue;
+    constexpr int kMaxZ = 65535;                        // the grid's z extent
+    for (int at = 0; at < n_frames; at += kMaxZ) {
+        if (params.frames) p.frames = params.frames + at;
+        const dim3 grid((unsigned)((p.w + 255) / 256), (unsigned)((p.h / 2 + 3) / 4), (unsigned)std::min(kMaxZ, n_frames - at));
+        const hipError_t e = in10 ? (out10 ? LaunchSiting<true, true>(p, siting, grid, stream) : LaunchSiting<true, false>(p, siting, grid, stream))
+                                  : (out10 ? LaunchSiting<false, true>(p, siting, grid, stream) : LaunchSiting<false, false>(p, siting, grid, stream));
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 }  // namespace mpcvr

@@ -2,6 +2,7 @@
 #include "vp_lanes.h"
 
 #include <cstdlib>
+#include <utility>
 
 namespace mpcvr {
 
@@ -45,14 +46,21 @@ int FrameLanes::PickFrameLane(const RtSpan &rt)
 
 int FrameLanes::PickBatchLane(int n, void *const *dsts, size_t bytes, int *waits)
 {
+    std::vector<RtSpan> spans;
+    spans.reserve((size_t)n);
+    for (int i = 0; i < n; i++) { RtSpan s; s.lo = (uintptr_t)dsts[i]; s.hi = s.lo + bytes; spans.push_back(s); }
+    return PickBatchLane(std::move(spans), waits);
+}
+
+int FrameLanes::PickBatchLane(std::vector<RtSpan> &&written, int *waits)
+{
     Lane *pick = &m_lanes[m_batchNext];
     if (!pick->stream && hipStreamCreateWithFlags(&pick->stream, hipStreamDefault) != hipSuccess) { pick->stream = nullptr; return -1; }
     // (two lanes: MPCVR_BATCH_LANE_COUNT = 2 .. 8 for the A/B — profiles/r06/batch_lane_count_call34.txt)
     static const int count = [] { const char *e = std::getenv("MPCVR_BATCH_LANE_COUNT"); const int v = e && *e ? std::atoi(e) : kBatchLanes; return v < 2 ? 2 : v > kFrameLanes ? kFrameLanes : v; }();
     m_batchNext = (m_batchNext + 1) % count;
     std::vector<RtSpan> &spans = m_batchSpans;
-    spans.clear();
-    for (int i = 0; i < n; i++) { RtSpan s; s.lo = (uintptr_t)dsts[i]; s.hi = s.lo + bytes; spans.push_back(s); }
+    spans = std::move(written);
     SortAndMergeSpans(spans);
     *waits = 0;
     for (Lane &fl : m_lanes) {

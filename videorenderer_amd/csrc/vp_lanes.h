@@ -1,6 +1,6 @@
 // vp_lanes.h — FrameLanes: the streams beside the context stream that frames and whole batches of one context overlap on, and the
 // bookkeeping that keeps writes into the same memory in order.  WHICH frames and batches may take a lane is the processor's decision
-// (CHipVideoProcessor::FrameLanesUsable, ProcessBatchRoutes: it depends on the plan); this class only answers where and behind what.
+// (CHipVideoProcessor::FrameLanesUsable, BatchLaneEligible: it depends on the plan); this class only answers where and behind what.
 //
 // mpcvr_process frame after frame (the reference's own call pattern, Render -> Process, DX11VideoProcessor.cpp:2730): a single 4K
 // frame is one round of waves on this part, so a kernel's ramp-up and drain cost a third of its time when frames run strictly one
@@ -37,6 +37,9 @@ public:
     // writes into the bytes of one of its render targets [dsts[i], dsts[i] + bytes): single frames (their ring entries) and batches;
     // *waits: how many such writers.  -1: no stream
     int PickBatchLane(int n, void *const *dsts, size_t bytes, int *waits);
+    // the same for a batch that writes `spans` (any order, overlaps allowed; taken over): what mpcvr_process_batch_yuv passes for a chunk — the
+    // planes it leaves, not the context-owned surface it renders into on the way (that surface belongs to the lane: stream order covers it)
+    int PickBatchLane(std::vector<RtSpan> &&spans, int *waits);
     hipStream_t Stream(int lane) const { return m_lanes[lane].stream; }
     void NoteLaneFrame(int lane, const RtSpan &rt);   // the frame just queued on the lane writes `rt`
     void NoteLaneBatch(int lane);                     // the batch PickBatchLane picked the lane for has been queued on it

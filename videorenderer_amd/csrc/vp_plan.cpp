@@ -223,6 +223,18 @@ void ComputeColorMatrix(const ExtFmt &ex, const FmtConvParams &f, const ProcAmp 
 // inverts it: yuv = N (rgb - c), N = inverse(M), with rgb = code_in / maxin and code_out = yuv * T (T = 255: one byte per component;
 // 65535 / 64: the 10-bit code sits in the top of a 16-bit word, of which this library's P010 reader takes all 16 bits).
 // ------------------------------------------------------------------------------------------------
+bool PlanBatchYuv(int w, int h, int n, size_t budget, BatchYuvLayout *out)
+{
+    if (n <= 0 || w < 2 || h < 2 || ((w | h) & 1) || w > 32768 || h > 32768) return false;
+    if (!budget) budget = kBatchYuvDefaultBudget;
+    out->surfacePitch = (4 * w + 15) & ~15;
+    out->frameStride = ((size_t)out->surfacePitch * (size_t)h + 255) & ~(size_t)255;
+    const size_t fit = budget / out->frameStride;
+    out->framesPerChunk = (int32_t)(fit < 1 ? 1 : fit > (size_t)n ? (size_t)n : fit);
+    out->chunks = (n + out->framesPerChunk - 1) / out->framesPerChunk;
+    return true;
+}
+
 bool PlanEncode(int out_cformat, int src_fmt, uint32_t extfmt, int w, int h, EncodePlan *plan)
 {
     if (out_cformat != MPCVR_CF_NV12 && out_cformat != MPCVR_CF_P010) return false;

@@ -24,6 +24,30 @@ inline void SortAndMergeSpans(std::vector<RtSpan> &v)
     v.resize(m);
 }
 
+// do any two of the (non-empty) spans share a byte?  Sorted by address, a span overlaps an earlier one exactly when it starts in front of the
+// furthest end seen so far; spans that touch do not overlap, two spans from one address do.  (mpcvr_process_batch_yuv: the 2n planes of a batch)
+inline bool AnyTwoSpansOverlap(std::vector<RtSpan> v)
+{
+    std::sort(v.begin(), v.end(), [](const RtSpan &a, const RtSpan &b) { return a.lo < b.lo; });
+    uintptr_t end = 0;
+    for (size_t i = 0; i < v.size(); i++) {
+        if (i && v[i].lo < end) return true;
+        end = std::max(end, v[i].hi);
+    }
+    return false;
+}
+
+// the 2n planes of a batch of 4:2:0 frames as spans, frame i at [2i] (Y: h rows) and [2i + 1] (UV: h / 2 rows), rows of rowBytes
+inline std::vector<RtSpan> BatchPlaneSpans(int n, void *const *y, int yPitch, void *const *uv, int uvPitch, int h, size_t rowBytes)
+{
+    std::vector<RtSpan> v((size_t)2 * (size_t)n);
+    for (int i = 0; i < n; i++) {
+        v[2 * i].lo = (uintptr_t)y[i]; v[2 * i].hi = v[2 * i].lo + (size_t)(h - 1) * (size_t)yPitch + rowBytes;
+        v[2 * i + 1].lo = (uintptr_t)uv[i]; v[2 * i + 1].hi = v[2 * i + 1].lo + (size_t)(h / 2 - 1) * (size_t)uvPitch + rowBytes;
+    }
+    return v;
+}
+
 // does `s` share a byte with one of `sorted` (SortAndMergeSpans' result)?
 inline bool SpansOverlap(const std::vector<RtSpan> &sorted, const RtSpan &s)
 {
