@@ -304,6 +304,41 @@ int32_t mpcvr_encode_pass(const void *src, int32_t src_pitch, int32_t src_fmt, i
 int32_t mpcvr_render_yuv(mpcvr_ctx *ctx, int32_t field, int32_t out_cformat, uint32_t extfmt, void *y_plane, int32_t y_pitch,
                          void *uv_plane, int32_t uv_pitch);
 
+/* EXTENSION — measuring what was rendered: the histogram of max(R, G, B), and MaxCLL / MaxFALL (CTA-861.3) from it.  The reference's
+ * statistics are an on-screen overlay; there is no reference line to cite.  The definition is the integer text below, modelled bit for bit
+ * by tests/measure_model.py.
+ *   Input: a DEVICE surface of w x h 32-bit texels, src_fmt = MPCVR_OUT_BGRA8 (maxin = 255) or MPCVR_OUT_RGB10A2 (maxin = 1023), w and h in
+ *   1 .. 32768 (odd sizes allowed), src and src_pitch multiples of 4, src_pitch >= 4 w; the A / X bits are ignored.
+ *   rect = [left, right) x [top, bottom), non-empty and inside the surface, any parity and alignment; NULL = the whole surface.
+ *   Output: uint32_t hist[MPCVR_HIST_BINS] in DEVICE memory, 4-byte aligned.  After the pass hist[c] = the number of texels of rect with
+ *   max(R, G, B) == c (for BGRA8 the bins 256 .. 1023 are 0).  The pass OVERWRITES the 1024 words whatever they held and writes no other byte.
+ * Counts are exact (the largest is 32768^2 = 2^30): every counter on the way is a 32-bit integer, so the result does not depend on the
+ * order of the additions and is bit-reproducible.  The histogram is complete in stream order behind the call.
+ * Refusals, with nothing launched and nothing written: MPCVR_E_POINTER for a NULL src or hist_dev; MPCVR_E_INVALIDARG for another src_fmt,
+ * w or h out of range, a pointer or pitch that breaks the rules above, a rect that is empty or leaves the surface, and a histogram that
+ * overlaps the surface (the surface counts as the bytes from its first pixel to the last pixel of its last row).
+ * The same histogram serves SDR frames: black-frame detection, scene cuts, percentile peaks (mpcvr_histogram_percentile). */
+#define MPCVR_HIST_BINS 1024
+int32_t mpcvr_measure_pass(const void *src, int32_t src_pitch, int32_t src_fmt, int32_t w, int32_t h,
+                           const mpcvr_rect *rect, uint32_t *hist_dev, void *stream);
+/* The pass over the frame the last mpcvr_render / mpcvr_render_yuv left in the context's back buffer, over video rect ∩ window: the active
+ * picture without the letterbox, as CTA-861.3 wants for the frame-average.  Queued on the context stream behind whatever the frame lanes
+ * still write, and every later frame, lanes included, runs behind it; the histogram is complete after mpcvr_synchronize.  MPCVR_S_FALSE,
+ * with nothing written, when no frame has been rendered yet (or the window changed since); an empty active area gives 1024 zeros and S_OK.
+ * MPCVR_E_POINTER for a NULL hist_dev, MPCVR_E_INVALIDARG for one that is not 4-byte aligned or overlaps the back buffer. */
+int32_t mpcvr_measure_backbuffer(mpcvr_ctx *ctx, uint32_t *hist_dev);
+/* What a host derives from a histogram (HOST memory; no GPU, no context).  pixels = sum of hist; min_code / max_code = the smallest /
+ * largest non-empty bin (-1 for an empty histogram, the nits are then 0); max_nits = L(max_code); avg_nits = (sum over c ascending of
+ * hist[c] * L(c)) / pixels in double, with L(c) = 10000 * EOTF_ST2084(c / maxin) evaluated in double with the constants of
+ * Shaders/convert/st2084.hlsl.  The codes mean something for every surface; the NITS only for a PQ surface (a context with
+ * mpcvr_set_hdr_output enabled, whose frames are HDR10).  For a stream, MaxCLL = the maximum of max_nits over its frames and MaxFALL = the
+ * maximum of avg_nits: the host keeps the two running maxima.  MPCVR_E_POINTER for a NULL pointer, MPCVR_E_INVALIDARG for another src_fmt. */
+typedef struct mpcvr_light_level { uint64_t pixels; int32_t min_code, max_code; double max_nits, avg_nits; } mpcvr_light_level;
+int32_t mpcvr_light_level_from_histogram(const uint32_t hist[MPCVR_HIST_BINS], int32_t src_fmt, mpcvr_light_level *out);
+/* *code = the smallest c with hist[0] + ... + hist[c] >= ceil(ppm * pixels / 10^6), in 64-bit integers; ppm in 1 .. 1000000 (1000000: the
+ * largest non-empty bin).  MPCVR_E_POINTER for a NULL pointer, MPCVR_E_INVALIDARG for ppm out of range or an empty histogram. */
+int32_t mpcvr_histogram_percentile(const uint32_t hist[MPCVR_HIST_BINS], uint32_t ppm, int32_t *code);
+
 /* Configure — DX11VideoProcessor.cpp:3800-4050: diff each field, rebuild only what changed. */
 int32_t mpcvr_configure(mpcvr_ctx *ctx, const mpcvr_settings *settings);
 
@@ -455,6 +490,17 @@ int32_t mpcvr_plan_batch_yuv(int32_t window_w, int32_t window_h, int32_t n, size
 int32_t mpcvr_set_batch_yuv_budget(mpcvr_ctx *ctx, size_t bytes);
 int32_t mpcvr_process_batch_yuv(mpcvr_ctx *ctx, int32_t n, const void *const *srcs, int32_t out_cformat, uint32_t extfmt,
                                 void *const *y_planes, int32_t y_pitch, void *const *uv_planes, int32_t uv_pitch);
+/* EXTENSION — mpcvr_process_batch_yuv plus the histograms of mpcvr_measure_pass: hist_dev holds n rows of MPCVR_HIST_BINS words in DEVICE
+ * memory, frame i at hist_dev + 1024 i.  Row i is what mpcvr_measure_pass over video rect ∩ window gives on the RGB target i that
+ * mpcvr_process_batch leaves (an empty active area: zeros); the planes are byte for byte those of mpcvr_process_batch_yuv.  Per chunk ONE
+ * measure launch with a frame dimension reads the chunk's frames in the context-owned surface, on the chunk's stream behind its k_encode420
+ * launch: "launches" of mpcvr_get_last_batch_info grows by exactly one per chunk.  The rows of a chunk are bytes it writes for the caller:
+ * the lanes order on them as on the planes, so two calls into one histogram buffer stay in the order they were queued.  The rows are
+ * complete after mpcvr_synchronize.  Refusals beyond those of mpcvr_process_batch_yuv, before anything is drawn: MPCVR_E_POINTER for a NULL
+ * hist_dev; MPCVR_E_INVALIDARG for one that is not 4-byte aligned or whose n rows overlap a plane of the batch. */
+int32_t mpcvr_process_batch_yuv_stats(mpcvr_ctx *ctx, int32_t n, const void *const *srcs, int32_t out_cformat, uint32_t extfmt,
+                                      void *const *y_planes, int32_t y_pitch, void *const *uv_planes, int32_t uv_pitch,
+                                      uint32_t *hist_dev /* n rows of 1024 words, frame i at hist_dev + 1024 i */);
 
 /* Multi-GPU: the parameter blob (colour matrix, luminance scale, gamut matrix, resize phase weights,
  * dither table) a rank-0 context computes and every other rank adopts after an RCCL broadcast.

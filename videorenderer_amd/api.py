@@ -144,6 +144,13 @@ class DoviMetadata(C.Structure):       # mpcvr_dovi_metadata
         return st
 
 
+HIST_BINS = 1024
+
+
+class LightLevel(C.Structure):         # mpcvr_light_level
+    _fields_ = [("pixels", C.c_uint64), ("min_code", C.c_int32), ("max_code", C.c_int32), ("max_nits", C.c_double), ("avg_nits", C.c_double)]
+
+
 class MpcvrError(RuntimeError):
     def __init__(self, hr, msg):
         super().__init__(f"HRESULT 0x{hr & 0xffffffff:08X}: {msg}")
@@ -166,6 +173,8 @@ EXPORTS = [
     "mpcvr_eval_transcendental", "mpcvr_eval_transcendental_host", "mpcvr_bandwidth_probe_up2x", "mpcvr_eval_dovi_tail",
     "mpcvr_plan_encode", "mpcvr_encode_pass", "mpcvr_render_yuv",
     "mpcvr_plan_batch_yuv", "mpcvr_set_batch_yuv_budget", "mpcvr_process_batch_yuv",
+    "mpcvr_measure_pass", "mpcvr_measure_backbuffer", "mpcvr_process_batch_yuv_stats",
+    "mpcvr_light_level_from_histogram", "mpcvr_histogram_percentile",
 ]
 
 _lib = None
@@ -267,6 +276,11 @@ def load_library():
         "mpcvr_plan_batch_yuv": [i32, i32, i32, C.c_size_t, P(i32), P(C.c_size_t), P(i32), P(i32)],
         "mpcvr_set_batch_yuv_budget": [vp, C.c_size_t],
         "mpcvr_process_batch_yuv": [vp, i32, P(vp), i32, u32, P(vp), i32, P(vp), i32],
+        "mpcvr_measure_pass": [vp, i32, i32, i32, i32, P(Rect), vp, vp],
+        "mpcvr_measure_backbuffer": [vp, vp],
+        "mpcvr_process_batch_yuv_stats": [vp, i32, P(vp), i32, u32, P(vp), i32, P(vp), i32, vp],
+        "mpcvr_light_level_from_histogram": [vp, i32, P(LightLevel)],
+        "mpcvr_histogram_percentile": [vp, u32, P(i32)],
     }
     for name, args in sig.items():
         if lib_path != LIB_PATH and not hasattr(L, name):
@@ -384,6 +398,46 @@ def encode_pass(src, src_pitch, src_fmt, w, h, out_cformat, extfmt, y_plane, y_p
                                           C.c_void_p(stream) if stream else None)
     if hr:
         raise MpcvrError(hr, "mpcvr_encode_pass")
+
+
+def measure_pass(src, src_pitch, src_fmt, w, h, hist, rect=None, stream=None):
+    """(extension) The histogram of max(R, G, B) over `rect` = (left, top, right, bottom) (None: the whole surface) of one device surface of
+    32-bit RGB texels (src_fmt: 0 = BGRA8, 1 = RGB10A2) into the 1024 uint32 words at `hist` (device tensor or address), which it overwrites
+    (include/mpcvr.h: mpcvr_measure_pass).  Complete in stream order."""
+    r = Rect(*[int(v) for v in rect]) if rect is not None else None
+    hr = load_library().mpcvr_measure_pass(C.c_void_p(_ptr(src)), int(src_pitch), int(src_fmt), int(w), int(h), C.byref(r) if r is not None else None,
+                                           C.c_void_p(_ptr(hist)), C.c_void_p(stream) if stream else None)
+    if hr:
+        raise MpcvrError(hr, "mpcvr_measure_pass")
+
+
+def _host_hist(hist):
+    import numpy as np
+    h = np.ascontiguousarray(hist, dtype=np.uint32).reshape(-1)
+    if h.size != HIST_BINS:
+        raise ValueError("a histogram has %d bins" % HIST_BINS)
+    return h
+
+
+def light_level_from_histogram(hist, src_fmt):
+    """(extension) dict(pixels, min_code, max_code, max_nits, avg_nits) of a host histogram (include/mpcvr.h: mpcvr_light_level_from_histogram).
+    The nits mean something for a PQ surface only; MaxCLL / MaxFALL of a stream are the maxima of max_nits / avg_nits over its frames.  No GPU needed."""
+    h = _host_hist(hist)
+    out = LightLevel()
+    hr = load_library().mpcvr_light_level_from_histogram(C.c_void_p(h.ctypes.data), int(src_fmt), C.byref(out))
+    if hr:
+        raise MpcvrError(hr, "mpcvr_light_level_from_histogram")
+    return dict(pixels=out.pixels, min_code=out.min_code, max_code=out.max_code, max_nits=out.max_nits, avg_nits=out.avg_nits)
+
+
+def histogram_percentile(hist, ppm):
+    """(extension) The smallest code whose cumulative count reaches ceil(ppm * pixels / 10^6) (include/mpcvr.h: mpcvr_histogram_percentile).  No GPU needed."""
+    h = _host_hist(hist)
+    code = C.c_int32()
+    hr = load_library().mpcvr_histogram_percentile(C.c_void_p(h.ctypes.data), int(ppm), C.byref(code))
+    if hr:
+        raise MpcvrError(hr, "mpcvr_histogram_percentile")
+    return code.value
 
 
 def plan_batch_yuv(window_w, window_h, n, budget_bytes=0):
@@ -676,6 +730,16 @@ class VideoProcessor:
             y, uv = y[:, :ww], uv[:, :ww]
         return y, uv
 
+    def MeasureBackBuffer(self, hist=None):
+        """(extension) The histogram of max(R, G, B) of the frame the last Render / RenderYuv left, over video rect ∩ window
+        (mpcvr_measure_backbuffer): a device tensor of 1024 int32 words holding the uint32 counts (allocated when `hist` is None), complete
+        after Synchronize; None when nothing has been rendered yet."""
+        import torch
+        if hist is None:
+            hist = torch.empty(HIST_BINS, dtype=torch.int32, device=f"cuda:{self.device}")
+        hr = self._check(self._L.mpcvr_measure_backbuffer(self._ctx, C.c_void_p(_ptr(hist))))
+        return None if hr == S_FALSE else hist
+
     def GetBackBuffer(self):
         p, pitch, w, h = C.c_void_p(), C.c_int32(), C.c_int32(), C.c_int32()
         self._check(self._L.mpcvr_get_backbuffer(self._ctx, C.byref(p), C.byref(pitch), C.byref(w), C.byref(h)))
@@ -719,6 +783,17 @@ class VideoProcessor:
         keep = (arr(*[_ptr(s) for s in srcs]), arr(*[_ptr(p) for p in y_planes]), arr(*[_ptr(p) for p in uv_planes]), (srcs, y_planes, uv_planes))
         self._keep = keep
         return self._check(self._L.mpcvr_process_batch_yuv(self._ctx, n, keep[0], int(out_cformat), int(extfmt), keep[1], int(y_pitch), keep[2], int(uv_pitch)))
+
+    def ProcessBatchYuvStats(self, srcs, out_cformat, extfmt, y_planes, y_pitch, uv_planes, uv_pitch, hist):
+        """(extension) ProcessBatchYuv plus one histogram of max(R, G, B) per frame over video rect ∩ window (mpcvr_process_batch_yuv_stats):
+        `hist` is a device tensor or address of len(srcs) rows of 1024 uint32 words; complete after Synchronize."""
+        n = len(srcs)
+        assert n == len(y_planes) == len(uv_planes) and n > 0
+        arr = C.c_void_p * n
+        keep = (arr(*[_ptr(s) for s in srcs]), arr(*[_ptr(p) for p in y_planes]), arr(*[_ptr(p) for p in uv_planes]), (srcs, y_planes, uv_planes, hist))
+        self._keep = keep
+        return self._check(self._L.mpcvr_process_batch_yuv_stats(self._ctx, n, keep[0], int(out_cformat), int(extfmt), keep[1], int(y_pitch), keep[2],
+                                                                 int(uv_pitch), C.c_void_p(_ptr(hist))))
 
     def ProcessBatchDovi(self, srcs, dsts, rt_pitch, rpus):
         """ProcessBatch with one Dolby Vision RPU per frame (mpcvr_process_batch_dovi): rpus[i] is a DoviMetadata or the dict

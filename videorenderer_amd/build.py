@@ -45,6 +45,7 @@ SOURCES = [
     ("vp_fused_jinc.hip", []),
     ("vp_errdiff.hip", []),
     ("vp_encode.hip", []),
+    ("vp_measure.hip", []),
     ("vp_probe.hip", []),
 ]
 

@@ -1756,14 +1756,87 @@ HRESULT CHipVideoProcessor::RenderYuv(int /*field*/, int outCformat, uint32_t ex
     return hr ? Fail(hr, why) : MPCVR_S_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// EXTENSION — measuring a rendered frame: the histogram of max(R, G, B) (include/mpcvr.h: mpcvr_measure_pass, mpcvr_measure_backbuffer;
+// kernel: vp_measure.hip).  No reference line: the reference's statistics are an overlay.
+// ------------------------------------------------------------------------------------------------
+HRESULT MeasureSurface(const void *src, int srcPitch, int srcFmt, int w, int h, const mpcvr_rect *rect, uint32_t *histDev, hipStream_t stream,
+                       bool checkOnly, const char **why)
+{
+    const char *dummy;
+    if (!why) why = &dummy;
+    if (!src || !histDev) { *why = "null surface or histogram"; return MPCVR_E_POINTER; }
+    if (srcFmt != MPCVR_OUT_BGRA8 && srcFmt != MPCVR_OUT_RGB10A2) { *why = "source BGRA8 or RGB10A2"; return MPCVR_E_INVALIDARG; }
+    if (w < 1 || h < 1 || w > 32768 || h > 32768) { *why = "width and height must be 1 .. 32768"; return MPCVR_E_INVALIDARG; }
+    if (srcPitch < 4 * w) { *why = "pitch smaller than a row"; return MPCVR_E_INVALIDARG; }
+    if (((uintptr_t)src | (uintptr_t)histDev | (uintptr_t)srcPitch) & 3) { *why = "surface, pitch and histogram must be multiples of 4"; return MPCVR_E_INVALIDARG; }
+    const mpcvr_rect whole{0, 0, w, h};
+    const mpcvr_rect r = rect ? *rect : whole;
+    if (r.left < 0 || r.top < 0 || r.right > w || r.bottom > h || r.left >= r.right || r.top >= r.bottom) {
+        *why = "the rectangle is empty or leaves the surface"; return MPCVR_E_INVALIDARG;
+    }
+    // the surface counts as the bytes from its first pixel to the last pixel of its last row
+    const uintptr_t s0 = (uintptr_t)src, s1 = s0 + (size_t)(h - 1) * srcPitch + (size_t)4 * w;
+    const uintptr_t h0 = (uintptr_t)histDev, h1 = h0 + sizeof(uint32_t) * kHistBins;
+    if (h0 < s1 && s0 < h1) { *why = "the histogram overlaps the surface"; return MPCVR_E_INVALIDARG; }
+    if (checkOnly) return MPCVR_S_OK;
+    MeasureParams p{};
+    p.src = (const uint8_t *)src; p.src_pitch = srcPitch;
+    p.hist = histDev;
+    p.w = w;
+    p.left = r.left; p.top = r.top; p.right = r.right; p.bottom = r.bottom;
+    p.src16 = ((s0 | (uintptr_t)srcPitch) & 15) == 0;
+    if (LaunchMeasure(p, srcFmt == MPCVR_OUT_RGB10A2, stream) != hipSuccess) { *why = "k_measure_maxrgb launch failed"; return MPCVR_E_FAIL; }
+    return MPCVR_S_OK;
+}
+
+CRect CHipVideoProcessor::ActiveRect() const
+{
+    CRect a(std::max(m_videoRect.left, 0), std::max(m_videoRect.top, 0), std::min(m_videoRect.right, m_windowRect.Width()),
+            std::min(m_videoRect.bottom, m_windowRect.Height()));
+    if (a.right <= a.left || a.bottom <= a.top) a = CRect();
+    return a;
+}
+
+// The pass over the back buffer as the last Render / RenderYuv left it.  It READS memory the frame lanes may still be writing and a later
+// Render on a lane may overwrite, and the lanes order writers only — so, as RenderYuv: behind the lanes on the context stream
+// (OrderOnContextStream), and everything queued later, lanes included, behind the pass (NoteStreamWork).
+HRESULT CHipVideoProcessor::MeasureBackBuffer(uint32_t *histDev)
+{
+    if (!m_bInit || !m_srcParams) return Fail(MPCVR_E_NOT_VALID_STATE, "InitMediaType has not been called");
+    if (!histDev) return Fail(MPCVR_E_POINTER, "null histogram");
+    const int w = m_windowRect.Width(), h = m_windowRect.Height();
+    // no frame yet, or none of this window's size and format (the back buffer is addressed by the window)
+    if (!m_BackBuffer.ptr || m_backW != w || m_backH != h || m_backFmt != m_cfg.output_format || w < 1 || h < 1) return MPCVR_S_FALSE;
+    (void)hipSetDevice(m_device);
+    const CRect a = ActiveRect();
+    const bool empty = a.IsRectNull();
+    const mpcvr_rect r{a.left, a.top, a.right, a.bottom};
+    const char *why = "";
+    HRESULT hr;
+    // (an empty active area: the checks run against the whole window, then only the clear is queued)
+    if ((hr = MeasureSurface(m_BackBuffer.ptr, w * 4, m_backFmt, w, h, empty ? nullptr : &r, histDev, nullptr, true, &why))) return Fail(hr, why);
+    OrderOnContextStream();
+    if (empty) hr = CheckHip(hipMemsetAsync(histDev, 0, sizeof(uint32_t) * kHistBins, m_stream), "clear histogram");
+    else {
+        hr = MeasureSurface(m_BackBuffer.ptr, w * 4, m_backFmt, w, h, &r, histDev, m_stream, false, &why);
+        if (hr) hr = Fail(hr, why); else m_launches++;
+    }
+    m_lanes.NoteStreamWork();
+    return hr;
+}
+
 // A batch as NV12 / P010 (include/mpcvr.h: mpcvr_process_batch_yuv).  Everything about the arguments is answered first; then the call is cut
 // into chunks of PlanBatchYuv's size, and each chunk is: the batch machinery into frames of a context-owned surface, ONE k_encode420 launch
 // with a frame dimension behind it on the same stream.  A chunk whose route may take a batch lane (BatchLaneEligible) takes the next lane in
 // turn and that lane's own surface — the lane's stream order covers the surface's write, read and reuse, and the render of the next chunk
 // runs beside this one's pass on the other lane; the lanes order the chunk on the bytes it WRITES for the caller, its planes.  Every other
 // chunk runs on the context stream into the first surface, behind whatever the lanes hold (OrderOnContextStream), the lanes' next work behind it.
+// With histograms (mpcvr_process_batch_yuv_stats): ONE k_measure_maxrgb launch behind the chunk's pass on the same stream, its frame dimension
+// over the chunk's frames in the surface (they sit at frameStride: a base, a stride and the chunk's first row are all it needs).  The rows
+// are one more span the chunk writes for the caller: the lanes order on them as on the planes.
 HRESULT CHipVideoProcessor::ProcessBatchYuv(int n, const void *const *srcs, int outCformat, uint32_t extfmt, void *const *yPlanes, int yPitch,
-                                            void *const *uvPlanes, int uvPitch)
+                                            void *const *uvPlanes, int uvPitch, uint32_t *histDev)
 {
     m_lastBatchFrames = n > 0 ? n : 0; m_lastBatchLaunches = m_lastBatchUploads = 0; m_lastBatchLane = -1; m_lastBatchWaits = 0;
     m_dvLastInfo.clear(); m_yuvLastInfo.clear();
@@ -1772,6 +1845,7 @@ HRESULT CHipVideoProcessor::ProcessBatchYuv(int n, const void *const *srcs, int 
     if (!srcs || !yPlanes || !uvPlanes) return Fail(MPCVR_E_POINTER, "null array of frames or planes");
     for (int i = 0; i < n; i++)
         if (!srcs[i] || !yPlanes[i] || !uvPlanes[i]) return Fail(MPCVR_E_POINTER, "null frame or plane in batch");
+    if ((uintptr_t)histDev & 3) return Fail(MPCVR_E_INVALIDARG, "the histogram must be 4-byte aligned");
     const int w = m_windowRect.Width(), h = m_windowRect.Height();
     BatchYuvLayout lay;
     if (!PlanBatchYuv(w, h, n, m_yuvBudget, &lay)) return Fail(MPCVR_E_INVALIDARG, "a 4:2:0 frame needs an even window width and height, 2 .. 32768");
@@ -1786,6 +1860,12 @@ HRESULT CHipVideoProcessor::ProcessBatchYuv(int n, const void *const *srcs, int 
     const size_t rowBytes = plan.out10 ? (size_t)2 * w : (size_t)w;
     const std::vector<RtSpan> planes = BatchPlaneSpans(n, yPlanes, yPitch, uvPlanes, uvPitch, h, rowBytes);
     if (AnyTwoSpansOverlap(planes)) return Fail(MPCVR_E_INVALIDARG, "two planes of the batch overlap");
+    constexpr size_t kHistRow = sizeof(uint32_t) * kHistBins;
+    if (histDev) {
+        const RtSpan rows{(uintptr_t)histDev, (uintptr_t)histDev + kHistRow * (size_t)n};
+        for (const RtSpan &pl : planes)
+            if (pl.Overlaps(rows)) return Fail(MPCVR_E_INVALIDARG, "the histogram rows overlap a plane of the batch");
+    }
 
     const unsigned before = m_launches, uploadsBefore = m_tableUploads;
     (void)hipSetDevice(m_device);
@@ -1820,7 +1900,9 @@ HRESULT CHipVideoProcessor::ProcessBatchYuv(int n, const void *const *srcs, int 
             rp = ClassifyBatch(run);
             if (BatchLaneEligible(rp, run)) {
                 int waits = 0;
-                bl = m_lanes.PickBatchLane(std::vector<RtSpan>(planes.begin() + 2 * (size_t)at, planes.begin() + 2 * (size_t)(at + m)), &waits);
+                std::vector<RtSpan> writes(planes.begin() + 2 * (size_t)at, planes.begin() + 2 * (size_t)(at + m));
+                if (histDev) writes.push_back(RtSpan{(uintptr_t)histDev + kHistRow * (size_t)at, (uintptr_t)histDev + kHistRow * (size_t)(at + m)});
+                bl = m_lanes.PickBatchLane(std::move(writes), &waits);
                 m_lastBatchWaits += waits;
                 if (bl > 0) {                           // another lane, another surface: the route is planned for the targets it draws into
                     surf = &m_yuvSurf[bl];
@@ -1835,7 +1917,7 @@ HRESULT CHipVideoProcessor::ProcessBatchYuv(int n, const void *const *srcs, int 
             m_lanes.LaneWaitsForStream(bl, m_stream);
         } else OrderOnContextStream();
         if (chunks < 64) lanes += (chunks ? "," : "") + std::to_string(bl);
-        hr = RunYuvChunk(rp, run, *surf, ep, plan, yPlanes + at, uvPlanes + at);
+        hr = RunYuvChunk(rp, run, *surf, ep, plan, yPlanes + at, uvPlanes + at, histDev ? histDev + (size_t)kHistBins * (size_t)at : nullptr);
         if (bl >= 0) m_lanes.NoteLaneBatch(bl); else m_lanes.NoteStreamWork();
     }
     m_lastBatchLaunches = (int)(m_launches - before);
@@ -1845,7 +1927,7 @@ HRESULT CHipVideoProcessor::ProcessBatchYuv(int n, const void *const *srcs, int 
 }
 
 HRESULT CHipVideoProcessor::RunYuvChunk(BatchRoutePlan &rp, BatchRun &run, YuvSurface &surf, const EncodeParams &encode,
-                                        const EncodePlan &plan, void *const *yPlanes, void *const *uvPlanes)
+                                        const EncodePlan &plan, void *const *yPlanes, void *const *uvPlanes, uint32_t *histRows)
 {
     hipStream_t const stream = run.on.stream;
     HRESULT hr;
@@ -1872,7 +1954,20 @@ HRESULT CHipVideoProcessor::RunYuvChunk(BatchRoutePlan &rp, BatchRun &run, YuvSu
     EncodeParams ep = encode;
     ep.frames = (const EncodeFrame *)table.dev;
     ep.dst8 = (bits & 7) == 0;                          // the 8-byte stores only if every plane of the launch allows them
-    return CheckHip(LaunchEncode420(ep, plan.in10, plan.out10, plan.siting, stream, run.n), "k_encode420");
+    if ((hr = CheckHip(LaunchEncode420(ep, plan.in10, plan.out10, plan.siting, stream, run.n), "k_encode420")) || !histRows) return hr;
+    // the chunk's histograms: the frames of the surface are run.dsts[0] + i * frame stride (ProcessBatchYuv lays them out so)
+    const CRect a = ActiveRect();
+    MeasureParams mp{};
+    mp.src = (const uint8_t *)run.dsts[0]; mp.src_pitch = encode.src_pitch;
+    mp.frame_stride = run.n > 1 ? (size_t)((const uint8_t *)run.dsts[1] - (const uint8_t *)run.dsts[0]) : 0;
+    mp.hist = histRows;
+    mp.w = encode.w;
+    mp.left = a.left; mp.top = a.top; mp.right = a.right; mp.bottom = a.bottom;
+    mp.src16 = 1;                                       // as the pass above: frames on 256 bytes, the pitch a multiple of 16
+    int launched = 0;
+    const hipError_t e = LaunchMeasure(mp, plan.in10, stream, run.n, &launched);
+    // (counted as the kernel launches it was: none for an empty active area, whose rows are only cleared)
+    return launched ? CheckHip(e, "k_measure_maxrgb") : CheckHip(e, "clear histogram rows");
 }
 
 HRESULT CHipVideoProcessor::GetBackBuffer(void **ptr, int *pitch, int *w, int *h)

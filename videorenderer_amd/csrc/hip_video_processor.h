@@ -12,6 +12,7 @@
 #include "../../include/mpcvr.h"
 #include "vp_encode.h"
 #include "vp_lanes.h"
+#include "vp_measure.h"
 #include "vp_launch.h"
 #include "vp_params.h"
 #include "vp_plan.h"
@@ -46,6 +47,11 @@ struct DevBuffer {
 HRESULT EncodeSurface(const void *src, int srcPitch, int srcFmt, int w, int h, int outCformat, uint32_t extfmt, void *yPlane, int yPitch,
                       void *uvPlane, int uvPitch, hipStream_t stream, bool checkOnly, const char **why = nullptr);
 
+// EXTENSION (mpcvr_measure_pass, include/mpcvr.h): checks every argument, then — unless checkOnly — clears the histogram and launches
+// k_measure_maxrgb on `stream`.  rect = nullptr: the whole surface.  MPCVR_E_POINTER / MPCVR_E_INVALIDARG with nothing launched or written
+HRESULT MeasureSurface(const void *src, int srcPitch, int srcFmt, int w, int h, const mpcvr_rect *rect, uint32_t *histDev, hipStream_t stream,
+                       bool checkOnly, const char **why = nullptr);
+
 class CHipVideoProcessor {
 public:
     CHipVideoProcessor();
@@ -75,13 +81,17 @@ public:
     HRESULT Render(int field) { return RenderBackBuffer(false); }             // :2599 minus Present
     // EXTENSION (mpcvr_render_yuv): Render, then the back buffer written as NV12 / P010 (vp_encode.h) behind it in stream order
     HRESULT RenderYuv(int field, int outCformat, uint32_t extfmt, void *yPlane, int yPitch, void *uvPlane, int uvPitch);
+    // EXTENSION (mpcvr_measure_backbuffer): the histogram of the last rendered frame over video rect ∩ window, on the context stream
+    HRESULT MeasureBackBuffer(uint32_t *histDev);
     HRESULT GetBackBuffer(void **ptr, int *pitch, int *w, int *h);
     HRESULT GetCurentImage(void *hostBGRA, size_t *size);                     // :3493
     HRESULT GetDisplayedImage(void *hostPixels, size_t *size, bool deepColor, int *width, int *height, int *bits);     // :3610
     HRESULT ProcessBatch(int n, const void *const *srcs, void *const *dsts, int rtPitch);
     // EXTENSION (mpcvr_process_batch_yuv): the batch in chunks through the batch machinery into a context-owned RGB surface, one k_encode420
     // launch (its frame dimension) behind each chunk on the same stream — the context stream, or a batch lane with a surface of its own
-    HRESULT ProcessBatchYuv(int n, const void *const *srcs, int outCformat, uint32_t extfmt, void *const *yPlanes, int yPitch, void *const *uvPlanes, int uvPitch);
+    // histDev (mpcvr_process_batch_yuv_stats; nullptr: none): n rows of kHistBins words, one k_measure_maxrgb launch behind each chunk's pass
+    HRESULT ProcessBatchYuv(int n, const void *const *srcs, int outCformat, uint32_t extfmt, void *const *yPlanes, int yPitch, void *const *uvPlanes, int uvPitch,
+                            uint32_t *histDev = nullptr);
     HRESULT SetBatchYuvBudget(size_t bytes) { m_yuvBudget = bytes; return MPCVR_S_OK; }
     std::string GetLastBatchInfo() const;
     HRESULT ProcessBatchDovi(int n, const void *const *srcs, void *const *dsts, int rtPitch, const mpcvr_dovi_metadata *rpus);
@@ -395,7 +405,9 @@ private:
     std::string m_yuvLastInfo;         // ";yuv_chunks=..;yuv_lanes=.." of the last batch call, if it was a ProcessBatchYuv
     // one chunk: rp / run.dsts name the surface's frames, run.on the stream; `encode` holds the launch's pitches, size and coefficients
     HRESULT RunYuvChunk(BatchRoutePlan &rp, BatchRun &run, YuvSurface &surf, const EncodeParams &encode, const EncodePlan &plan,
-                        void *const *yPlanes, void *const *uvPlanes);
+                        void *const *yPlanes, void *const *uvPlanes, uint32_t *histRows);
+    // video rect ∩ window: the active picture the measure pass counts (may be empty)
+    CRect ActiveRect() const;
     HRESULT RunBatchRoute(BatchRoutePlan &rp, BatchRun &run);
     bool BatchPlan(const uint8_t *sample0, void *rt0, int rtPitch, bool aligned, bool repacked, bool src16, FusedParams *conv, FusedParams *direct) const;
     HRESULT ProcessBatchLaunches(const BatchRun &run, const FusedFrame *table, bool aligned, FusedParams conv);

@@ -190,6 +190,43 @@ int32_t mpcvr_process_batch_yuv(mpcvr_ctx *ctx, int32_t n, const void *const *sr
     return ctx->vp.ProcessBatchYuv(n, srcs, out_cformat, extfmt, y_planes, y_pitch, uv_planes, uv_pitch);
 }
 
+// EXTENSION: the histogram of max(R, G, B) of rendered frames and what a host derives from it (include/mpcvr.h; k_measure_maxrgb
+// vp_measure.hip, MeasureSurface hip_video_processor.cpp, the host functions vp_plan.cpp)
+static_assert(MPCVR_HIST_BINS == mpcvr::kHistBins, "the header and vp_measure.h name one histogram size");
+int32_t mpcvr_process_batch_yuv_stats(mpcvr_ctx *ctx, int32_t n, const void *const *srcs, int32_t out_cformat, uint32_t extfmt,
+                                      void *const *y_planes, int32_t y_pitch, void *const *uv_planes, int32_t uv_pitch, uint32_t *hist_dev)
+{
+    CTX_OR_FAIL();
+    if (!hist_dev) return MPCVR_E_POINTER;
+    return ctx->vp.ProcessBatchYuv(n, srcs, out_cformat, extfmt, y_planes, y_pitch, uv_planes, uv_pitch, hist_dev);
+}
+
+int32_t mpcvr_measure_pass(const void *src, int32_t src_pitch, int32_t src_fmt, int32_t w, int32_t h, const mpcvr_rect *rect, uint32_t *hist_dev,
+                           void *stream)
+{
+    return mpcvr::MeasureSurface(src, src_pitch, src_fmt, w, h, rect, hist_dev, (hipStream_t)stream, false);
+}
+
+int32_t mpcvr_measure_backbuffer(mpcvr_ctx *ctx, uint32_t *hist_dev) { CTX_OR_FAIL(); return ctx->vp.MeasureBackBuffer(hist_dev); }
+
+int32_t mpcvr_light_level_from_histogram(const uint32_t hist[MPCVR_HIST_BINS], int32_t src_fmt, mpcvr_light_level *out)
+{
+    if (!hist || !out) return MPCVR_E_POINTER;
+    if (src_fmt != MPCVR_OUT_BGRA8 && src_fmt != MPCVR_OUT_RGB10A2) return MPCVR_E_INVALIDARG;
+    mpcvr::LightLevelFromHistogram(hist, src_fmt == MPCVR_OUT_RGB10A2 ? 1023 : 255, out);
+    return MPCVR_S_OK;
+}
+
+int32_t mpcvr_histogram_percentile(const uint32_t hist[MPCVR_HIST_BINS], uint32_t ppm, int32_t *code)
+{
+    if (!hist || !code) return MPCVR_E_POINTER;
+    if (ppm < 1 || ppm > 1000000) return MPCVR_E_INVALIDARG;
+    const int c = mpcvr::HistogramPercentile(hist, ppm);
+    if (c < 0) return MPCVR_E_INVALIDARG;
+    *code = c;
+    return MPCVR_S_OK;
+}
+
 int32_t mpcvr_get_param_blob(mpcvr_ctx *ctx, void *buf, size_t *size) { CTX_OR_FAIL(); return ctx->vp.GetParamBlob(buf, size); }
 int32_t mpcvr_get_fused_tables(mpcvr_ctx *ctx, void *buf, size_t *size) { CTX_OR_FAIL(); return ctx->vp.GetFusedTables(buf, size); }
 int32_t mpcvr_set_param_blob(mpcvr_ctx *ctx, const void *buf, size_t size) { CTX_OR_FAIL(); return ctx->vp.SetParamBlob(buf, size); }

@@ -8,6 +8,7 @@
 
 #include "../../include/mpcvr.h"
 #include "vp_encode.h"
+#include "vp_measure.h"
 #include "vp_crmath.h"      // the shaders' sin / cos as defined functions (the weights the resize shaders compute per pixel are computed here, once)
 
 namespace mpcvr {
@@ -233,6 +234,51 @@ bool PlanBatchYuv(int w, int h, int n, size_t budget, BatchYuvLayout *out)
     out->framesPerChunk = (int32_t)(fit < 1 ? 1 : fit > (size_t)n ? (size_t)n : fit);
     out->chunks = (n + out->framesPerChunk - 1) / out->framesPerChunk;
     return true;
+}
+
+// ------------------------------------------------------------------------------------------------
+// EXTENSION — what a host derives from a histogram of max(R, G, B) (include/mpcvr.h: mpcvr_light_level_from_histogram,
+// mpcvr_histogram_percentile; the histogram itself: vp_measure.hip).  No reference line: the reference's statistics are an overlay.
+// ------------------------------------------------------------------------------------------------
+double PqCodeToNits(int code, int maxin)
+{
+    // ST2084ToLinear of Shaders/convert/st2084.hlsl in double; every constant is exact in binary
+    const double m1 = 2610.0 / (4096.0 * 4.0), m2 = (2523.0 / 4096.0) * 128.0;
+    const double c1 = 3424.0 / 4096.0, c2 = (2413.0 / 4096.0) * 32.0, c3 = (2392.0 / 4096.0) * 32.0;
+    const double v = std::pow((double)code / (double)maxin, 1.0 / m2);
+    return 10000.0 * std::pow(std::max(v - c1, 0.0) / (c2 - c3 * v), 1.0 / m1);
+}
+
+void LightLevelFromHistogram(const uint32_t *hist, int maxin, ::mpcvr_light_level *out)
+{
+    uint64_t pixels = 0;
+    int lo = -1, hi = -1;
+    double sum = 0.0;
+    for (int c = 0; c < kHistBins; c++) {              // ascending: the order of the definition's sum
+        if (!hist[c]) continue;
+        if (lo < 0) lo = c;
+        hi = c;
+        pixels += hist[c];
+        sum += (double)hist[c] * PqCodeToNits(c, maxin);
+    }
+    out->pixels = pixels; out->min_code = lo; out->max_code = hi;
+    out->max_nits = hi >= 0 ? PqCodeToNits(hi, maxin) : 0.0;
+    out->avg_nits = pixels ? sum / (double)pixels : 0.0;
+}
+
+int HistogramPercentile(const uint32_t *hist, uint32_t ppm)
+{
+    uint64_t pixels = 0;
+    for (int c = 0; c < kHistBins; c++) pixels += hist[c];
+    if (!pixels) return -1;
+    // pixels <= 1024 * (2^32 - 1) and ppm <= 10^6: the product stays below 2^62
+    const uint64_t need = ((uint64_t)ppm * pixels + 999999u) / 1000000u;
+    uint64_t run = 0;
+    for (int c = 0; c < kHistBins; c++) {
+        run += hist[c];
+        if (run >= need) return c;
+    }
+    return kHistBins - 1;
 }
 
 bool PlanEncode(int out_cformat, int src_fmt, uint32_t extfmt, int w, int h, EncodePlan *plan)
