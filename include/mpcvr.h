@@ -162,6 +162,10 @@ int32_t mpcvr_synchronize(mpcvr_ctx *ctx);
  *   anything.  For the interleaved RGB formats the pitch, not the width, drives the reference's copy loops (Helper.cpp:446-482, 541-565):
  *   RGB48 fills whole groups of four texels of |pitch| / 6 and RGB24 one texel of a remainder of three of |pitch| / 3, so the last texels of
  *   a row whose width is no multiple of 4 are black or filled depending on the pitch — as in the reference;
+ *   Any legal pitch up to INT32_MAX is rendered correctly — a small frame carved out of a large pooled surface may have rows tens of MiB
+ *   apart.  The fused kernels address rows and chroma planes with 32-bit offsets and step aside (mpcvr_get_path_info says what ran) where a
+ *   chroma plane — or, for formats with fewer than three planes, the sum pitch * height + chroma pitch * chroma rows the library forms all
+ *   the same — starts at or beyond 2 GiB, or the rows read span 4 GiB; the convert kernel and the resize draws take such a sample;
  * src_rect: rcSource (NULL or empty => whole frame, :1821-1823);
  * extfmt: DXVA2_ExtendedFormat.value from the media type (0 fields are defaulted per
  * SpecifyExtendedFormat, Helper.cpp:1169-1211).  Returns S_OK, or E_INVALIDARG/E_NOTIMPL. */
@@ -383,8 +387,11 @@ int32_t mpcvr_copy_sample(mpcvr_ctx *ctx, const void *data, int32_t pitch, int32
  * window's pixels: the bytes between window_w * 4 and dst_pitch of a row, and everything in front of and behind the target.
  * A render target is made of dwords: dst_dev and dst_pitch must be multiples of 4 (any multiple: a sub-allocated, pitch-padded
  * surface is served; the 8- and 16-byte stores are taken where target and pitch allow them).  MPCVR_E_INVALIDARG otherwise, with
- * nothing launched and the target untouched.  The same holds for every dsts[i] / dst_pitch of mpcvr_process_frames,
- * mpcvr_process_batch and mpcvr_process_batch_dovi. */
+ * nothing launched and the target untouched.  Any such dst_pitch up to INT32_MAX is rendered correctly, with the same pixels: the fused
+ * kernels address target rows with 32-bit offsets and step aside, per call, where dst_pitch * (max(dst_rect top, 0) + dst_rect height)
+ * reaches 4 GiB — the convert kernel and the resize draws then write the frame, in stream order (such a frame takes no lane), and
+ * mpcvr_get_path_info, read after the call, names what ran.  The same holds for every dsts[i] / dst_pitch of mpcvr_process_frames,
+ * mpcvr_process_batch and mpcvr_process_batch_dovi (the targets of a batch may lie any distance apart). */
 int32_t mpcvr_process(mpcvr_ctx *ctx, void *dst_dev, int32_t dst_pitch, const mpcvr_rect *src_rect,
                       const mpcvr_rect *dst_rect, int32_t second_field);
 

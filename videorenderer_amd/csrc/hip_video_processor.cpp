@@ -527,6 +527,7 @@ HRESULT CHipVideoProcessor::UpdatePlan()
     // convert kernel -> m_TexConvertOutput -> k_fused_strip:surface
     m_stripSurf = false;
     m_stripRan = -1;
+    m_fusedAside = false;
     m_strip = m_tables.stripPlanned && m_plan.convert && !m_doviValid && m_plan.internal_fmt != SF_RGBA16F && m_plan.rotation == 0;
 
     // 6. the LUTs and the exact-2x kernel's baked image.  PQ -> SDR table: the fused kernel's tone-map stage and the folded convert kernel's
@@ -890,7 +891,9 @@ HRESULT CHipVideoProcessor::ResizeShaderPass(const uint8_t *sample, void *rt, in
     const bool plain = (m_cfg.flags & MPCVR_FLAG_NO_FUSED) != 0;      // keep the whole path on the one-kernel-fits-all versions
     const bool jfast = !(m_cfg.flags & (MPCVR_FLAG_NO_FUSED | MPCVR_FLAG_NO_FAST_CONVERT));       // Jinc2m quad kernel: default tier only
     FusedStripParams ssp{};
-    if (m_stripSurf && FillStripSurfParams(conv, last, &ssp)) {
+    const bool surfStrip = m_stripSurf && FillStripSurfParams(conv, last, &ssp);
+    if (m_stripSurf) m_fusedAside = !surfStrip;
+    if (surfStrip) {
         // convert output (or RGB source texture) -> both draws -> final pass in the arbitrary-ratio fused kernel, no convert stage
         ssp.surf_stride = df.convStride;
         if (df.lastTab) ssp.fp.dst_aligned16 = df.aligned;
@@ -979,11 +982,17 @@ bool CHipVideoProcessor::FillStripSurfParams(const Surface &src, const StorePara
 HRESULT CHipVideoProcessor::ProcessOne(const uint8_t *sample, void *rt, int rtPitch, const RunOn &on)
 {
     HRESULT hr;
+    m_fusedAside = false;
     if (m_plan.fused_up2x) {
         FusedParams fp{};
         FillFusedParams(sample, rt, rtPitch, &fp, on.inflight);
-        const FusedFrame fr{sample, rt};        // a single frame travels by value in the kernel arguments
-        return CheckHip(LaunchFusedUp2x(fp, nullptr, fr, 1, on.stream), "k_fused_up2x");
+        // UpdatePlan asked FusedUp2xSupported without a target (pitch 0): what depends on THIS call's target is asked here, as the strip and
+        // same-size routes below ask it — rows that span 4 GiB go to the convert kernel and the resize draws, which store through size_t
+        if (StoreRowsFit32(fp.store, fp.out_h)) {
+            const FusedFrame fr{sample, rt};        // a single frame travels by value in the kernel arguments
+            return CheckHip(LaunchFusedUp2x(fp, nullptr, fr, 1, on.stream), "k_fused_up2x");
+        }
+        m_fusedAside = true;
     }
     if (m_strip) {
         // with the HDR10 tone-mapping step the resize draws into the post-scale texture and the step writes the target (:3359-3367)
@@ -997,6 +1006,7 @@ HRESULT CHipVideoProcessor::ProcessOne(const uint8_t *sample, void *rt, int rtPi
             if (!m_plan.hdr_tonemap) return MPCVR_S_OK;
             return CheckHip(LaunchHdr10ToneMap(post, m_hdrTm, w2, h2, final, on.stream), "k_hdr10_tonemap");
         }
+        m_fusedAside = true;
     }
     if (m_plan.direct_convert) {
         FusedParams fp{};
@@ -1036,7 +1046,11 @@ HRESULT CHipVideoProcessor::ProcessFrame(void *pRenderTarget, int rtPitch, const
     if (rtPitch < m_windowRect.Width() * 4) return Fail(MPCVR_E_INVALIDARG, "render-target pitch smaller than a row");
     if (m_planDirty && (hr = UpdatePlan())) return hr;
     const RtSpan span = TargetSpan(pRenderTarget, rtPitch);
-    const int lane = (onContextStream || !FrameLanesUsable()) ? -1 : m_lanes.PickFrameLane(span);
+    // (where the target's rows span 4 GiB the fused kernels step aside — ProcessOne — and a resize then goes through the context's intermediates,
+    // which are shared: such a frame runs in stream order.  The same-size per-pixel convert shares nothing and would be safe on a lane; it stays
+    // off them too, so that one condition decides)
+    const bool rows32 = StoreRowsFit32(MakeStore(pRenderTarget, rtPitch, m_plan.swap_fmt, true), m_videoRect.Height());
+    const int lane = (onContextStream || !rows32 || !FrameLanesUsable()) ? -1 : m_lanes.PickFrameLane(span);
     // (on the lanes the kernels size their segments for that many frames side by side)
     const RunOn on{lane >= 0 ? m_lanes.Stream(lane) : m_stream, lane >= 0 ? FrameLanes::Count() : 1};
     if (lane >= 0) {
@@ -1164,11 +1178,14 @@ CHipVideoProcessor::BatchRoutePlan CHipVideoProcessor::ClassifyBatch(const Batch
     const StoreParams target = MakeStore(dsts[0], rtPitch, m_plan.swap_fmt, true);
     // the arbitrary-ratio fused kernel takes the whole batch in one launch, like the 2x kernel
     FusedStripParams sp{};
-    const bool strip = m_strip && !m_plan.fused_up2x && !m_plan.hdr_tonemap && rp.src4 && !run.dvFrames && FillStripParams(sample0, dsts[0], rtPitch, target, &sp);
+    // the exact-2x kernels were planned without a target (UpdatePlan): this batch's pitch has its say here, as in ProcessOne
+    const bool up2x = m_plan.fused_up2x && StoreRowsFit32(target, m_videoRect.Height());
+    const bool strip = m_strip && !up2x && !m_plan.hdr_tonemap && rp.src4 && !run.dvFrames && FillStripParams(sample0, dsts[0], rtPitch, target, &sp);
+    m_fusedAside = m_plan.fused_up2x ? !up2x : (m_strip && !m_plan.hdr_tonemap && !strip);       // (frame by frame: ProcessOne says it again per frame)
     // pass-per-kernel path, whole batch per launch: possible when every stage has a kernel with a frame dimension.  One RPU per frame
     // (ProcessBatchDovi): the block convert's Dolby Vision variants index the run's tables by the frame; the HDR10 tone-mapping step takes
     // its level-1 constants by value, so such a run goes frame by frame
-    const bool batchable = !m_plan.fused_up2x && !strip && n > 1 && rp.src4 && fast && !(run.dvFrames && (!run.dvTab || m_plan.hdr_tonemap)) &&
+    const bool batchable = !up2x && !strip && n > 1 && rp.src4 && fast && !(run.dvFrames && (!run.dvTab || m_plan.hdr_tonemap)) &&
                            BatchPlan(sample0, dsts[0], rtPitch, rp.aligned, rp.repackSlot != 0, rp.src16, &rp.conv, &rp.direct);
     auto take = [&rp](BatchRoute r) { rp.route = r; return rp; };
     if (batchable && m_plan.direct_convert) return take(BatchRoute::DirectConvert);
@@ -1177,7 +1194,7 @@ CHipVideoProcessor::BatchRoutePlan CHipVideoProcessor::ClassifyBatch(const Batch
         rp.strip = sp;
         return take(BatchRoute::RgbSurfaceStrip);
     }
-    if (m_plan.hdr_tonemap && m_strip && !m_plan.fused_up2x && rp.src4 && n > 1 && fastStrip) {
+    if (m_plan.hdr_tonemap && m_strip && !up2x && rp.src4 && n > 1 && fastStrip) {
         const int postPitch = (int)(m_videoRect.Width() * SurfBytesPerPixel(m_plan.internal_fmt));
         if (FillStripParams(sample0, nullptr, postPitch, MakeStore(nullptr, postPitch, m_plan.internal_fmt, false), &sp)) {
             rp.strip = sp;
@@ -1185,7 +1202,7 @@ CHipVideoProcessor::BatchRoutePlan CHipVideoProcessor::ClassifyBatch(const Batch
         }
     }
     // (a batch of one needs no frame table: the frame travels in the kernel arguments, like mpcvr_process)
-    if ((!m_plan.fused_up2x && !strip && !batchable) || !rp.src4 || n == 1) return take(BatchRoute::FrameByFrame);
+    if ((!up2x && !strip && !batchable) || !rp.src4 || n == 1) return take(BatchRoute::FrameByFrame);
     if (batchable) return take(BatchRoute::WholeBatchLaunches);
     if (strip) {
         rp.strip = sp;
@@ -2248,6 +2265,11 @@ std::string CHipVideoProcessor::GetPathInfo()
 {
     if (!m_srcParams) return "uninitialised";
     if (m_planDirty && UpdatePlan() != MPCVR_S_OK) return "error: " + m_lastError;
+    if (m_fusedAside) {     // the last frame / batch went past the plan's fused kernel (a per-call condition failed): what ran is the pass-per-kernel plan
+        PassPlan p = m_plan;
+        p.fused_up2x = p.fused_jinc = false;
+        return p.describe();
+    }
     if ((!m_strip && !m_stripSurf) || m_plan.fused_up2x) return m_plan.describe();
     if ((m_strip || m_stripSurf) && (m_stripRan >= 0 ? m_stripRan == 1 : m_period))
         return m_plan.describe() + (m_strip ? ";kernel=fused_period(rows=" : ";kernel=fused_period:surface(rows=") + std::to_string(m_tables.period.P) + ":" + std::to_string(m_tables.period.Q) + ",taps=" + std::to_string(m_tables.period.nt) + ",px_per_lane=2,strip=" + std::to_string(m_tables.period.strip_w) + ",window=6 rows in registers)";

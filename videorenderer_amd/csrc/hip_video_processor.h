@@ -380,6 +380,10 @@ private:
     // periodic-phase variant of the same launch (vp_fused_period.h): vertical ratio 4:3 / 3:2 / 2:3 / 1:2 / 3:1, tables behind the strip kernel's in m_stripTab (m_tables.period)
     mutable int m_stripRan = -1;   // which kernel the last strip launch of this plan really ran (1 = k_fused_period, 0 = k_fused_strip, -1 = none yet): the plan-time
                                    // probe uses a null, aligned target — a real target with an odd pitch or offset sends the launch to k_fused_strip (GetPathInfo reports what ran)
+    mutable bool m_fusedAside = false;   // the last frame / batch of this plan went past the fused kernel the plan names (exact-2x, strip / periodic): a condition
+                                   // asked per call failed — StoreRowsFit32 for the exact-2x kernels; for the strip kernels whatever FillStripParams /
+                                   // FillStripSurfParams refuse with this call's target (rows that span 4 GiB, the LDS the launch would need) — and the
+                                   // convert kernel + resize draws ran (GetPathInfo reports what ran)
     bool m_period = false;         // the planned launch (window-sized target) takes the periodic kernel: what GetVPInfo reports
     // the route of a mpcvr_process_batch call, in order of precedence (ClassifyBatch), and what its launches need
     enum class BatchRoute { DirectConvert, RgbSurfaceStrip, StripToneMap, FrameByFrame, WholeBatchLaunches, Strip, FusedUp2x };

@@ -427,7 +427,7 @@ bool FusedUp2xSupported(const FusedParams &P)
     // 32-bit row offsets inside the kernel
     if ((uint64_t)c.pitch[0] * (uint64_t)(c.rect_t + c.out_h + 2) >= (1ull << 32)) return false;
     if ((uint64_t)P.plane_off[1] >= (1ull << 31) || (uint64_t)P.plane_off[2] >= (1ull << 31)) return false;
-    if ((uint64_t)P.store.dst_pitch * (uint64_t)(P.store.off_y + P.out_h) >= (1ull << 32)) return false;
+    if (!StoreRowsFit32(P.store, P.out_h)) return false;
     return true;
 }
 
@@ -568,7 +568,7 @@ bool ConvertBlocksSupported(const FusedParams &P, bool to_rt)
     if ((uint64_t)c.pitch[0] * (uint64_t)(c.rect_t + c.out_h + 2) >= (1ull << 32)) return false;
     if ((uint64_t)P.plane_off[1] >= (1ull << 31) || (uint64_t)P.plane_off[2] >= (1ull << 31)) return false;
     const StoreParams &st = P.store;
-    if ((uint64_t)st.dst_pitch * (uint64_t)(st.off_y + c.out_h) >= (1ull << 32)) return false;
+    if (!StoreRowsFit32(st, c.out_h)) return false;
     if ((st.dst_pitch & 7) || (st.off_x & 1) || !P.dst_aligned16) return false;                 // 8-byte stores
     if (to_rt) {
         // the whole rect inside the window (no per-pixel clipping here)

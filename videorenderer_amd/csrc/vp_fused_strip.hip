@@ -27,7 +27,7 @@ bool FusedStripSupported(const FusedStripParams &S)
         if (S.surf.fmt != SF_BGRA8 && S.surf.fmt != SF_RGB10A2 && S.surf.fmt != SF_RGBA16F) return false;
         if (S.mid_h < 1 || S.surf.w < 1 || S.surf.pitch <= 0 || (S.surf.pitch & 3)) return false;
         if ((uint64_t)S.surf.pitch * (uint64_t)S.surf.h >= (1ull << 32)) return false;
-        if (P.store.off_x + S.out_w > 0 && (uint64_t)P.store.dst_pitch * (uint64_t)(std::max(P.store.off_y, 0) + S.out_h) >= (1ull << 32)) return false;
+        if (!StoreRowsFit32(P.store, S.out_h)) return false;
         if (S.nt != 4 && S.nt != 6 && S.nt != 8 && S.nt != 16) return false;
         if (!S.xi_t || !S.xw_t || !S.yi || !S.yw || !S.yrange || !S.xstrip) return false;
         if ((S.ring != 8 && S.ring != 16 && S.ring != 32) || (S.pxl != 1 && S.pxl != 2) || (S.nt == 16 && S.pxl != 1)) return false;
@@ -39,7 +39,7 @@ bool FusedStripSupported(const FusedStripParams &S)
     if (!P.fast_convert) return false;
     if ((uint64_t)c.pitch[0] * (uint64_t)(c.rect_t + c.out_h + 2) >= (1ull << 32)) return false;
     if ((uint64_t)P.plane_off[1] >= (1ull << 31) || (uint64_t)P.plane_off[2] >= (1ull << 31)) return false;
-    if (P.store.off_x + S.out_w > 0 && (uint64_t)P.store.dst_pitch * (uint64_t)(std::max(P.store.off_y, 0) + S.out_h) >= (1ull << 32)) return false;
+    if (!StoreRowsFit32(P.store, S.out_h)) return false;
     if (S.nt != 4 && S.nt != 6 && S.nt != 8 && S.nt != 16) return false;
     if (!S.xi_t || !S.xw_t || !S.yi || !S.yw || !S.yrange || !S.xstrip) return false;
     if (S.ring != 8 && S.ring != 16 && S.ring != 32) return false;

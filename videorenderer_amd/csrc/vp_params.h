@@ -133,6 +133,16 @@ struct StoreParams {
     const uint16_t *dither;  // 32x32 fp16 table (device)
 };
 
+// The fused kernels (k_fused_up2x, k_fused_jinc2x, k_fused_strip, k_fused_period, k_convert_stream, k_convert_blocks) address a row of
+// their destination as base + (uint32_t)row * (uint32_t)dst_pitch: every row of an image `out_h` rows high must start below 4 GiB (rows
+// above the window, off_y < 0, are never stored).  The ONE statement of that condition: the *Supported functions ask it, and so does every
+// call that hands a caller's render-target pitch to a kernel chosen at plan time (CHipVideoProcessor::ProcessOne, ClassifyBatch).
+// Everything else stores through (size_t)row * pitch.
+inline bool StoreRowsFit32(const StoreParams &st, int out_h)
+{
+    return (uint64_t)st.dst_pitch * (uint64_t)((st.off_y > 0 ? st.off_y : 0) + out_h) < (1ull << 32);
+}
+
 // Tex[AXIS] * wh[AXIS] of output i of n_out, as the reference's shaders see it.  FillVertices (DX11VideoProcessor.cpp:133-138)
 // puts fp32 texture coordinates on the quad's corners (src_dx = 1.0f / texLen; src_l = src_dx * rect.left; src_r = src_dx *
 // rect.right), the rasteriser interpolates them to the pixel centre (i + .5) / n_out (taken as exact, rounded once to fp32) and the
