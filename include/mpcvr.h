@@ -391,7 +391,12 @@ int32_t mpcvr_copy_sample(mpcvr_ctx *ctx, const void *data, int32_t pitch, int32
  * kernels address target rows with 32-bit offsets and step aside, per call, where dst_pitch * (max(dst_rect top, 0) + dst_rect height)
  * reaches 4 GiB — the convert kernel and the resize draws then write the frame, in stream order (such a frame takes no lane), and
  * mpcvr_get_path_info, read after the call, names what ran.  The same holds for every dsts[i] / dst_pitch of mpcvr_process_frames,
- * mpcvr_process_batch and mpcvr_process_batch_dovi (the targets of a batch may lie any distance apart). */
+ * mpcvr_process_batch and mpcvr_process_batch_dovi (the targets of a batch may lie any distance apart).
+ * Exact 2x: the kernels that filter with the weights of the NOMINAL phases (the exact-2x kernel, the fused Jinc2m kernel, the Jinc2m phase
+ * tables) are planned only where, on either axis, sum_k |w_real - w_nominal| x the target's quantisation (255 / 1023) is at most 0.5 codes
+ * (w_real: the weights at the reference's fp32 texture coordinate); above that the any-ratio kernel / the per-pixel Jinc2m kernel draw the
+ * frame with the real weights.  Lanczos3: 3840 -> 7680 is 0.08 codes of 8 bits and 0.31 of 10, a 15360- or 16380-wide source 0.31 and 1.25,
+ * a power of two 0 (measured worst case per side of the threshold: DESIGN.md section 4.2). */
 int32_t mpcvr_process(mpcvr_ctx *ctx, void *dst_dev, int32_t dst_pitch, const mpcvr_rect *src_rect,
                       const mpcvr_rect *dst_rect, int32_t second_field);
 

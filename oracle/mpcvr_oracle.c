@@ -2014,7 +2014,7 @@ int orc_process(const orc_params *p, const uint8_t *src, int src_pitch,
     /* ConvertColorPass -> m_TexConvertOutput (w1 x h1, internal format); rSrc = whole texture :3316-3319 */
     /* with the convert draw disabled (interleaved RGB, default brightness/contrast) the source texture itself feeds
        the resize with rSrc = srcRect (:3321-3323) */
-    img_t conv = {0}, mid = {0}, post = {0};
+    img_t conv = {0}, mid = {0}, post = {0}, tm = {0};      /* (all four in front of the first `goto done`, which frees them) */
     const int *srect = c.enable ? NULL : c.rect;
     if (c.enable) {
         if (img_alloc(&conv, w1, h1)) { free(c.owned); return -5; }
@@ -2098,7 +2098,6 @@ int orc_process(const orc_params *p, const uint8_t *src, int src_pitch,
                           post.p + ((size_t)y * w2 + x) * 4);
         result = &post; result_fmt = swap_fmt;
     }
-    img_t tm = {0};
     if (tonemap) {      /* TextureCopyRect(..., m_pPSHDR10ToneMapping, ...) into the next post-scale texture or the RT */
         const int ox = (result == &conv && srect) ? srect[0] : 0, oy = (result == &conv && srect) ? srect[1] : 0;
         if (img_alloc(&tm, w2, h2)) { rc = -5; goto done; }

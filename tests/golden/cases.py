@@ -243,6 +243,12 @@ FULL_SIZE_CASES = {
 PINNING_CASES["pin_format_p216_2x"] = dict(cformat=7, w=64, h=32, kind="noise", seed=390, dst=(128, 64), iUpscaling=2, exfmt=ext(matrix=M709))
 PINNING_CASES["pin_format_yuv422p16_down"] = dict(cformat=23, w=128, h=64, kind="noise", seed=391, dst=(48, 24), iDownscaling=2, exfmt=HDR10)
 
+# ps_convolution near its largest tap count (128: BuildAxisTaps, ORC_MAX_TAPS) on a 16-output strip: a Lanczos downscale at 20x (121 taps)
+# along X and a Box downscale at 120x (121 taps) along Y, so that the oracle's answer at the top of the ladder of tests/large_geometry.py
+# rests on the reference's own ps_convolution.hlsl text
+PINNING_CASES["pin_down20x_x_only_lanczos_121taps"] = dict(cformat=2, w=320, h=32, kind="noise", seed=395, dst=(16, 32), iDownscaling=5)
+PINNING_CASES["pin_down120x_y_only_box_121taps"] = dict(cformat=1, w=64, h=1920, kind="noise", seed=396, dst=(64, 16), iDownscaling=0, exfmt=ext(matrix=M709))
+
 SETTING_KEYS = ("iTexFormat", "iChromaScaling", "iUpscaling", "iDownscaling", "bInterpolateAt50pct",
                 "bUseDither", "bConvertToSdr", "iSDRDisplayNits", "output_format", "flags")
 

@@ -558,7 +558,7 @@ HRESULT CHipVideoProcessor::UpdatePlan()
         dc.n_x = m_videoRect.Width(); dc.n_y = m_videoRect.Height();
         std::vector<unsigned char> phases(JincPhasesBytes());
         std::vector<float> tab(FusedJincTableBytes() / sizeof(float));
-        if (!BuildJincPhases(dc, phases.data())) m_plan.fused_up2x = m_plan.fused_jinc = false;
+        if (!BuildJincPhases(dc, phases.data(), kNominalPhaseMaxCodes / (float)m_plan.quant)) m_plan.fused_up2x = m_plan.fused_jinc = false;
         else {
 #ifdef MPCVR_DEBUG_HOOKS        // (debug builds only — tools/debug/jinc_diff.py: a one-tap filter, which texel does an output pixel read?)
             if (const char *e = std::getenv("MPCVR_JINC_DBG")) {
@@ -625,7 +625,7 @@ HRESULT CHipVideoProcessor::UploadJincPhases(const DrawCoords &dc, DevBuffer &bu
     *tab = nullptr; *ctr = nullptr;
     HRESULT hr;
     std::vector<unsigned char> host(JincPhasesBytes());
-    if ((m_cfg.flags & MPCVR_FLAG_NO_FUSED) || !BuildJincPhases(dc, host.data())) {
+    if ((m_cfg.flags & MPCVR_FLAG_NO_FUSED) || !BuildJincPhases(dc, host.data(), kNominalPhaseMaxCodes / (float)m_plan.quant)) {
         // the plain kernel: its per-column / per-row texture coordinates as a table (FillVertices' corner values interpolated in fp64, once per index)
         std::vector<float> c((size_t)dc.n_x + dc.n_y);
         BuildDrawCentres(dc, c.data());

@@ -1016,8 +1016,11 @@ hipError_t LaunchHdr10ToneMap(const Surface &in, const HdrToneMapParams &tm, int
     return hipGetLastError();
 }
 
-// the phase table of k_jinc2_phases for this draw, or false when the draw is not dyadic / is rotated or mirrored
-bool BuildJincPhases(const DrawCoords &dc, void *out_table)
+// the phase table of k_jinc2_phases for this draw, or false when the draw is not dyadic / is rotated or mirrored — or when the weights of
+// the nominal phases are further than `max_drift` from the weights the shader computes at the interpolated texture coordinate
+// (sum_k |w_real - w_nominal| of the normalised 16 weights, per axis, at the output index whose coordinate is furthest from its nominal
+// position: vp_plan.h, kNominalPhaseMaxCodes over the quantisation of the render target)
+bool BuildJincPhases(const DrawCoords &dc, void *out_table, float max_drift)
 {
     JincPhases &t = *(JincPhases *)out_table;
     auto period = [](float step) { return step == 1.0f ? 1 : step == 0.5f ? 2 : step == 0.25f ? 4 : 0; };
@@ -1028,33 +1031,49 @@ bool BuildJincPhases(const DrawCoords &dc, void *out_table)
     // step and the ulp changes nothing; on a 1:1 axis (the OTHER axis of a two-draw Jinc2m, always) the position is k + 0.5 — exactly ON the
     // step: one ulp low and the shader's 4 x 4 window sits a texel further left (found by the Jinc2m mode of tests/tools/fuzz_strip.py: 4 columns
     // of an 88-wide frame, up to 53 codes).  So: every output index is checked here, and a draw with one such index keeps the per-pixel kernel.
-    auto axis_ok = [](int org, int len, int tex, int n, int rev, float step) {
+    // `off`: the largest distance of a coordinate from its nominal position (an ulp of the coordinate: 2^-11 texels beyond 8192)
+    auto axis_ok = [](int org, int len, int tex, int n, int rev, float step, float *off) {
+        *off = 0.0f;
         for (int i = 0; i < n; i++) {
             const float pc = TexCenter(org, len, tex, i, n, rev), nominal = (float)org + ((float)i + 0.5f) * step;
             if (floorf(pc - 0.5f) != floorf(nominal - 0.5f)) return false;
+            *off = fmaxf(*off, fabsf(pc - nominal));
         }
         return true;
     };
-    if (!axis_ok(dc.org_x, dc.len_x, dc.tex_x, dc.n_x, dc.rev_x, dc.step_x) || !axis_ok(dc.org_y, dc.len_y, dc.tex_y, dc.n_y, dc.rev_y, dc.step_y)) return false;
+    float off_x = 0.0f, off_y = 0.0f;
+    if (!axis_ok(dc.org_x, dc.len_x, dc.tex_x, dc.n_x, dc.rev_x, dc.step_x, &off_x) || !axis_ok(dc.org_y, dc.len_y, dc.tex_y, dc.n_y, dc.rev_y, dc.step_y, &off_y)) return false;
     const float pi = 3.14159274101257324f, wa = 0.416f * pi, wb = 0.985f * pi;
+    // the shader's expressions at a pixel whose coordinate is (pcx, pcy) in a draw starting at the origin (integer origins drop out exactly)
+    auto weights = [&](float pcx, float pcy, float w16[16]) {
+        const float tcx = floorf(pcx - 0.5f) + 0.5f, tcy = floorf(pcy - 0.5f) + 0.5f;
+        float wsum = 0.0f;
+        for (int j = 0; j < 4; j++) {
+            float rowsum = 0.0f;
+            for (int i = 0; i < 4; i++) {
+                const float vx = (tcx + (float)(i - 1)) - pcx, vy = (tcy + (float)(j - 1)) - pcy;
+                const float dd = sqrtf(vx * vx + vy * vy);
+                const float w = (dd == 0.0f) ? wa * wb : crm_sinf(dd * wa) * crm_sinf(dd * wb) / (dd * dd);
+                w16[j * 4 + i] = w;
+                rowsum = i == 0 ? w : rowsum + w;
+            }
+            wsum = j == 0 ? rowsum : wsum + rowsum;
+        }
+        return wsum;
+    };
     for (int py = 0; py < 4; py++)
         for (int px = 0; px < 4; px++) {
-            // the shader's expressions at output (px, py) of a draw starting at the origin (integer origins drop out exactly)
             const float pcx = ((float)(px % t.px) + 0.5f) * dc.step_x, pcy = ((float)(py % t.py) + 0.5f) * dc.step_y;
-            const float tcx = floorf(pcx - 0.5f) + 0.5f, tcy = floorf(pcy - 0.5f) + 0.5f;
-            float wsum = 0.0f;
-            for (int j = 0; j < 4; j++) {
-                float rowsum = 0.0f;
-                for (int i = 0; i < 4; i++) {
-                    const float vx = (tcx + (float)(i - 1)) - pcx, vy = (tcy + (float)(j - 1)) - pcy;
-                    const float dd = sqrtf(vx * vx + vy * vy);
-                    const float w = (dd == 0.0f) ? wa * wb : crm_sinf(dd * wa) * crm_sinf(dd * wb) / (dd * dd);
-                    t.w[py][px][j * 4 + i] = w;
-                    rowsum = i == 0 ? w : rowsum + w;
-                }
-                wsum = j == 0 ? rowsum : wsum + rowsum;
+            t.wsum[py][px] = weights(pcx, pcy, t.w[py][px]);
+            // the same pixel with its coordinate `off` beside the nominal position, along either axis and to either side
+            for (int a = 0; a < 4; a++) {
+                const float off = a < 2 ? off_x : off_y, sg = (a & 1) ? -off : off;
+                if (off == 0.0f) continue;
+                float w[16], d = 0.0f;
+                const float ws = weights(a < 2 ? pcx + sg : pcx, a < 2 ? pcy : pcy + sg, w);
+                for (int k = 0; k < 16; k++) d += fabsf(w[k] / ws - t.w[py][px][k] / t.wsum[py][px]);
+                if (d > max_drift) return false;
             }
-            t.wsum[py][px] = wsum;
         }
     return true;
 }

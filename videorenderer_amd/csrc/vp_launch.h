@@ -49,7 +49,7 @@ void BuildDrawCentres(const DrawCoords &dc, float *out);       // out: dc.n_x + 
 bool Jinc2QuadSupported(const Surface &in, const DrawCoords &dc, int out_w, int out_h, const StoreParams &st);
 hipError_t LaunchJinc2Quad(const Surface &in, const DrawCoords &dc, int out_w, int out_h, const StoreParams &st, hipStream_t s, const void *phases_dev,
                            const ResizeBatch *batch = nullptr);
-bool BuildJincPhases(const DrawCoords &dc, void *out_table);      // out_table: JincPhasesBytes() bytes of host memory
+bool BuildJincPhases(const DrawCoords &dc, void *out_table, float max_drift);      // out_table: JincPhasesBytes() bytes of host memory; max_drift: see vp_kernels.hip
 size_t JincPhasesBytes();
 
 // fused 2x path (vp_fused.hip): convert + X pass + Y pass + final pass in one kernel, n frames per launch.

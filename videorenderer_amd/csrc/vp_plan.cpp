@@ -891,6 +891,31 @@ bool PlanFusedPeriod(const HostAxisTaps &hx, const HostAxisTaps &hy, int n_out_x
     return true;
 }
 
+// Exact 2x: k_fused_up2x filters with the weights of the two NOMINAL phases (t = 0.75 for even outputs, 0.25 for odd), the shader with
+// those of t = frac(Tex * wh - .5), and TexCenter's fp32 roundings move that t from its nominal value — by up to 2^-13 on a 3840-wide
+// texture, 2^-11 on a 15360-wide one, not at all on a power of two.  The worst output of an axis: sum_k |w_real - w_nominal| (infinite
+// where a tap base itself differs).  The weights of a filter sum to one and a texel lies in [0, 1], so the filtered value moves by at
+// most HALF that sum per axis.  Same principle as PlanFusedPeriod: a disagreement may cost the fast path, never a pixel.
+float Up2xWeightDrift(int iUpscaling, int len)
+{
+    float nom[2][6], w[6];
+    const int n = UpscaleWeights(iUpscaling, 0.75f, nom[0]);
+    if (n != 4 && n != 6) return 0.0f;
+    UpscaleWeights(iUpscaling, 0.25f, nom[1]);
+    float worst = 0.0f;
+    for (int i = 0; i < 2 * len; i++) {
+        const float pos = TexCenter(0, len, len, i, 2 * len, 0) - 0.5f;
+        const float base = std::floor(pos), t = pos - base;
+        if ((int)base != (i >> 1) - 1 + (i & 1)) return INFINITY;
+        if (t == ((i & 1) ? 0.25f : 0.75f)) continue;
+        UpscaleWeights(iUpscaling, t, w);
+        float d = 0.0f;
+        for (int k = 0; k < n; k++) d += std::fabs(w[k] - nom[i & 1][k]);
+        worst = std::max(worst, d);
+    }
+    return worst;
+}
+
 bool DecidePlan(int iTexFormat, int iChromaScaling, int iUpscaling, int iDownscaling, int bInterpolateAt50pct,
                 int bUseDither, int output_format, uint32_t flags, const FmtConvParams &f,
                 const PlanGeometry &g, PassPlan *plan, std::string *why)
@@ -956,6 +981,10 @@ bool DecidePlan(int iTexFormat, int iChromaScaling, int iUpscaling, int iDownsca
     p.fused_up2x = !(flags & MPCVR_FLAG_NO_FUSED) && !g.dovi && g.rotation == 0 && !p.flip && !p.hdr_tonemap && (p.two_pass || jinc_draw) && w2 == 2 * w1 && h2 == 2 * h1 &&
                    p.rx.kind == RS_UP && p.ry.kind == RS_UP && fused_layout && p.internal_fmt != SF_RGBA16F &&
                    g.vl >= 0 && g.vt >= 0 && g.vr <= g.ww && g.vb <= g.wh && w1 >= 8 && h1 >= 8 && !(w1 & 1);
+    // ... and the real tap table within kNominalPhaseMaxCodes of the nominal weights on either axis (the Jinc2m draw's phase table is held to
+    // the same threshold where it is built: BuildJincPhases)
+    if (p.fused_up2x && !jinc_draw &&
+        std::max(Up2xWeightDrift(iUpscaling, w1), Up2xWeightDrift(iUpscaling, h1)) * (float)p.quant > kNominalPhaseMaxCodes) p.fused_up2x = false;
     p.fused_jinc = p.fused_up2x && jinc_draw;
     p.direct_convert = !(flags & MPCVR_FLAG_NO_FUSED) && p.copy_only && p.convert && !p.hdr_tonemap;
     *plan = p;

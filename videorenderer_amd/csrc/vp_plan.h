@@ -105,6 +105,14 @@ struct HostAxisTaps {
 };
 // weights for one fractional phase (ps_interpolation_*.hlsl); returns tap count (4/6) or 0
 int UpscaleWeights(int iUpscaling, float t, float w[6]);
+// Kernels that filter with the weights of the nominal phases of a dyadic ratio (k_fused_up2x, k_fused_jinc2x, k_jinc2_phases, k_jinc2_quad) are
+// planned only where, on either axis, sum_k |w_real - w_nominal| x the quantisation of the render target (255 / 1023) stays at or below this
+// many codes: the filtered value then moves by at most half a code over both axes (half the sum per axis), so a rounded code moves by at
+// most one.  Predictor values (Lanczos3): 3840 -> 7680 0.078 codes of 8 bits / 0.31 of 10; 7680 -> 15360 0.155 / 0.62; 15360 and 16380
+// wide or high 0.31 / 1.25; powers of two 0.  Above the threshold the any-ratio kernels draw the frame with the real table.
+constexpr float kNominalPhaseMaxCodes = 0.5f;
+// the worst output's sum_k |w_real - w_nominal| of an exact-2x axis `len` texels long (the convert draw's output: rect-sized, rect at the origin)
+float Up2xWeightDrift(int iUpscaling, int len);
 // convolution kernels (Shaders/resize/convolution_filters.hlsl); *support optional
 float DownscaleFilter(int iDownscaling, float x, float *support);
 // tap table for n_out outputs of one TextureResizeShader draw along one axis
