@@ -78,9 +78,9 @@ CHipVideoProcessor::~CHipVideoProcessor()
         if (d.pinned) (void)hipHostFree(d.pinned);
         if (d.copied) (void)hipEventDestroy(d.copied);
     }
-    for (TableSlot &ts : m_dvSlots) ts.Release();
+    m_dvTableRing.Release();
     m_lanes.Release();
-    for (TableSlot &ts : m_slots) ts.Release();
+    m_tableRing.Release();
     if (m_evStart) (void)hipEventDestroy(m_evStart);
     if (m_evStop) (void)hipEventDestroy(m_evStop);
     for (hipEvent_t *e : {&m_evUp0, &m_evUp1, &m_evRb0, &m_evRb1}) { if (*e) (void)hipEventDestroy(*e); *e = nullptr; }
@@ -1080,12 +1080,8 @@ HRESULT CHipVideoProcessor::ProcessFrame(void *pRenderTarget, int rtPitch, const
     return hr;
 }
 
-// What every batch entry point starts with: the call's record (GetLastBatchInfo) starts empty — RunBatch adds what each run of the call
-// uses — and the arguments are checked once, before anything is applied or queued
-HRESULT CHipVideoProcessor::BeginBatch(int n, const void *const *srcs, void *const *dsts, int rtPitch)
+HRESULT CHipVideoProcessor::CheckBatchArgs(int n, const void *const *srcs, void *const *dsts, int rtPitch)
 {
-    m_lastBatchFrames = n; m_lastBatchLaunches = m_lastBatchUploads = 0; m_lastBatchLane = -1; m_lastBatchWaits = 0;
-    m_dvLastInfo.clear(); m_yuvLastInfo.clear();
     if (!m_bInit || !m_srcParams) return Fail(MPCVR_E_NOT_VALID_STATE, "InitMediaType has not been called");
     if (n <= 0 || !srcs || !dsts) return Fail(MPCVR_E_INVALIDARG, "empty batch");
     if (rtPitch < m_windowRect.Width() * 4) return Fail(MPCVR_E_INVALIDARG, "render-target pitch smaller than a row");
@@ -1097,20 +1093,17 @@ HRESULT CHipVideoProcessor::BeginBatch(int n, const void *const *srcs, void *con
 
 HRESULT CHipVideoProcessor::ProcessBatch(int n, const void *const *srcs, void *const *dsts, int rtPitch)
 {
-    if (HRESULT bad = BeginBatch(n, srcs, dsts, rtPitch)) return bad;
+    const BatchRecord record(*this, n);
+    if (HRESULT bad = CheckBatchArgs(n, srcs, dsts, rtPitch)) return bad;
     BatchRun run{n, srcs, dsts, rtPitch};
     return RunBatch(run);
 }
 
 HRESULT CHipVideoProcessor::RunBatch(BatchRun &run)
 {
-    const unsigned before = m_launches, uploadsBefore = m_tableUploads;
     (void)hipSetDevice(m_device);
-    HRESULT hr = m_planDirty ? UpdatePlan() : MPCVR_S_OK;
-    if (!hr) hr = m_plan.errdiff ? ProcessBatchErrDiff(run) : ProcessBatchRoutes(run);
-    m_lastBatchLaunches += (int)(m_launches - before);
-    m_lastBatchUploads += (int)(m_tableUploads - uploadsBefore);
-    return hr;
+    if (HRESULT bad = m_planDirty ? UpdatePlan() : MPCVR_S_OK) return bad;
+    return m_plan.errdiff ? ProcessBatchErrDiff(run) : ProcessBatchRoutes(run);
 }
 
 // One batch: classified once (ClassifyBatch), then run on one of two lanes beside the batch before it when its route shares nothing
@@ -1118,6 +1111,16 @@ HRESULT CHipVideoProcessor::RunBatch(BatchRun &run)
 HRESULT CHipVideoProcessor::ProcessBatchRoutes(BatchRun &run)
 {
     BatchRoutePlan rp = ClassifyBatch(run);
+    std::vector<RtSpan> targets((size_t)run.n);
+    for (int i = 0; i < run.n; i++) targets[i] = TargetSpan(run.dsts[i], run.rtPitch);
+    const int bl = PlaceBatch(rp, run, std::move(targets));
+    const HRESULT hr = RunBatchRoute(rp, run);
+    NoteBatchQueued(bl);
+    return hr;
+}
+
+int CHipVideoProcessor::PlaceBatch(const BatchRoutePlan &rp, BatchRun &run, std::vector<RtSpan> &&writes)
+{
     // The same rule as for single frames — nothing a batch touches may be shared with the batch beside it — read off the route the batch takes:
     // the exact-2x kernel, the strip / periodic kernel reading the samples themselves, the same-size block convert (no intermediate surface; a
     // repacked v210 batch reads the shared m_batchTex); default tier only.  Two launches in flight were measured to pay on every such route (same
@@ -1125,21 +1128,17 @@ HRESULT CHipVideoProcessor::ProcessBatchRoutes(BatchRun &run)
     // bench_batch_lanes_call27.txt): same-size block convert +11-16 %, exact-2x kernel +2-5 % (4K -> 8K, four rounds of waves per batch) to +15 %
     // (1080p -> 4K, one round), strip / periodic kernel +11-29 % (1080p -> 1440p 99.8 k -> 116.4 k frames/s, 720p -> 1080p 190 k -> 246 k), fused
     // Jinc2m +4 %.  (An earlier table that had the strip kernels LOSE was a wall clock around 30 launches of 0.3 ms: it measured the closing synchronize.)
-    // (the rule itself: BatchLaneEligible, shared with ProcessBatchYuv)
-    const bool onLane = BatchLaneEligible(rp, run);
-    const int bl = onLane ? m_lanes.PickBatchLane(run.n, run.dsts, TargetSpan(nullptr, run.rtPitch).hi, &m_lastBatchWaits) : -1;
+    const int bl = BatchLaneEligible(rp, run) ? m_lanes.PickBatchLane(std::move(writes), &m_lastBatchWaits) : -1;
     run.on = RunOn{bl >= 0 ? m_lanes.Stream(bl) : m_stream};
     if (bl >= 0) {
         m_lastBatchLane = bl;
         m_lanes.LaneWaitsForStream(bl, m_stream);    // behind whatever the context stream was given since the lane last looked
     } else OrderOnContextStream();           // behind every single frame still in flight, and single frames queued after it run behind the batch
-    const HRESULT hr = RunBatchRoute(rp, run);
-    if (bl >= 0) m_lanes.NoteLaneBatch(bl);
-    return hr;
+    return bl;
 }
 
 // May the batch run on a batch lane?  One launch with nothing shared, on a context that owns its stream, default tier (the measurements: the
-// comment in ProcessBatchRoutes).  PrepareSample, ApplyDoviFrame / UploadDoviParams and UploadDoviTables queue on the context stream whatever
+// comment in PlaceBatch).  PrepareSample, ApplyDoviFrame / UploadDoviParams and UploadDoviTables queue on the context stream whatever
 // the run says: they are reached only from routes that never take a lane — FrameByFrame is no lane route, and a run with Dolby Vision
 // metadata fails the condition below.
 bool CHipVideoProcessor::BatchLaneEligible(const BatchRoutePlan &rp, const BatchRun &run) const
@@ -1236,9 +1235,7 @@ HRESULT CHipVideoProcessor::RunBatchRoute(BatchRoutePlan &rp, BatchRun &run)
         run.usedTables = true;
         rp.direct.conv.dovi = rp.conv.conv.dovi = run.dvTab; rp.direct.dovi_cm = rp.conv.dovi_cm = run.dvCm;
     }
-    // The frame table travels through a small ring of pinned/device slots so the host can queue several batches ahead; a slot is reused
-    // only after the launches that read it have completed (the lease records its event behind them, at the end of this function).
-    SlotLease table;
+    SlotLease table;        // the batch's frame table, where it travels through the ring: on loan until the end of this function, behind the launches that read it
     switch (rp.route) {
     case BatchRoute::DirectConvert:
         if (n <= kHostTableMax) {
@@ -1260,7 +1257,7 @@ HRESULT CHipVideoProcessor::RunBatchRoute(BatchRoutePlan &rp, BatchRun &run)
         // k_fused_strip:surface launch resizes the whole chunk from there, instead of a repack + a resize launch per frame
         const int tp = TexPitch();
         const size_t texBytes = (size_t)tp * m_srcHeight;
-        const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, ((size_t)1 << 30) / std::max<size_t>(texBytes, 1)));
+        const int chunk = FramesPerChunk(n, texBytes, (size_t)1 << 30);
         const bool fresh = m_batchTex.size < texBytes * chunk || !m_batchTex.ptr || !m_batchTexZeroed;     // (not by size alone: a v210 batch or another media type may have used it since)
         if ((hr = CheckHip(m_batchTex.CheckCreate(texBytes * chunk), "batch source texture"))) break;
         // texels the reference's copy loop never writes (RGB48 remainder) stay zero, as in PrepareSample
@@ -1285,7 +1282,7 @@ HRESULT CHipVideoProcessor::RunBatchRoute(BatchRoutePlan &rp, BatchRun &run)
         // k_hdr10_tonemap launch writes the render targets (:3359-3367)
         const int w2 = m_videoRect.Width(), h2 = m_videoRect.Height();
         const size_t postStride = PostStride();
-        const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, ((size_t)4 << 30) / std::max<size_t>(postStride, 1)));
+        const int chunk = FramesPerChunk(n, postStride, (size_t)4 << 30);
         if ((hr = CheckHip(m_batchPost.CheckCreate(postStride * chunk), "batch post-scale textures"))) break;
         const Surface post{m_batchPost.ptr, (int)(w2 * SurfBytesPerPixel(m_plan.internal_fmt)), w2, h2, m_plan.internal_fmt};
         rp.strip.fp.store.dst = post.ptr;
@@ -1403,7 +1400,7 @@ HRESULT CHipVideoProcessor::ProcessBatchErrDiff(BatchRun &run)
     // intermediates for up to ~4 GiB of frames at a time, in chunks of equal size: the pass is a chain of dependent steps per frame and only
     // many frames side by side fill the chip (a 33-frame batch as 32 + 1 took 13.8 ms where 32 take 8.5: the odd frame ran alone)
     static const int cap = [] { const char *e = std::getenv("MPCVR_ERRDIFF_CHUNK"); return e ? std::atoi(e) : 0; }();      // (tests: chunks of a few small frames)
-    int most = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, ((size_t)4 << 30) / std::max<size_t>(one, 1)));
+    int most = FramesPerChunk(n, one, (size_t)4 << 30);
     if (cap > 0) most = std::min(most, cap);
     const int chunks = (n + most - 1) / most;
     const int chunk = (n + chunks - 1) / chunks;
@@ -1431,44 +1428,48 @@ HRESULT CHipVideoProcessor::ProcessBatchErrDiff(BatchRun &run)
     return MPCVR_S_OK;
 }
 
-void CHipVideoProcessor::TableSlot::Release()
+void CHipVideoProcessor::TableRing::Release()
 {
-    dev.Release();
-    if (pinned) (void)hipHostFree(pinned);
-    if (done) (void)hipEventDestroy(done);
+    for (Slot &slot : m_slots) {
+        slot.dev.Release();
+        if (slot.pinned) (void)hipHostFree(slot.pinned);
+        if (slot.done) (void)hipEventDestroy(slot.done);
+    }
 }
 
-// A slot of the frame-table or the Dolby Vision table ring on loan: free to be rewritten (the launches behind its last lease have completed)
-// and large enough for `bytes` (allocated for `atLeast` or more, so that batches of growing size do not reallocate one by one).  An event
-// that was never recorded counts as complete.
-HRESULT CHipVideoProcessor::AcquireSlot(TableSlot &slot, size_t bytes, size_t atLeast, hipStream_t stream, SlotLease *lease)
+HRESULT CHipVideoProcessor::TableRing::Next(size_t bytes, size_t atLeast, void **pinned)
 {
-    HRESULT hr = slot.done ? CheckHip(hipEventSynchronize(slot.done), "table slot wait")
-                           : CheckHip(hipEventCreateWithFlags(&slot.done, hipEventDisableTiming), "table slot event");
+    Slot &slot = m_slots[m_sent % m_slots.size()];
+    HRESULT hr = slot.done ? m_owner->CheckHip(hipEventSynchronize(slot.done), "table slot wait")
+                           : m_owner->CheckHip(hipEventCreateWithFlags(&slot.done, hipEventDisableTiming), "table slot event");
     if (hr) return hr;
     if (bytes > slot.cap) {
         if (slot.pinned) (void)hipHostFree(slot.pinned);
         slot.pinned = nullptr; slot.cap = 0;
         const size_t cap = std::max(bytes, atLeast);
-        if ((hr = CheckHip(hipHostMalloc(&slot.pinned, cap, hipHostMallocDefault), "table slot pinned"))) return hr;
-        if ((hr = CheckHip(slot.dev.CheckCreate(cap), "table slot"))) return hr;
+        if ((hr = m_owner->CheckHip(hipHostMalloc(&slot.pinned, cap, hipHostMallocDefault), "table slot pinned"))) return hr;
+        if ((hr = m_owner->CheckHip(slot.dev.CheckCreate(cap), "table slot"))) return hr;
         slot.cap = cap;
     }
+    *pinned = slot.pinned;
+    return MPCVR_S_OK;
+}
+
+HRESULT CHipVideoProcessor::TableRing::Send(size_t bytes, hipStream_t stream, const char *what, SlotLease *lease)
+{
+    Slot &slot = m_slots[m_sent % m_slots.size()];
     *lease = SlotLease(slot.dev.ptr, slot.done, stream);
+    if (HRESULT hr = m_owner->CheckHip(hipMemcpyAsync(slot.dev.ptr, slot.pinned, bytes, hipMemcpyHostToDevice, stream), what)) return hr;
+    m_sent++;
     return MPCVR_S_OK;
 }
 
 HRESULT CHipVideoProcessor::UploadFrameTable(int n, const void *const *srcs, void *const *dsts, uint8_t *dst_base, size_t dst_stride, hipStream_t stream, SlotLease *lease)
 {
-    HRESULT hr;
-    TableSlot &slot = m_slots[m_slotNext];
-    m_slotNext = (m_slotNext + 1) % kFrameSlots;
-    if ((hr = AcquireSlot(slot, sizeof(FusedFrame) * n, sizeof(FusedFrame) * 64, stream, lease))) return hr;
-    FusedFrame *fr = (FusedFrame *)slot.pinned;
+    FusedFrame *fr;
+    if (HRESULT hr = m_tableRing.Next(sizeof(FusedFrame) * n, sizeof(FusedFrame) * 64, (void **)&fr)) return hr;
     for (int i = 0; i < n; i++) { fr[i].src = srcs ? (const uint8_t *)srcs[i] : nullptr; fr[i].dst = dsts ? dsts[i] : (void *)(dst_base + (size_t)i * dst_stride); }
-    if ((hr = CheckHip(hipMemcpyAsync(slot.dev.ptr, fr, sizeof(FusedFrame) * n, hipMemcpyHostToDevice, stream), "frame table"))) return hr;
-    m_tableUploads++;
-    return MPCVR_S_OK;
+    return m_tableRing.Send(sizeof(FusedFrame) * n, stream, "frame table", lease);
 }
 
 // The exact-2x kernel's tables as it keeps them in LDS, computed once per plan instead of by every workgroup of every launch
@@ -1567,7 +1568,7 @@ HRESULT CHipVideoProcessor::ProcessBatchLaunches(const BatchRun &run, const Fuse
     const bool hdr = m_plan.hdr_tonemap;
     const size_t postStride = hdr ? PostStride() : 0;
     const size_t per = m_convBytes + m_midBytes + postStride;
-    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, ((size_t)4 << 30) / std::max<size_t>(per, 1)));
+    const int chunk = FramesPerChunk(n, per, (size_t)4 << 30);
     if ((hr = CheckHip(m_batchConv.CheckCreate(m_convBytes * chunk), "batch convert output"))) return hr;
     if (m_midBytes && (hr = CheckHip(m_batchMid.CheckCreate(m_midBytes * chunk), "batch resize texture"))) return hr;
     if (hdr && (hr = CheckHip(m_batchPost.CheckCreate(postStride * chunk), "batch post-scale textures"))) return hr;
@@ -1626,30 +1627,28 @@ HRESULT CHipVideoProcessor::ApplyDoviFrame(const DoviFrameState &f)
     return UploadDoviParams();          // through the pinned ring, in stream order: the frames before this one read their own copy
 }
 
-// DoviParams[n] followed by cm[12 n], staged through one of two pinned / device slots (a slot is rewritten only after the launches
-// that read it have completed: the lease, which ProcessBatchDovi keeps until the run is queued); fills run->dvTab / dvCm
+// DoviParams[n] followed by cm[12 n], through the ring of two slots (ProcessBatchDovi keeps the lease until the run is queued); fills run->dvTab / dvCm
 HRESULT CHipVideoProcessor::UploadDoviTables(BatchRun *run, hipStream_t stream, SlotLease *lease)
 {
     const int n = run->n;
-    HRESULT hr;
-    TableSlot &slot = m_dvSlots[m_dvSlotNext++ % 2];
     const size_t each = sizeof(DoviParams) + 12 * sizeof(float), need = each * n;
-    if ((hr = AcquireSlot(slot, need, each * 64, stream, lease))) return hr;
-    DoviParams *tp = (DoviParams *)slot.pinned;
+    DoviParams *tp;
+    if (HRESULT hr = m_dvTableRing.Next(need, each * 64, (void **)&tp)) return hr;
     float *tc = (float *)(tp + n);
     for (int i = 0; i < n; i++) {
         tp[i] = run->dvFrames[i].p;
         std::memcpy(tc + (size_t)12 * i, run->dvFrames[i].cm, 12 * sizeof(float));
     }
-    if ((hr = CheckHip(hipMemcpyAsync(slot.dev.ptr, slot.pinned, need, hipMemcpyHostToDevice, stream), "dovi tables upload"))) return hr;
-    run->dvTab = (const DoviParams *)slot.dev.ptr;
+    if (HRESULT hr = m_dvTableRing.Send(need, stream, "dovi tables upload", lease)) return hr;
+    run->dvTab = (const DoviParams *)lease->dev;
     run->dvCm = (const float *)(run->dvTab + n);
     return MPCVR_S_OK;
 }
 
 HRESULT CHipVideoProcessor::ProcessBatchDovi(int n, const void *const *srcs, void *const *dsts, int rtPitch, const mpcvr_dovi_metadata *rpus)
 {
-    if (HRESULT bad = BeginBatch(n, rpus ? srcs : nullptr, dsts, rtPitch)) return bad;        // (no RPUs: an empty batch, like no samples)
+    const BatchRecord record(*this, n);
+    if (HRESULT bad = CheckBatchArgs(n, rpus ? srcs : nullptr, dsts, rtPitch)) return bad;       // (no RPUs: an empty batch, like no samples)
     for (int i = 0; i < n; i++)         // all or nothing: no frame is drawn when one RPU of the batch is malformed
         if (!CheckDoviCurves(rpus[i])) return Fail(MPCVR_E_INVALIDARG, "Dolby Vision curves: num_pivots outside [2,9], mapping_idc > 1 or more than 32 level-2 blocks");
     (void)hipSetDevice(m_device);
@@ -1674,7 +1673,7 @@ HRESULT CHipVideoProcessor::ProcessBatchDovi(int n, const void *const *srcs, voi
         const int len = j - i;
         BatchRun run{len, srcs + i, dsts + i, rtPitch, fs.data() + i};
         SlotLease tables;           // (until the run is queued)
-        if (len > 1 && !m_plan.hdr_tonemap) hr = UploadDoviTables(&run, m_stream, &tables);       // (a run with RPUs stays on the context stream: ProcessBatchRoutes)
+        if (len > 1 && !m_plan.hdr_tonemap) hr = UploadDoviTables(&run, m_stream, &tables);       // (a run with RPUs stays on the context stream: BatchLaneEligible)
         if (!hr) hr = RunBatch(run);
         m_dvLastInfo += (m_dvLastInfo.empty() ? "" : ",") + std::to_string(len) + (run.usedTables ? ":tables" : ":frames");
         // the context's own copy of the constants: the run's last frame (a whole-batch route did not touch it)
@@ -1717,6 +1716,20 @@ HRESULT CHipVideoProcessor::RenderBackBuffer(bool onContextStream)
 // EXTENSION — the frame as NV12 / P010 for an encoder (include/mpcvr.h: mpcvr_encode_pass, mpcvr_render_yuv; kernel: vp_encode.hip).
 // No reference line: the reference has no RGB -> YUV path.
 // ------------------------------------------------------------------------------------------------
+// What a k_encode420 launch is given, but for its pointers: the caller adds src / y / uv or the frame table, and takes src16 / dst8 back
+// where a pointer of the launch is off 16 / 8 bytes (here they say what the pitches allow)
+static EncodeParams EncodeLaunchParams(const EncodePlan &plan, int w, int h, int srcPitch, int yPitch, int uvPitch)
+{
+    EncodeParams p{};
+    p.src_pitch = srcPitch; p.y_pitch = yPitch; p.uv_pitch = uvPitch;
+    p.w = w; p.h = h;
+    std::memcpy(p.coef, plan.coef, sizeof(p.coef));
+    std::memcpy(p.off, plan.off, sizeof(p.off));
+    p.src16 = (srcPitch & 15) == 0;
+    p.dst8 = ((yPitch | uvPitch) & 7) == 0;
+    return p;
+}
+
 HRESULT EncodeSurface(const void *src, int srcPitch, int srcFmt, int w, int h, int outCformat, uint32_t extfmt, void *yPlane, int yPitch,
                       void *uvPlane, int uvPitch, hipStream_t stream, bool checkOnly, const char **why)
 {
@@ -1731,21 +1744,14 @@ HRESULT EncodeSurface(const void *src, int srcPitch, int srcFmt, int w, int h, i
     if (((uintptr_t)src | (uintptr_t)yPlane | (uintptr_t)uvPlane | (uintptr_t)srcPitch | (uintptr_t)yPitch | (uintptr_t)uvPitch) & 3) {
         *why = "surface, planes and pitches must be multiples of 4"; return MPCVR_E_INVALIDARG;
     }
-    // a plane counts as the bytes from its first pixel to the last pixel of its last row
-    const uintptr_t s0 = (uintptr_t)src, s1 = s0 + (size_t)(h - 1) * srcPitch + (size_t)4 * w;
-    const uintptr_t y0 = (uintptr_t)yPlane, y1 = y0 + (size_t)(h - 1) * yPitch + rowBytes;
-    const uintptr_t c0 = (uintptr_t)uvPlane, c1 = c0 + (size_t)(h / 2 - 1) * uvPitch + rowBytes;
-    if ((y0 < c1 && c0 < y1) || (src && ((y0 < s1 && s0 < y1) || (c0 < s1 && s0 < c1)))) { *why = "the planes overlap each other or the source"; return MPCVR_E_INVALIDARG; }
+    const RtSpan s = RowsSpan(src, (size_t)srcPitch, h, (size_t)4 * w);
+    const RtSpan y = RowsSpan(yPlane, (size_t)yPitch, h, (size_t)rowBytes), c = RowsSpan(uvPlane, (size_t)uvPitch, h / 2, (size_t)rowBytes);
+    if (y.Overlaps(c) || (src && (y.Overlaps(s) || c.Overlaps(s)))) { *why = "the planes overlap each other or the source"; return MPCVR_E_INVALIDARG; }
     if (checkOnly) return MPCVR_S_OK;
-    EncodeParams p{};
-    p.src = (const uint8_t *)src; p.src_pitch = srcPitch;
-    p.y = (uint8_t *)yPlane; p.y_pitch = yPitch;
-    p.uv = (uint8_t *)uvPlane; p.uv_pitch = uvPitch;
-    p.w = w; p.h = h;
-    std::memcpy(p.coef, plan.coef, sizeof(p.coef));
-    std::memcpy(p.off, plan.off, sizeof(p.off));
-    p.src16 = ((s0 | (uintptr_t)srcPitch) & 15) == 0;
-    p.dst8 = ((y0 | c0 | (uintptr_t)yPitch | (uintptr_t)uvPitch) & 7) == 0;
+    EncodeParams p = EncodeLaunchParams(plan, w, h, srcPitch, yPitch, uvPitch);
+    p.src = (const uint8_t *)src; p.y = (uint8_t *)yPlane; p.uv = (uint8_t *)uvPlane;
+    p.src16 &= (s.lo & 15) == 0;
+    p.dst8 &= ((y.lo | c.lo) & 7) == 0;
     if (LaunchEncode420(p, plan.in10, plan.out10, plan.siting, stream) != hipSuccess) { *why = "k_encode420 launch failed"; return MPCVR_E_FAIL; }
     return MPCVR_S_OK;
 }
@@ -1777,6 +1783,16 @@ HRESULT CHipVideoProcessor::RenderYuv(int /*field*/, int outCformat, uint32_t ex
 // EXTENSION — measuring a rendered frame: the histogram of max(R, G, B) (include/mpcvr.h: mpcvr_measure_pass, mpcvr_measure_backbuffer;
 // kernel: vp_measure.hip).  No reference line: the reference's statistics are an overlay.
 // ------------------------------------------------------------------------------------------------
+// What a k_measure_maxrgb launch is given, but for its pointers: src / hist and the frame stride are the caller's, as in EncodeLaunchParams
+static MeasureParams MeasureLaunchParams(int srcPitch, int w, const mpcvr_rect &r)
+{
+    MeasureParams p{};
+    p.src_pitch = srcPitch; p.w = w;
+    p.left = r.left; p.top = r.top; p.right = r.right; p.bottom = r.bottom;
+    p.src16 = (srcPitch & 15) == 0;
+    return p;
+}
+
 HRESULT MeasureSurface(const void *src, int srcPitch, int srcFmt, int w, int h, const mpcvr_rect *rect, uint32_t *histDev, hipStream_t stream,
                        bool checkOnly, const char **why)
 {
@@ -1792,26 +1808,21 @@ HRESULT MeasureSurface(const void *src, int srcPitch, int srcFmt, int w, int h, 
     if (r.left < 0 || r.top < 0 || r.right > w || r.bottom > h || r.left >= r.right || r.top >= r.bottom) {
         *why = "the rectangle is empty or leaves the surface"; return MPCVR_E_INVALIDARG;
     }
-    // the surface counts as the bytes from its first pixel to the last pixel of its last row
-    const uintptr_t s0 = (uintptr_t)src, s1 = s0 + (size_t)(h - 1) * srcPitch + (size_t)4 * w;
-    const uintptr_t h0 = (uintptr_t)histDev, h1 = h0 + sizeof(uint32_t) * kHistBins;
-    if (h0 < s1 && s0 < h1) { *why = "the histogram overlaps the surface"; return MPCVR_E_INVALIDARG; }
+    const RtSpan s = RowsSpan(src, (size_t)srcPitch, h, (size_t)4 * w), bins{(uintptr_t)histDev, (uintptr_t)histDev + sizeof(uint32_t) * kHistBins};
+    if (bins.Overlaps(s)) { *why = "the histogram overlaps the surface"; return MPCVR_E_INVALIDARG; }
     if (checkOnly) return MPCVR_S_OK;
-    MeasureParams p{};
-    p.src = (const uint8_t *)src; p.src_pitch = srcPitch;
-    p.hist = histDev;
-    p.w = w;
-    p.left = r.left; p.top = r.top; p.right = r.right; p.bottom = r.bottom;
-    p.src16 = ((s0 | (uintptr_t)srcPitch) & 15) == 0;
+    MeasureParams p = MeasureLaunchParams(srcPitch, w, r);
+    p.src = (const uint8_t *)src; p.hist = histDev;
+    p.src16 &= (s.lo & 15) == 0;
     if (LaunchMeasure(p, srcFmt == MPCVR_OUT_RGB10A2, stream) != hipSuccess) { *why = "k_measure_maxrgb launch failed"; return MPCVR_E_FAIL; }
     return MPCVR_S_OK;
 }
 
-CRect CHipVideoProcessor::ActiveRect() const
+mpcvr_rect CHipVideoProcessor::ActiveRect() const
 {
-    CRect a(std::max(m_videoRect.left, 0), std::max(m_videoRect.top, 0), std::min(m_videoRect.right, m_windowRect.Width()),
-            std::min(m_videoRect.bottom, m_windowRect.Height()));
-    if (a.right <= a.left || a.bottom <= a.top) a = CRect();
+    mpcvr_rect a{std::max(m_videoRect.left, 0), std::max(m_videoRect.top, 0), std::min(m_videoRect.right, m_windowRect.Width()),
+                 std::min(m_videoRect.bottom, m_windowRect.Height())};
+    if (a.right <= a.left || a.bottom <= a.top) a = mpcvr_rect{0, 0, 0, 0};
     return a;
 }
 
@@ -1826,9 +1837,8 @@ HRESULT CHipVideoProcessor::MeasureBackBuffer(uint32_t *histDev)
     // no frame yet, or none of this window's size and format (the back buffer is addressed by the window)
     if (!m_BackBuffer.ptr || m_backW != w || m_backH != h || m_backFmt != m_cfg.output_format || w < 1 || h < 1) return MPCVR_S_FALSE;
     (void)hipSetDevice(m_device);
-    const CRect a = ActiveRect();
-    const bool empty = a.IsRectNull();
-    const mpcvr_rect r{a.left, a.top, a.right, a.bottom};
+    const mpcvr_rect r = ActiveRect();
+    const bool empty = r.right <= r.left;
     const char *why = "";
     HRESULT hr;
     // (an empty active area: the checks run against the whole window, then only the clear is queued)
@@ -1855,8 +1865,7 @@ HRESULT CHipVideoProcessor::MeasureBackBuffer(uint32_t *histDev)
 HRESULT CHipVideoProcessor::ProcessBatchYuv(int n, const void *const *srcs, int outCformat, uint32_t extfmt, void *const *yPlanes, int yPitch,
                                             void *const *uvPlanes, int uvPitch, uint32_t *histDev)
 {
-    m_lastBatchFrames = n > 0 ? n : 0; m_lastBatchLaunches = m_lastBatchUploads = 0; m_lastBatchLane = -1; m_lastBatchWaits = 0;
-    m_dvLastInfo.clear(); m_yuvLastInfo.clear();
+    const BatchRecord record(*this, n > 0 ? n : 0);
     if (!m_bInit || !m_srcParams) return Fail(MPCVR_E_NOT_VALID_STATE, "InitMediaType has not been called");
     if (n <= 0) return Fail(MPCVR_E_INVALIDARG, "empty batch");
     if (!srcs || !yPlanes || !uvPlanes) return Fail(MPCVR_E_POINTER, "null array of frames or planes");
@@ -1884,16 +1893,10 @@ HRESULT CHipVideoProcessor::ProcessBatchYuv(int n, const void *const *srcs, int 
             if (pl.Overlaps(rows)) return Fail(MPCVR_E_INVALIDARG, "the histogram rows overlap a plane of the batch");
     }
 
-    const unsigned before = m_launches, uploadsBefore = m_tableUploads;
     (void)hipSetDevice(m_device);
-    HRESULT hr;
+    HRESULT hr = MPCVR_S_OK;
     if (m_planDirty && (hr = UpdatePlan())) return hr;
-    EncodeParams ep{};
-    ep.src_pitch = lay.surfacePitch; ep.y_pitch = yPitch; ep.uv_pitch = uvPitch;
-    ep.w = w; ep.h = h;
-    std::memcpy(ep.coef, plan.coef, sizeof(ep.coef));
-    std::memcpy(ep.off, plan.off, sizeof(ep.off));
-    ep.src16 = 1;                                       // every frame of a surface starts on 256 bytes, the pitch is a multiple of 16
+    const EncodeParams ep = EncodeLaunchParams(plan, w, h, lay.surfacePitch, yPitch, uvPitch);      // (src16 holds for every chunk: every frame of a surface starts on 256 bytes)
     const int most = lay.framesPerChunk;
     std::vector<void *> frames((size_t)most);
     auto surfaceFrames = [&](YuvSurface &s) -> HRESULT {       // the surface for `most` frames, and their addresses
@@ -1905,40 +1908,24 @@ HRESULT CHipVideoProcessor::ProcessBatchYuv(int n, const void *const *srcs, int 
     };
     std::string lanes;
     int chunks = 0;
-    hr = MPCVR_S_OK;
     for (int at = 0; at < n && !hr; at += most, chunks++) {
         const int m = std::min(most, n - at);
         BatchRun run{m, srcs + at, frames.data(), lay.surfacePitch};
         YuvSurface *surf = &m_yuvSurf[0];
         if ((hr = surfaceFrames(*surf))) break;
-        int bl = -1;
-        BatchRoutePlan rp;
-        if (!m_plan.errdiff) {
+        BatchRoutePlan rp = m_plan.errdiff ? BatchRoutePlan{} : ClassifyBatch(run);     // (an error-diffusion plan classifies its own chunks: the default is no lane route)
+        std::vector<RtSpan> writes(planes.begin() + 2 * (size_t)at, planes.begin() + 2 * (size_t)(at + m));
+        if (histDev) writes.push_back(RtSpan{(uintptr_t)histDev + kHistRow * (size_t)at, (uintptr_t)histDev + kHistRow * (size_t)(at + m)});
+        const int bl = PlaceBatch(rp, run, std::move(writes));
+        if (bl > 0) {                                   // another lane, another surface: the route is planned for the targets it draws into
+            surf = &m_yuvSurf[bl];
+            if ((hr = surfaceFrames(*surf))) break;
             rp = ClassifyBatch(run);
-            if (BatchLaneEligible(rp, run)) {
-                int waits = 0;
-                std::vector<RtSpan> writes(planes.begin() + 2 * (size_t)at, planes.begin() + 2 * (size_t)(at + m));
-                if (histDev) writes.push_back(RtSpan{(uintptr_t)histDev + kHistRow * (size_t)at, (uintptr_t)histDev + kHistRow * (size_t)(at + m)});
-                bl = m_lanes.PickBatchLane(std::move(writes), &waits);
-                m_lastBatchWaits += waits;
-                if (bl > 0) {                           // another lane, another surface: the route is planned for the targets it draws into
-                    surf = &m_yuvSurf[bl];
-                    if ((hr = surfaceFrames(*surf))) break;
-                    rp = ClassifyBatch(run);
-                }
-            }
         }
-        run.on = RunOn{bl >= 0 ? m_lanes.Stream(bl) : m_stream};
-        if (bl >= 0) {
-            m_lastBatchLane = bl;
-            m_lanes.LaneWaitsForStream(bl, m_stream);
-        } else OrderOnContextStream();
         if (chunks < 64) lanes += (chunks ? "," : "") + std::to_string(bl);
         hr = RunYuvChunk(rp, run, *surf, ep, plan, yPlanes + at, uvPlanes + at, histDev ? histDev + (size_t)kHistBins * (size_t)at : nullptr);
-        if (bl >= 0) m_lanes.NoteLaneBatch(bl); else m_lanes.NoteStreamWork();
+        NoteBatchQueued(bl);
     }
-    m_lastBatchLaunches = (int)(m_launches - before);
-    m_lastBatchUploads = (int)(m_tableUploads - uploadsBefore);
     m_yuvLastInfo = ";yuv_chunks=" + std::to_string(chunks) + ";yuv_lanes=" + lanes;
     return hr;
 }
@@ -1955,32 +1942,22 @@ HRESULT CHipVideoProcessor::RunYuvChunk(BatchRoutePlan &rp, BatchRun &run, YuvSu
     }
     // (the error-diffusion plan runs its own chunks and its pass on the context stream: `run` is on it, BatchLaneEligible refuses such a plan)
     if ((hr = m_plan.errdiff ? ProcessBatchErrDiff(run) : RunBatchRoute(rp, run))) return hr;
-    // the planes' table through the frame-table ring; the lease ends behind the pass
+    // the planes' table through the frame tables' ring; the lease ends behind the pass
     SlotLease table;
-    TableSlot &slot = m_slots[m_slotNext];
-    m_slotNext = (m_slotNext + 1) % kFrameSlots;
-    if ((hr = AcquireSlot(slot, sizeof(EncodeFrame) * run.n, sizeof(EncodeFrame) * 64, stream, &table))) return hr;
-    EncodeFrame *fr = (EncodeFrame *)slot.pinned;
-    uintptr_t bits = (uintptr_t)encode.y_pitch | (uintptr_t)encode.uv_pitch;
+    EncodeFrame *fr;
+    if ((hr = m_tableRing.Next(sizeof(EncodeFrame) * run.n, sizeof(EncodeFrame) * 64, (void **)&fr))) return hr;
+    EncodeParams ep = encode;
     for (int i = 0; i < run.n; i++) {
         fr[i] = EncodeFrame{(const uint8_t *)run.dsts[i], (uint8_t *)yPlanes[i], (uint8_t *)uvPlanes[i]};
-        bits |= (uintptr_t)yPlanes[i] | (uintptr_t)uvPlanes[i];
+        ep.dst8 &= (((uintptr_t)yPlanes[i] | (uintptr_t)uvPlanes[i]) & 7) == 0;       // the 8-byte stores only if every plane of the launch allows them
     }
-    if ((hr = CheckHip(hipMemcpyAsync(slot.dev.ptr, fr, sizeof(EncodeFrame) * run.n, hipMemcpyHostToDevice, stream), "plane table"))) return hr;
-    m_tableUploads++;
-    EncodeParams ep = encode;
+    if ((hr = m_tableRing.Send(sizeof(EncodeFrame) * run.n, stream, "plane table", &table))) return hr;
     ep.frames = (const EncodeFrame *)table.dev;
-    ep.dst8 = (bits & 7) == 0;                          // the 8-byte stores only if every plane of the launch allows them
     if ((hr = CheckHip(LaunchEncode420(ep, plan.in10, plan.out10, plan.siting, stream, run.n), "k_encode420")) || !histRows) return hr;
-    // the chunk's histograms: the frames of the surface are run.dsts[0] + i * frame stride (ProcessBatchYuv lays them out so)
-    const CRect a = ActiveRect();
-    MeasureParams mp{};
-    mp.src = (const uint8_t *)run.dsts[0]; mp.src_pitch = encode.src_pitch;
+    // the chunk's histograms: the frames of the surface are run.dsts[0] + i * frame stride (ProcessBatchYuv lays them out so: on 256 bytes)
+    MeasureParams mp = MeasureLaunchParams(encode.src_pitch, encode.w, ActiveRect());
+    mp.src = (const uint8_t *)run.dsts[0]; mp.hist = histRows;
     mp.frame_stride = run.n > 1 ? (size_t)((const uint8_t *)run.dsts[1] - (const uint8_t *)run.dsts[0]) : 0;
-    mp.hist = histRows;
-    mp.w = encode.w;
-    mp.left = a.left; mp.top = a.top; mp.right = a.right; mp.bottom = a.bottom;
-    mp.src16 = 1;                                       // as the pass above: frames on 256 bytes, the pitch a multiple of 16
     int launched = 0;
     const hipError_t e = LaunchMeasure(mp, plan.in10, stream, run.n, &launched);
     // (counted as the kernel launches it was: none for an empty active area, whose rows are only cleared)

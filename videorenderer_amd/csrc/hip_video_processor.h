@@ -124,7 +124,7 @@ private:
     void SetShaderConvertColorParams();                  // :813
     void SetShaderLuminanceParams();                     // :889
     HRESULT UpdatePlan();                                // UpdateTexures/UpdatePostScaleTexures/Update*scalingShaders
-    // Where a frame or a batch is queued, handed down by value from Process / ProcessBatchRoutes to every launch: the stream (the context's,
+    // Where a frame or a batch is queued, handed down by value from Process / PlaceBatch to every launch: the stream (the context's,
     // or a frame lane's) and, for single-frame launches, how many frames the host keeps side by side (FusedParams::inflight)
     struct RunOn { hipStream_t stream = nullptr; int inflight = 1; };
     HRESULT ConvertColorPass(const uint8_t *sample, const RunOn &on);     // :3048
@@ -200,7 +200,7 @@ private:
     void SaveDoviWalk(DoviWalkState *s) const;
     void RestoreDoviWalk(const DoviWalkState &s);
     // One batch call in flight, handed down by reference from ProcessBatch / ProcessBatchDovi to the launches: the frames, for a run of
-    // ProcessBatchDovi its per-frame RPU state, and the stream ProcessBatchRoutes put it on.  Nothing of it outlives the call.
+    // ProcessBatchDovi its per-frame RPU state, and the stream PlaceBatch put it on.  Nothing of it outlives the call.
     struct BatchRun {
         int n = 0;
         const void *const *srcs = nullptr;
@@ -211,7 +211,7 @@ private:
         const float *dvCm = nullptr;
         bool started = false;                          // m_evStart is in place already (error diffusion: in front of the first chunk)
         bool usedTables = false;                       // out: a whole-batch route read dvTab / dvCm
-        RunOn on;                                      // where the launches go: decided by ProcessBatchRoutes (until then: no stream)
+        RunOn on;                                      // where the launches go: decided by PlaceBatch (until then: no stream)
         BatchRun Slice(int at, int m) const {          // the frames [at, at + m), every per-frame pointer advanced together
             BatchRun r = *this;
             r.n = m; r.srcs += at; r.dsts += at;
@@ -221,7 +221,7 @@ private:
             return r;
         }
     };
-    // A ring slot (frame table, Dolby Vision tables) on loan: leaving scope records the slot's event on the stream the copy was queued on, that is
+    // A slot of a TableRing on loan: leaving scope records the slot's event on the stream the copy was queued on, that is
     // behind every launch queued there since, and the slot is rewritten only after that event.  Scope = the last launch that reads the slot.
     struct SlotLease {
         const void *dev = nullptr; hipEvent_t done = nullptr; hipStream_t stream = nullptr;
@@ -232,23 +232,45 @@ private:
         ~SlotLease() { if (done) (void)hipEventRecord(done, stream); }
         const FusedFrame *frames() const { return (const FusedFrame *)dev; }
     };
-    // a slot of a table ring (the frame tables of a batch, the Dolby Vision tables of a run): pinned host copy, device copy of `cap` bytes, and
-    // the event behind the last launch that reads it (SlotLease)
-    struct TableSlot { void *pinned = nullptr; size_t cap = 0; DevBuffer dev; hipEvent_t done = nullptr; void Release(); };
-    HRESULT AcquireSlot(TableSlot &slot, size_t bytes, size_t atLeast, hipStream_t stream, SlotLease *lease);
-    TableSlot m_dvSlots[2];
-    unsigned m_dvSlotNext = 0;
+    // A ring of table slots, so that the host can queue several batches ahead: a slot is a pinned host copy, a device copy and the event
+    // behind the last launch that reads the device copy (SlotLease).  The slots take turns; a table is filled, then sent
+    class TableRing {
+    public:
+        TableRing(CHipVideoProcessor *owner, int slots) : m_owner(owner), m_slots((size_t)slots) {}
+        // *pinned: the host copy of the slot whose turn it is, free to be rewritten (the host has waited for the launches behind its last lease; an
+        // event never recorded counts as complete) and large enough for `bytes` (allocated for `atLeast` or more: batches of growing size do not reallocate one by one)
+        HRESULT Next(size_t bytes, size_t atLeast, void **pinned);
+        // its first `bytes` to the device on `stream` (`what` names the copy in an error); *lease: the device copy on loan.  The turn passes on
+        HRESULT Send(size_t bytes, hipStream_t stream, const char *what, SlotLease *lease);
+        size_t Sent() const { return m_sent; }
+        void Release();
+    private:
+        struct Slot { void *pinned = nullptr; size_t cap = 0; DevBuffer dev; hipEvent_t done = nullptr; };
+        CHipVideoProcessor *m_owner;
+        std::vector<Slot> m_slots;
+        size_t m_sent = 0;             // tables sent so far: slot m_sent % slots is next
+    };
+    TableRing m_dvTableRing{this, 2};                 // the Dolby Vision tables of a run
     HRESULT UploadDoviTables(BatchRun *run, hipStream_t stream, SlotLease *lease);
     HRESULT ApplyDoviFrame(const DoviFrameState &f);
     std::string m_dvLastInfo;                         // the runs of the last batch call, if it was a ProcessBatchDovi (GetLastBatchInfo: ";dovi_runs=3:tables,1:frames")
     unsigned m_laneFrames = 0;                        // frames queued on the frame lanes (the timing pair is recorded on every n-th)
     unsigned m_launches = 0;                          // kernel launches so far (CheckHip) ...
     int m_lastBatchLane = -1;                                // the lane the last batch ran on (-1: the context stream)
-    unsigned m_tableUploads = 0;                             // UploadFrameTable calls so far
-    int m_lastBatchUploads = 0;                              // ... of the last batch call (a table of up to 32 frames travels in the exact-2x kernel's arguments: 0)
+    int m_lastBatchUploads = 0;                              // frame / plane tables the last batch call sent (a table of up to 32 frames travels in the exact-2x kernel's arguments: 0)
     int m_lastBatchFrames = 0, m_lastBatchLaunches = 0;      // ... and what the last batch call used
     HRESULT CheckTargetLayout(int n, void *const *dsts, int rtPitch);
-    HRESULT BeginBatch(int n, const void *const *srcs, void *const *dsts, int rtPitch);         // opens the call's record and checks what every batch entry point checks
+    // The record of a batch call (GetLastBatchInfo), open for as long as the call runs: every batch entry point starts with one, so a refused call reports an empty record
+    struct BatchRecord {
+        CHipVideoProcessor &vp; const unsigned launches; const size_t uploads;
+        BatchRecord(CHipVideoProcessor &v, int frames) : vp(v), launches(v.m_launches), uploads(v.m_tableRing.Sent())
+        {
+            vp.m_lastBatchFrames = frames; vp.m_lastBatchLaunches = vp.m_lastBatchUploads = 0; vp.m_lastBatchLane = -1; vp.m_lastBatchWaits = 0;
+            vp.m_dvLastInfo.clear(); vp.m_yuvLastInfo.clear();
+        }
+        ~BatchRecord() { vp.m_lastBatchLaunches = (int)(vp.m_launches - launches); vp.m_lastBatchUploads = (int)(vp.m_tableRing.Sent() - uploads); }     // (what the call launched and sent up to its return)
+    };
+    HRESULT CheckBatchArgs(int n, const void *const *srcs, void *const *dsts, int rtPitch);     // what the RGB batch entry points check, before anything is applied or queued
     HRESULT RunBatch(BatchRun &run);                  // a validated batch: the plan, then error diffusion or the routes
     HRESULT ProcessBatchRoutes(BatchRun &run);
     bool ToneMapActive() const;
@@ -319,11 +341,8 @@ private:
     DevBuffer m_axisX, m_axisY;
     AxisTaps m_tapsX{}, m_tapsY{};
     const int32_t *m_otherX = nullptr, *m_otherY = nullptr;
-    // ring of frame-table slots for mpcvr_process_batch (pinned host copy + device copy + completion event)
-    // (eight: a chunk of mpcvr_process_batch_yuv takes up to two, its frames' and its planes' — the host queues four such chunks before it waits for the first)
-    static constexpr int kFrameSlots = 8;
-    TableSlot m_slots[kFrameSlots];
-    int m_slotNext = 0;
+    // (eight slots: a chunk of mpcvr_process_batch_yuv takes up to two, its frames' and its planes' — the host queues four such chunks before it waits for the first)
+    TableRing m_tableRing{this, 8};        // the frame tables of mpcvr_process_batch and the plane tables of mpcvr_process_batch_yuv (GetLastBatchInfo's uploads=)
     uint16_t m_ditherHost[1024];
     // Frames and whole batches of a context that owns its stream overlap on the frame lanes (vp_lanes.h: the streams, what is in flight on
     // them and what orders it).  What may take a lane is decided here, from the plan: FrameLanesUsable for frames, BatchLaneEligible for batches
@@ -332,7 +351,7 @@ private:
     hipStream_t m_lastRun = nullptr;          // the stream the current sample's last Process ran on (MarkConsumed records there)
     bool FrameLanesUsable() const;
     // what a frame written through `rt` covers (RtSpan, vp_spans.h): the window's rows at this pitch
-    RtSpan TargetSpan(const void *rt, int rtPitch) const { return RtSpan{(uintptr_t)rt, (uintptr_t)rt + (size_t)std::max(m_windowRect.Height() - 1, 0) * (size_t)rtPitch + (size_t)m_windowRect.Width() * 4}; }
+    RtSpan TargetSpan(const void *rt, int rtPitch) const { return RowsSpan(rt, (size_t)rtPitch, m_windowRect.Height(), (size_t)m_windowRect.Width() * 4); }
     // host_wait: block until the lanes are idle; otherwise the context stream waits for them (work queued on it afterwards runs behind
     // every frame in flight)
     HRESULT JoinFrameLanes(bool host_wait) { return CheckHip(m_lanes.Join(host_wait, m_stream), "frame lane sync"); }
@@ -395,8 +414,11 @@ private:
         FusedParams conv{}, direct{};  // WholeBatchLaunches / DirectConvert (BatchPlan)
     };
     BatchRoutePlan ClassifyBatch(const BatchRun &run) const;
-    // may a batch of this route run on a batch lane beside the one before it?  The one predicate of ProcessBatchRoutes and ProcessBatchYuv
+    // may a batch of this route run on a batch lane beside the one before it?
     bool BatchLaneEligible(const BatchRoutePlan &rp, const BatchRun &run) const;
+    // where a classified batch runs and what it is ordered behind; `writes`: the spans it writes for the caller.  Sets run.on; returns the lane (-1: none)
+    int PlaceBatch(const BatchRoutePlan &rp, BatchRun &run, std::vector<RtSpan> &&writes);
+    void NoteBatchQueued(int lane) { if (lane >= 0) m_lanes.NoteLaneBatch(lane); }      // the batch PlaceBatch placed has been queued
     // mpcvr_process_batch_yuv: one RGB surface per batch lane (a lane's chunks write, read and reuse its surface in stream order); chunks on
     // the context stream use the first (they run behind everything the lanes hold, and the lanes' next work behind them)
     struct YuvSurface {
@@ -410,8 +432,8 @@ private:
     // one chunk: rp / run.dsts name the surface's frames, run.on the stream; `encode` holds the launch's pitches, size and coefficients
     HRESULT RunYuvChunk(BatchRoutePlan &rp, BatchRun &run, YuvSurface &surf, const EncodeParams &encode, const EncodePlan &plan,
                         void *const *yPlanes, void *const *uvPlanes, uint32_t *histRows);
-    // video rect ∩ window: the active picture the measure pass counts (may be empty)
-    CRect ActiveRect() const;
+    // video rect ∩ window: the active picture the measure pass counts (empty: all zero)
+    mpcvr_rect ActiveRect() const;
     HRESULT RunBatchRoute(BatchRoutePlan &rp, BatchRun &run);
     bool BatchPlan(const uint8_t *sample0, void *rt0, int rtPitch, bool aligned, bool repacked, bool src16, FusedParams *conv, FusedParams *direct) const;
     HRESULT ProcessBatchLaunches(const BatchRun &run, const FusedFrame *table, bool aligned, FusedParams conv);

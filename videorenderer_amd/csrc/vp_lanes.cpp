@@ -44,14 +44,6 @@ int FrameLanes::PickFrameLane(const RtSpan &rt)
     return (int)(pick - m_lanes);
 }
 
-int FrameLanes::PickBatchLane(int n, void *const *dsts, size_t bytes, int *waits)
-{
-    std::vector<RtSpan> spans;
-    spans.reserve((size_t)n);
-    for (int i = 0; i < n; i++) { RtSpan s; s.lo = (uintptr_t)dsts[i]; s.hi = s.lo + bytes; spans.push_back(s); }
-    return PickBatchLane(std::move(spans), waits);
-}
-
 int FrameLanes::PickBatchLane(std::vector<RtSpan> &&written, int *waits)
 {
     Lane *pick = &m_lanes[m_batchNext];
@@ -62,7 +54,6 @@ int FrameLanes::PickBatchLane(std::vector<RtSpan> &&written, int *waits)
     std::vector<RtSpan> &spans = m_batchSpans;
     spans = std::move(written);
     SortAndMergeSpans(spans);
-    *waits = 0;
     for (Lane &fl : m_lanes) {
         if (&fl == pick || !fl.stream) continue;
         for (Frame &f : fl.ring) {

@@ -34,11 +34,9 @@ public:
     // (stream order then keeps the two writes apart; further lanes holding such a frame are waited for), else the next in turn.  -1: no stream
     int PickFrameLane(const RtSpan &rt);
     // the lane of the batch about to be queued (the batch lanes take turns), ordered behind everything still in flight on OTHER lanes that
-    // writes into the bytes of one of its render targets [dsts[i], dsts[i] + bytes): single frames (their ring entries) and batches;
-    // *waits: how many such writers.  -1: no stream
-    int PickBatchLane(int n, void *const *dsts, size_t bytes, int *waits);
-    // the same for a batch that writes `spans` (any order, overlaps allowed; taken over): what mpcvr_process_batch_yuv passes for a chunk — the
-    // planes it leaves, not the context-owned surface it renders into on the way (that surface belongs to the lane: stream order covers it)
+    // writes into the bytes of `spans`: single frames (their ring entries) and batches; *waits grows by the number of such writers.  -1: no stream
+    // spans (any order, overlaps allowed; taken over): what the batch writes for the caller — the render targets of mpcvr_process_batch; of a chunk of
+    // mpcvr_process_batch_yuv the planes it leaves, not the context-owned surface it renders into on the way (the lane's own: stream order covers it)
     int PickBatchLane(std::vector<RtSpan> &&spans, int *waits);
     hipStream_t Stream(int lane) const { return m_lanes[lane].stream; }
     void NoteLaneFrame(int lane, const RtSpan &rt);   // the frame just queued on the lane writes `rt`

@@ -230,8 +230,7 @@ bool PlanBatchYuv(int w, int h, int n, size_t budget, BatchYuvLayout *out)
     if (!budget) budget = kBatchYuvDefaultBudget;
     out->surfacePitch = (4 * w + 15) & ~15;
     out->frameStride = ((size_t)out->surfacePitch * (size_t)h + 255) & ~(size_t)255;
-    const size_t fit = budget / out->frameStride;
-    out->framesPerChunk = (int32_t)(fit < 1 ? 1 : fit > (size_t)n ? (size_t)n : fit);
+    out->framesPerChunk = FramesPerChunk(n, out->frameStride, budget);
     out->chunks = (n + out->framesPerChunk - 1) / out->framesPerChunk;
     return true;
 }

@@ -212,4 +212,11 @@ bool DecidePlan(int iTexFormat, int iChromaScaling, int iUpscaling, int iDownsca
                 int bUseDither, int output_format, uint32_t flags, const FmtConvParams &f,
                 const PlanGeometry &g, PassPlan *plan, std::string *why);
 
+// The chunk rule of the batch paths: the frames of a batch of n >= 1 that go through an intermediate at a time — what fits the budget, at least one, at most n
+inline int FramesPerChunk(int n, size_t bytesPerFrame, size_t budget)
+{
+    const size_t fit = budget / (bytesPerFrame ? bytesPerFrame : 1);
+    return (int)(fit < 1 ? 1 : fit > (size_t)n ? (size_t)n : fit);
+}
+
 }  // namespace mpcvr

@@ -11,6 +11,8 @@ namespace mpcvr {
 // what a frame in flight writes: the bytes [lo, hi) from the first pixel of its render target to the last pixel of its last row (the padding
 // of the rows in between counts as written: rows of two targets that interleave in one surface are ordered like rows that overlap)
 struct RtSpan { uintptr_t lo = 0, hi = 0; bool Overlaps(const RtSpan &o) const { return lo < o.hi && o.lo < hi; } };
+// ... of a surface or a plane of `rows` rows of rowBytes at `pitch`: the one definition of what a target, a source or a plane covers
+inline RtSpan RowsSpan(const void *p, size_t pitch, int rows, size_t rowBytes) { return RtSpan{(uintptr_t)p, (uintptr_t)p + (size_t)std::max(rows - 1, 0) * pitch + rowBytes}; }
 
 // sorted by address, spans that overlap or touch merged into one: the result is disjoint, so both ends ascend
 inline void SortAndMergeSpans(std::vector<RtSpan> &v)
@@ -42,8 +44,8 @@ inline std::vector<RtSpan> BatchPlaneSpans(int n, void *const *y, int yPitch, vo
 {
     std::vector<RtSpan> v((size_t)2 * (size_t)n);
     for (int i = 0; i < n; i++) {
-        v[2 * i].lo = (uintptr_t)y[i]; v[2 * i].hi = v[2 * i].lo + (size_t)(h - 1) * (size_t)yPitch + rowBytes;
-        v[2 * i + 1].lo = (uintptr_t)uv[i]; v[2 * i + 1].hi = v[2 * i + 1].lo + (size_t)(h / 2 - 1) * (size_t)uvPitch + rowBytes;
+        v[2 * i] = RowsSpan(y[i], (size_t)yPitch, h, rowBytes);
+        v[2 * i + 1] = RowsSpan(uv[i], (size_t)uvPitch, h / 2, rowBytes);
     }
     return v;
 }
