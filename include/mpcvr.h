@@ -343,6 +343,55 @@ int32_t mpcvr_light_level_from_histogram(const uint32_t hist[MPCVR_HIST_BINS], i
  * largest non-empty bin).  MPCVR_E_POINTER for a NULL pointer, MPCVR_E_INVALIDARG for ppm out of range or an empty histogram. */
 int32_t mpcvr_histogram_percentile(const uint32_t hist[MPCVR_HIST_BINS], uint32_t ppm, int32_t *code);
 
+/* EXTENSION — the rendered frame as the float tensor a model takes: fp32 / fp16 / bf16, C,H,W or H,W,C, RGB or BGR, value = code * scale
+ * + bias per channel (1 / 255 and 0, or a dataset's mean / std folded in).  The reference has no float output; there is no reference line
+ * to cite.  The definition is the text below, modelled bit for bit by tests/tensor_model.py (arithmetic: csrc/vp_tensor_core.h, which the
+ * kernel and mpcvr_plan_tensor_value both compile).
+ *   Input, as for mpcvr_encode_pass / mpcvr_measure_pass: a DEVICE surface of w x h 32-bit texels, src_fmt = MPCVR_OUT_BGRA8 (codes 0 ..
+ *   255) or MPCVR_OUT_RGB10A2 (0 .. 1023), the A / X bits ignored; src and src_pitch multiples of 4, src_pitch >= 4 w; w and h in 1 ..
+ *   32768, odd sizes allowed.  There is no rectangle: a caller crops by offsetting src.
+ *   Arithmetic, per channel k = R, G, B of the picture (whatever the channel order), c = the channel's code, an integer:
+ *       t = fp32(c) * scale[k], rounded to fp32;   v = t + bias[k], rounded to fp32
+ *   — two IEEE round-to-nearest-even operations, NOT a fused multiply-add.  F32 stores v.  F16 stores v rounded to nearest even to binary16:
+ *   overflow goes to +-inf, fp16 subnormals are kept.  BF16 stores (u + 0x7FFF + ((u >> 16) & 1)) >> 16 of v's bits u (nearest even).
+ *   scale[k] and bias[k] must be finite, and 0 or of magnitude in [2^-100, 2^100]; otherwise MPCVR_E_INVALIDARG.  With that no fp32
+ *   subnormal, infinity or NaN can arise: t is 0 or in [2^-100, 1023 * 2^100], and t + bias[k] is a sum of two multiples of 2^-123 below
+ *   2^111, so it is 0 or at least 2^-123 — results do not depend on a flush-to-zero mode.
+ *   Output: element size es = 4, 2, 2 bytes for F32, F16, BF16.  dst, row_pitch and (planar) plane_pitch are multiples of es — not of 4: a
+ *   contiguous fp16 tensor of odd width is accepted.  Pitches are positive; row_pitch >= w es (planar) or 3 w es (interleaved).
+ *   PLANAR: channel k of the tensor starts at dst + k plane_pitch, row y at + y row_pitch, column x at + x es.  INTERLEAVED: row y at
+ *   dst + y row_pitch, pixel x holds its three elements at 3 x es.  channel_order says which of R, G, B is channel 0, 1, 2 of the tensor.
+ *   No byte outside the elements is written: not the pitch padding, nothing in front of, between or behind planes.  Vector loads and
+ *   stores are taken where pointers and pitches allow them (source on 16 bytes; tensor on 16 bytes for F32, 8 for F16 / BF16).
+ * Refusals, with nothing launched and nothing written: MPCVR_E_POINTER for a NULL src, desc or dst; MPCVR_E_INVALIDARG for another src_fmt,
+ * dtype, layout or channel_order, reserved != 0, w or h out of range, a pointer or pitch that breaks the rules above (a pitch beyond 2^47
+ * bytes included), a scale or bias outside the set above, and a plane (first element to last element of its last row; for INTERLEAVED the
+ * whole tensor is one plane) that overlaps another plane or the source. */
+enum { MPCVR_TENSOR_F32 = 0, MPCVR_TENSOR_F16 = 1, MPCVR_TENSOR_BF16 = 2 };
+enum { MPCVR_TENSOR_PLANAR = 0 /* C,H,W */, MPCVR_TENSOR_INTERLEAVED = 1 /* H,W,C */ };
+enum { MPCVR_TENSOR_RGB = 0, MPCVR_TENSOR_BGR = 1 };      /* channel 0,1,2 of the tensor */
+typedef struct mpcvr_tensor_desc {
+    int32_t dtype, layout, channel_order, reserved;        /* reserved must be 0 */
+    int64_t row_pitch;      /* bytes between rows */
+    int64_t plane_pitch;    /* bytes between channel planes; PLANAR only, ignored otherwise */
+    float   scale[3], bias[3];                             /* for R, G, B of the picture, whatever the channel order */
+} mpcvr_tensor_desc;
+/* Host, no GPU: *bits = the stored bits of one element (the low 16 for F16 / BF16) for a channel code of a src_fmt surface.
+ * MPCVR_E_POINTER for a NULL bits; MPCVR_E_INVALIDARG for another dtype or src_fmt, a code beyond 255 / 1023, a scale or bias outside the
+ * set above. */
+int32_t mpcvr_plan_tensor_value(int32_t dtype, int32_t src_fmt, uint32_t code, float scale, float bias, uint32_t *bits);
+/* One standalone pass over one device surface, like mpcvr_encode_pass; stream = a hipStream_t or NULL.  One kernel launch (k_tensor,
+ * csrc/vp_tensor.hip). */
+int32_t mpcvr_tensor_pass(const void *src, int32_t src_pitch, int32_t src_fmt, int32_t w, int32_t h, const mpcvr_tensor_desc *desc,
+                          void *dst, void *stream);
+/* mpcvr_render, then the pass over the whole window, ordered exactly as mpcvr_render_yuv: Process into the context-owned back buffer with
+ * the letterbox cleared to black, on the context stream (not on a frame lane; the pixels are the same), the pass queued behind it, and
+ * everything queued later, lanes included, behind the pass.  The tensor is complete after mpcvr_synchronize; mpcvr_get_backbuffer and
+ * mpcvr_get_displayed_image afterwards see the RGB frame a plain mpcvr_render leaves.  The source format is the context's output_format
+ * (bUseDither = 0 with MPCVR_OUT_RGB10A2 gives a model 10-bit codes without dither noise).  Everything mpcvr_tensor_pass refuses about
+ * desc and dst is answered before anything is drawn.  S_FALSE, with nothing drawn or written, when there is no sample (as mpcvr_render). */
+int32_t mpcvr_render_tensor(mpcvr_ctx *ctx, int32_t field, const mpcvr_tensor_desc *desc, void *dst);
+
 /* Configure — DX11VideoProcessor.cpp:3800-4050: diff each field, rebuild only what changed. */
 int32_t mpcvr_configure(mpcvr_ctx *ctx, const mpcvr_settings *settings);
 
@@ -513,6 +562,26 @@ int32_t mpcvr_process_batch_yuv(mpcvr_ctx *ctx, int32_t n, const void *const *sr
 int32_t mpcvr_process_batch_yuv_stats(mpcvr_ctx *ctx, int32_t n, const void *const *srcs, int32_t out_cformat, uint32_t extfmt,
                                       void *const *y_planes, int32_t y_pitch, void *const *uv_planes, int32_t uv_pitch,
                                       uint32_t *hist_dev /* n rows of 1024 words, frame i at hist_dev + 1024 i */);
+/* EXTENSION — a batch written as float tensors (mpcvr_process_batch for a model; the pass itself: mpcvr_tensor_pass above).  dsts[i] is
+ * the tensor of frame i, all n described by one desc.  Frame i holds, byte for byte, what
+ *     mpcvr_process_batch(srcs -> n window-sized RGB targets of the context's output_format, black outside the video rect), then
+ *     mpcvr_tensor_pass(target i, output_format, window_w, window_h, desc, dsts[i])
+ * leave, with ONE k_tensor launch per chunk of frames (its frame dimension) where the composition takes n.  The machinery is that of
+ * mpcvr_process_batch_yuv: the RGB frames live in the same context-owned surfaces (one per batch lane used), laid out by
+ * mpcvr_plan_batch_tensor — the three formulas of mpcvr_plan_batch_yuv without the evenness condition (window width and height 1 .. 32768,
+ * otherwise MPCVR_E_INVALIDARG) — under the same budget: mpcvr_set_batch_yuv_budget serves both calls.  Chunks, routes, the letterbox and
+ * the order are as described there: the chunks of lane routes take turns on the two batch lanes, each with the lane's surface, everything
+ * else runs on the context stream.  Every plane of every frame (three per PLANAR frame, one per INTERLEAVED frame) counts as bytes the
+ * chunk writes: single frames, batches and further calls that write memory a plane in flight covers stay behind it in queue order.  The
+ * tensors are complete after mpcvr_synchronize.
+ * Refusals, answered before anything is drawn, allocated or written: MPCVR_E_NOT_VALID_STATE before mpcvr_set_input; MPCVR_E_POINTER for
+ * a NULL array, entry or desc; MPCVR_E_INVALIDARG for n <= 0, whatever mpcvr_tensor_pass refuses about desc and a dsts[i], and any two
+ * planes of the batch that overlap each other.
+ * mpcvr_get_last_batch_info afterwards: "launches" counts one pass per chunk, and ";tensor_chunks=<k>;tensor_lanes=<lane,lane,...>"
+ * follow (the lane of each chunk, -1 = the context stream; the first 64 chunks). */
+int32_t mpcvr_plan_batch_tensor(int32_t window_w, int32_t window_h, int32_t n, size_t budget_bytes,
+                                int32_t *surface_pitch, size_t *frame_stride, int32_t *frames_per_chunk, int32_t *chunks);
+int32_t mpcvr_process_batch_tensor(mpcvr_ctx *ctx, int32_t n, const void *const *srcs, const mpcvr_tensor_desc *desc, void *const *dsts);
 
 /* Multi-GPU: the parameter blob (colour matrix, luminance scale, gamut matrix, resize phase weights,
  * dither table) a rank-0 context computes and every other rank adopts after an RCCL broadcast.

@@ -151,6 +151,25 @@ class LightLevel(C.Structure):         # mpcvr_light_level
     _fields_ = [("pixels", C.c_uint64), ("min_code", C.c_int32), ("max_code", C.c_int32), ("max_nits", C.c_double), ("avg_nits", C.c_double)]
 
 
+TENSOR_F32, TENSOR_F16, TENSOR_BF16 = 0, 1, 2
+TENSOR_PLANAR, TENSOR_INTERLEAVED = 0, 1          # C,H,W / H,W,C
+TENSOR_RGB, TENSOR_BGR = 0, 1
+
+
+class TensorDesc(C.Structure):         # mpcvr_tensor_desc
+    _fields_ = [("dtype", C.c_int32), ("layout", C.c_int32), ("channel_order", C.c_int32), ("reserved", C.c_int32),
+                ("row_pitch", C.c_int64), ("plane_pitch", C.c_int64), ("scale", C.c_float * 3), ("bias", C.c_float * 3)]
+
+
+def tensor_desc(dtype, layout, row_pitch, plane_pitch=0, scale=(1 / 255,) * 3, bias=(0,) * 3, channel_order=TENSOR_RGB):
+    """(extension) An mpcvr_tensor_desc: dtype TENSOR_F32 / F16 / BF16, layout TENSOR_PLANAR / INTERLEAVED, pitches in bytes, scale and
+    bias for R, G, B of the picture (rounded to fp32 here, as the C struct holds them)."""
+    d = TensorDesc(int(dtype), int(layout), int(channel_order), 0, int(row_pitch), int(plane_pitch))
+    for k in range(3):
+        d.scale[k], d.bias[k] = float(scale[k]), float(bias[k])
+    return d
+
+
 class MpcvrError(RuntimeError):
     def __init__(self, hr, msg):
         super().__init__(f"HRESULT 0x{hr & 0xffffffff:08X}: {msg}")
@@ -175,6 +194,7 @@ EXPORTS = [
     "mpcvr_plan_batch_yuv", "mpcvr_set_batch_yuv_budget", "mpcvr_process_batch_yuv",
     "mpcvr_measure_pass", "mpcvr_measure_backbuffer", "mpcvr_process_batch_yuv_stats",
     "mpcvr_light_level_from_histogram", "mpcvr_histogram_percentile",
+    "mpcvr_plan_tensor_value", "mpcvr_tensor_pass", "mpcvr_render_tensor", "mpcvr_plan_batch_tensor", "mpcvr_process_batch_tensor",
 ]
 
 _lib = None
@@ -281,6 +301,11 @@ def load_library():
         "mpcvr_process_batch_yuv_stats": [vp, i32, P(vp), i32, u32, P(vp), i32, P(vp), i32, vp],
         "mpcvr_light_level_from_histogram": [vp, i32, P(LightLevel)],
         "mpcvr_histogram_percentile": [vp, u32, P(i32)],
+        "mpcvr_plan_tensor_value": [i32, i32, u32, f, f, P(u32)],
+        "mpcvr_tensor_pass": [vp, i32, i32, i32, i32, P(TensorDesc), vp, vp],
+        "mpcvr_render_tensor": [vp, i32, P(TensorDesc), vp],
+        "mpcvr_plan_batch_tensor": [i32, i32, i32, C.c_size_t, P(i32), P(C.c_size_t), P(i32), P(i32)],
+        "mpcvr_process_batch_tensor": [vp, i32, P(vp), P(TensorDesc), P(vp)],
     }
     for name, args in sig.items():
         if lib_path != LIB_PATH and not hasattr(L, name):
@@ -438,6 +463,51 @@ def histogram_percentile(hist, ppm):
     if hr:
         raise MpcvrError(hr, "mpcvr_histogram_percentile")
     return code.value
+
+
+def plan_tensor_value(dtype, src_fmt, code, scale, bias):
+    """(extension) The stored bits of one element of the tensor pass (include/mpcvr.h: mpcvr_plan_tensor_value): fp32 bits, or the 16 bits
+    of fp16 / bf16, of code * scale + bias for a channel code of a BGRA8 (0) / RGB10A2 (1) surface.  No GPU needed."""
+    bits = C.c_uint32()
+    hr = load_library().mpcvr_plan_tensor_value(int(dtype), int(src_fmt), int(code), float(scale), float(bias), C.byref(bits))
+    if hr:
+        raise MpcvrError(hr, "mpcvr_plan_tensor_value")
+    return bits.value
+
+
+def tensor_pass(src, src_pitch, src_fmt, w, h, desc, dst, stream=None):
+    """(extension) One device surface of 32-bit RGB texels (src_fmt: 0 = BGRA8, 1 = RGB10A2) written as the float tensor `desc`
+    (tensor_desc) describes at `dst` (device tensor or address) (include/mpcvr.h: mpcvr_tensor_pass).  Complete in stream order."""
+    hr = load_library().mpcvr_tensor_pass(C.c_void_p(_ptr(src)), int(src_pitch), int(src_fmt), int(w), int(h),
+                                          C.byref(desc) if desc is not None else None, C.c_void_p(_ptr(dst)), C.c_void_p(stream) if stream else None)
+    if hr:
+        raise MpcvrError(hr, "mpcvr_tensor_pass")
+
+
+def plan_batch_tensor(window_w, window_h, n, budget_bytes=0):
+    """(extension) The layout integers of mpcvr_process_batch_tensor (include/mpcvr.h: mpcvr_plan_batch_tensor): plan_batch_yuv's formulas
+    for a window of any parity.  No GPU needed."""
+    pitch, fpc, chunks, stride = C.c_int32(), C.c_int32(), C.c_int32(), C.c_size_t()
+    hr = load_library().mpcvr_plan_batch_tensor(int(window_w), int(window_h), int(n), int(budget_bytes), C.byref(pitch), C.byref(stride), C.byref(fpc), C.byref(chunks))
+    if hr:
+        raise MpcvrError(hr, "mpcvr_plan_batch_tensor")
+    return dict(surface_pitch=pitch.value, frame_stride=stride.value, frames_per_chunk=fpc.value, chunks=chunks.value)
+
+
+def _tensor_dtype(dt):
+    """torch dtype -> TENSOR_*"""
+    import torch
+    try:
+        return {torch.float32: TENSOR_F32, torch.float16: TENSOR_F16, torch.bfloat16: TENSOR_BF16}[dt]
+    except KeyError:
+        raise ValueError("a tensor of float32, float16 or bfloat16, not %s" % (dt,)) from None
+
+
+def _tensor_order(channel_order):
+    try:
+        return {"rgb": TENSOR_RGB, "bgr": TENSOR_BGR}[channel_order]
+    except KeyError:
+        raise ValueError("channel_order 'rgb' or 'bgr'") from None
 
 
 def plan_batch_yuv(window_w, window_h, n, budget_bytes=0):
@@ -730,6 +800,59 @@ class VideoProcessor:
             y, uv = y[:, :ww], uv[:, :ww]
         return y, uv
 
+    def _window_size(self):
+        if getattr(self, "_window", None) is not None:
+            return self._window[2] - self._window[0], self._window[3] - self._window[1]
+        return self.GetBackBuffer()[2:]            # (the window was not set through this object: the last Render knows it)
+
+    def RenderTensor(self, dtype=None, layout="chw", channel_order="rgb", scale=(1 / 255,) * 3, bias=(0,) * 3, out=None, field=1):
+        """(extension) Render, then the back buffer as a float tensor (mpcvr_render_tensor): value = code * scale + bias per channel of the
+        picture (R, G, B), as (3, H, W) for layout "chw" or (H, W, 3) for "hwc", torch.float16 unless `dtype` says float32 / bfloat16.
+        `out`: a device tensor of that shape to write into (its dtype and strides are used; the last dim(s) dense); else one is allocated.
+        Complete after Synchronize; None when there is no sample."""
+        import torch
+        if layout not in ("chw", "hwc"):
+            raise ValueError("layout 'chw' or 'hwc'")
+        ww, wh = self._window_size()
+        shape = (3, wh, ww) if layout == "chw" else (wh, ww, 3)
+        if out is None:
+            out = torch.empty(shape, dtype=dtype or torch.float16, device=f"cuda:{self.device}")
+        elif tuple(out.shape) != shape or (dtype is not None and out.dtype != dtype):
+            raise ValueError("out must be a %s tensor of shape %s" % (dtype or "float", shape))
+        es = out.element_size()
+        if layout == "chw":
+            if out.stride(2) != 1:
+                raise ValueError("the last dim of a (3, H, W) tensor must be dense")
+            d = tensor_desc(_tensor_dtype(out.dtype), TENSOR_PLANAR, out.stride(1) * es, out.stride(0) * es, scale, bias, _tensor_order(channel_order))
+        else:
+            if out.stride(2) != 1 or out.stride(1) != 3:
+                raise ValueError("the last two dims of an (H, W, 3) tensor must be dense")
+            d = tensor_desc(_tensor_dtype(out.dtype), TENSOR_INTERLEAVED, out.stride(0) * es, 0, scale, bias, _tensor_order(channel_order))
+        hr = self._check(self._L.mpcvr_render_tensor(self._ctx, field, C.byref(d), C.c_void_p(out.data_ptr())))
+        return None if hr == S_FALSE else out
+
+    def ProcessBatchTensor(self, srcs, out, scale=(1 / 255,) * 3, bias=(0,) * 3, channel_order="rgb"):
+        """(extension) ProcessBatch with the frames written as float tensors (mpcvr_process_batch_tensor): `out` is a device tensor of
+        (N, 3, H, W) — stride(-1) == 1 — or (N, H, W, 3) — the last two dims dense — with N = len(srcs) and H x W the window; dtype, layout,
+        pitches and the per-frame pointers are read from it (any batch stride: a slice of a larger tensor works).  Anything else raises
+        before any call.  Complete after Synchronize; GetLastBatchInfo adds tensor_chunks / tensor_lanes."""
+        n = len(srcs)
+        if n < 1 or out.dim() != 4 or out.shape[0] != n or not out.is_cuda:
+            raise ValueError("out must be a device tensor of (len(srcs), 3, H, W) or (len(srcs), H, W, 3)")
+        ww, wh = self._window_size()
+        es = out.element_size()
+        if tuple(out.shape[1:]) == (3, wh, ww) and out.stride(3) == 1:
+            d = tensor_desc(_tensor_dtype(out.dtype), TENSOR_PLANAR, out.stride(2) * es, out.stride(1) * es, scale, bias, _tensor_order(channel_order))
+        elif tuple(out.shape[1:]) == (wh, ww, 3) and out.stride(3) == 1 and out.stride(2) == 3:
+            d = tensor_desc(_tensor_dtype(out.dtype), TENSOR_INTERLEAVED, out.stride(1) * es, 0, scale, bias, _tensor_order(channel_order))
+        else:
+            raise ValueError("out of shape %s / strides %s is neither (N, 3, %d, %d) with a dense last dim nor (N, %d, %d, 3) with the last two dims dense"
+                             % (tuple(out.shape), out.stride(), wh, ww, wh, ww))
+        arr = C.c_void_p * n
+        keep = (arr(*[_ptr(s) for s in srcs]), arr(*[out.data_ptr() + i * out.stride(0) * es for i in range(n)]), d, (srcs, out))
+        self._keep = keep
+        return self._check(self._L.mpcvr_process_batch_tensor(self._ctx, n, keep[0], C.byref(d), keep[1]))
+
     def MeasureBackBuffer(self, hist=None):
         """(extension) The histogram of max(R, G, B) of the frame the last Render / RenderYuv left, over video rect ∩ window
         (mpcvr_measure_backbuffer): a device tensor of 1024 int32 words holding the uint32 counts (allocated when `hist` is None), complete
@@ -859,13 +982,15 @@ class VideoProcessor:
         return buf.value.decode()
 
     def GetLastBatchInfo(self):
-        """'frames=<n>;launches=<kernel launches>;lane=<0 | 1: the batch ran on that lane beside its predecessor, -1: on the context stream>;waits=<frames / batches still in flight on other lanes, into memory this batch's targets overlap, that it was ordered behind>[;dovi_runs=...]' of the last ProcessBatch / ProcessBatchDovi / ProcessBatchYuv call, as a dict; behind a ProcessBatchYuv also yuv_chunks and yuv_lanes (the lane of each chunk)."""
+        """'frames=<n>;launches=<kernel launches>;lane=<0 | 1: the batch ran on that lane beside its predecessor, -1: on the context stream>;waits=<frames / batches still in flight on other lanes, into memory this batch's targets overlap, that it was ordered behind>[;dovi_runs=...]' of the last ProcessBatch / ProcessBatchDovi / ProcessBatchYuv call, as a dict; behind a ProcessBatchYuv also yuv_chunks and yuv_lanes (the lane of each chunk), behind a ProcessBatchTensor tensor_chunks and tensor_lanes."""
         buf = C.create_string_buffer(512)
         self._check(self._L.mpcvr_get_last_batch_info(self._ctx, buf, 512))
         d = dict(kv.split("=", 1) for kv in buf.value.decode().split(";"))
         out = dict(frames=int(d["frames"]), launches=int(d["launches"]), dovi_runs=d.get("dovi_runs", ""), lane=int(d.get("lane", -1)), waits=int(d.get("waits", 0)), uploads=int(d.get("uploads", -1)))
         if "yuv_chunks" in d:        # (only behind a ProcessBatchYuv: the lane of each chunk, -1 = the context stream)
             out.update(yuv_chunks=int(d["yuv_chunks"]), yuv_lanes=[int(x) for x in d["yuv_lanes"].split(",") if x])
+        if "tensor_chunks" in d:     # (only behind a ProcessBatchTensor, likewise)
+            out.update(tensor_chunks=int(d["tensor_chunks"]), tensor_lanes=[int(x) for x in d["tensor_lanes"].split(",") if x])
         return out
 
     def GetLastProcessMs(self):

@@ -46,6 +46,7 @@ SOURCES = [
     ("vp_errdiff.hip", []),
     ("vp_encode.hip", []),
     ("vp_measure.hip", []),
+    ("vp_tensor.hip", []),
     ("vp_probe.hip", []),
 ]
 

@@ -1690,7 +1690,7 @@ std::string CHipVideoProcessor::GetLastBatchInfo() const
     std::string s = "frames=" + std::to_string(m_lastBatchFrames) + ";launches=" + std::to_string(m_lastBatchLaunches) + ";lane=" + std::to_string(m_lastBatchLane) + ";waits=" + std::to_string(m_lastBatchWaits) +
                     ";uploads=" + std::to_string(m_lastBatchUploads);
     if (!m_dvLastInfo.empty()) s += ";dovi_runs=" + m_dvLastInfo;
-    s += m_yuvLastInfo;            // (";yuv_chunks=..;yuv_lanes=.." behind a ProcessBatchYuv, empty otherwise)
+    s += m_yuvLastInfo;            // (";yuv_chunks=..;yuv_lanes=.." behind a ProcessBatchYuv, ";tensor_chunks=..;tensor_lanes=.." behind a ProcessBatchTensor, empty otherwise)
     return s;
 }
 
@@ -1897,6 +1897,22 @@ HRESULT CHipVideoProcessor::ProcessBatchYuv(int n, const void *const *srcs, int 
     HRESULT hr = MPCVR_S_OK;
     if (m_planDirty && (hr = UpdatePlan())) return hr;
     const EncodeParams ep = EncodeLaunchParams(plan, w, h, lay.surfacePitch, yPitch, uvPitch);      // (src16 holds for every chunk: every frame of a surface starts on 256 bytes)
+    return RunSurfaceChunks(n, srcs, lay, "yuv",
+        [&](int at, int m) {
+            std::vector<RtSpan> writes(planes.begin() + 2 * (size_t)at, planes.begin() + 2 * (size_t)(at + m));
+            if (histDev) writes.push_back(RtSpan{(uintptr_t)histDev + kHistRow * (size_t)at, (uintptr_t)histDev + kHistRow * (size_t)(at + m)});
+            return writes;
+        },
+        [&](BatchRun &run, int at) { return EncodeChunk(run, ep, plan, yPlanes + at, uvPlanes + at, histDev ? histDev + (size_t)kHistBins * (size_t)at : nullptr); });
+}
+
+// The chunk loop of the batch calls that render into a context-owned surface and run one pass per chunk behind it (ProcessBatchYuv,
+// ProcessBatchTensor): writesOf(at, m) names the bytes the chunk of frames [at, at + m) writes for the caller, pass(run, at) queues the
+// chunk's pass on run.on.stream (run.dsts: the chunk's frames in the surface).  `tag` names the call in GetLastBatchInfo.
+template <class WritesOf, class Pass>
+HRESULT CHipVideoProcessor::RunSurfaceChunks(int n, const void *const *srcs, const BatchYuvLayout &lay, const char *tag, WritesOf writesOf, Pass pass)
+{
+    HRESULT hr = MPCVR_S_OK;
     const int most = lay.framesPerChunk;
     std::vector<void *> frames((size_t)most);
     auto surfaceFrames = [&](YuvSurface &s) -> HRESULT {       // the surface for `most` frames, and their addresses
@@ -1914,34 +1930,38 @@ HRESULT CHipVideoProcessor::ProcessBatchYuv(int n, const void *const *srcs, int 
         YuvSurface *surf = &m_yuvSurf[0];
         if ((hr = surfaceFrames(*surf))) break;
         BatchRoutePlan rp = m_plan.errdiff ? BatchRoutePlan{} : ClassifyBatch(run);     // (an error-diffusion plan classifies its own chunks: the default is no lane route)
-        std::vector<RtSpan> writes(planes.begin() + 2 * (size_t)at, planes.begin() + 2 * (size_t)(at + m));
-        if (histDev) writes.push_back(RtSpan{(uintptr_t)histDev + kHistRow * (size_t)at, (uintptr_t)histDev + kHistRow * (size_t)(at + m)});
-        const int bl = PlaceBatch(rp, run, std::move(writes));
+        const int bl = PlaceBatch(rp, run, writesOf(at, m));
         if (bl > 0) {                                   // another lane, another surface: the route is planned for the targets it draws into
             surf = &m_yuvSurf[bl];
             if ((hr = surfaceFrames(*surf))) break;
             rp = ClassifyBatch(run);
         }
         if (chunks < 64) lanes += (chunks ? "," : "") + std::to_string(bl);
-        hr = RunYuvChunk(rp, run, *surf, ep, plan, yPlanes + at, uvPlanes + at, histDev ? histDev + (size_t)kHistBins * (size_t)at : nullptr);
+        if (!(hr = RenderChunk(rp, run, *surf))) hr = pass(run, at);
         NoteBatchQueued(bl);
     }
-    m_yuvLastInfo = ";yuv_chunks=" + std::to_string(chunks) + ";yuv_lanes=" + lanes;
+    m_yuvLastInfo = std::string(";") + tag + "_chunks=" + std::to_string(chunks) + ";" + tag + "_lanes=" + lanes;
     return hr;
 }
 
-HRESULT CHipVideoProcessor::RunYuvChunk(BatchRoutePlan &rp, BatchRun &run, YuvSurface &surf, const EncodeParams &encode,
-                                        const EncodePlan &plan, void *const *yPlanes, void *const *uvPlanes, uint32_t *histRows)
+// the chunk's frames into the surface: the batch machinery on run.on.stream
+HRESULT CHipVideoProcessor::RenderChunk(BatchRoutePlan &rp, BatchRun &run, YuvSurface &surf)
 {
     hipStream_t const stream = run.on.stream;
-    HRESULT hr;
     // Process never writes the letterbox: black once per allocation and per window / video rect, in front of the first chunk that draws there
     if (!surf.cleared || surf.window != m_windowRect || surf.video != m_videoRect) {
-        if ((hr = CheckHip(hipMemsetAsync(surf.buf.ptr, 0, surf.buf.size, stream), "clear batch RGB surface"))) return hr;
+        if (HRESULT hr = CheckHip(hipMemsetAsync(surf.buf.ptr, 0, surf.buf.size, stream), "clear batch RGB surface")) return hr;
         surf.cleared = true; surf.window = m_windowRect; surf.video = m_videoRect;
     }
     // (the error-diffusion plan runs its own chunks and its pass on the context stream: `run` is on it, BatchLaneEligible refuses such a plan)
-    if ((hr = m_plan.errdiff ? ProcessBatchErrDiff(run) : RunBatchRoute(rp, run))) return hr;
+    return m_plan.errdiff ? ProcessBatchErrDiff(run) : RunBatchRoute(rp, run);
+}
+
+HRESULT CHipVideoProcessor::EncodeChunk(BatchRun &run, const EncodeParams &encode, const EncodePlan &plan, void *const *yPlanes, void *const *uvPlanes,
+                                        uint32_t *histRows)
+{
+    hipStream_t const stream = run.on.stream;
+    HRESULT hr;
     // the planes' table through the frame tables' ring; the lease ends behind the pass
     SlotLease table;
     EncodeFrame *fr;
@@ -1954,7 +1974,7 @@ HRESULT CHipVideoProcessor::RunYuvChunk(BatchRoutePlan &rp, BatchRun &run, YuvSu
     if ((hr = m_tableRing.Send(sizeof(EncodeFrame) * run.n, stream, "plane table", &table))) return hr;
     ep.frames = (const EncodeFrame *)table.dev;
     if ((hr = CheckHip(LaunchEncode420(ep, plan.in10, plan.out10, plan.siting, stream, run.n), "k_encode420")) || !histRows) return hr;
-    // the chunk's histograms: the frames of the surface are run.dsts[0] + i * frame stride (ProcessBatchYuv lays them out so: on 256 bytes)
+    // the chunk's histograms: the frames of the surface are run.dsts[0] + i * frame stride (RunSurfaceChunks lays them out so: on 256 bytes)
     MeasureParams mp = MeasureLaunchParams(encode.src_pitch, encode.w, ActiveRect());
     mp.src = (const uint8_t *)run.dsts[0]; mp.hist = histRows;
     mp.frame_stride = run.n > 1 ? (size_t)((const uint8_t *)run.dsts[1] - (const uint8_t *)run.dsts[0]) : 0;
@@ -1962,6 +1982,142 @@ HRESULT CHipVideoProcessor::RunYuvChunk(BatchRoutePlan &rp, BatchRun &run, YuvSu
     const hipError_t e = LaunchMeasure(mp, plan.in10, stream, run.n, &launched);
     // (counted as the kernel launches it was: none for an empty active area, whose rows are only cleared)
     return launched ? CheckHip(e, "k_measure_maxrgb") : CheckHip(e, "clear histogram rows");
+}
+
+// ------------------------------------------------------------------------------------------------
+// EXTENSION — the frame as the float tensor a model takes (include/mpcvr.h: mpcvr_tensor_pass, mpcvr_render_tensor,
+// mpcvr_process_batch_tensor; kernel: vp_tensor.hip).  No reference line: the reference has no float output.
+// ------------------------------------------------------------------------------------------------
+// the planes of one tensor (first element to last element of the last row): three for C,H,W, the whole tensor for H,W,C; returns how many
+static int TensorPlaneSpans(const mpcvr_tensor_desc &d, const void *dst, int w, int h, RtSpan out[3])
+{
+    const size_t es = (size_t)TensorElementSize(d.dtype);
+    if (d.layout == TN_INTERLEAVED) { out[0] = RowsSpan(dst, (size_t)d.row_pitch, h, 3 * es * (size_t)w); return 1; }
+    for (int k = 0; k < 3; k++) out[k] = RowsSpan((const uint8_t *)dst + (size_t)k * (size_t)d.plane_pitch, (size_t)d.row_pitch, h, es * (size_t)w);
+    return 3;
+}
+
+// What a k_tensor launch is given, but for its pointers: src / dst or the frame table are the caller's, who takes src16 / dstvec back where
+// a pointer of the launch is off the grid (here they say what the pitches allow), as in EncodeLaunchParams
+static TensorParams TensorLaunchParams(const mpcvr_tensor_desc &d, int w, int h, int srcPitch)
+{
+    TensorParams p{};
+    p.src_pitch = srcPitch; p.w = w; p.h = h;
+    p.row_pitch = d.row_pitch; p.plane_pitch = d.layout == TN_PLANAR ? d.plane_pitch : 0;
+    std::memcpy(p.scale, d.scale, sizeof(p.scale));
+    std::memcpy(p.bias, d.bias, sizeof(p.bias));
+    p.bgr = d.channel_order == MPCVR_TENSOR_BGR;
+    p.src16 = (srcPitch & 15) == 0;
+    p.dstvec = ((p.row_pitch | p.plane_pitch) & (TensorVectorBytes(d.dtype) - 1)) == 0;
+    return p;
+}
+
+HRESULT TensorSurface(const void *src, int srcPitch, int srcFmt, int w, int h, const mpcvr_tensor_desc *desc, void *dst, hipStream_t stream,
+                      bool checkOnly, const char **why)
+{
+    const char *dummy;
+    if (!why) why = &dummy;
+    if ((!src && !checkOnly) || !desc || !dst) { *why = "null surface, description or tensor"; return MPCVR_E_POINTER; }      // (checkOnly: a source still to be allocated)
+    if (srcFmt != MPCVR_OUT_BGRA8 && srcFmt != MPCVR_OUT_RGB10A2) { *why = "source BGRA8 or RGB10A2"; return MPCVR_E_INVALIDARG; }
+    if (w < 1 || h < 1 || w > 32768 || h > 32768) { *why = "width and height must be 1 .. 32768"; return MPCVR_E_INVALIDARG; }
+    if (srcPitch < 4 * w) { *why = "pitch smaller than a row"; return MPCVR_E_INVALIDARG; }
+    if (((uintptr_t)src | (uintptr_t)srcPitch) & 3) { *why = "surface and pitch must be multiples of 4"; return MPCVR_E_INVALIDARG; }
+    const mpcvr_tensor_desc &d = *desc;
+    if (d.dtype < TN_F32 || d.dtype > TN_BF16 || (d.layout != TN_PLANAR && d.layout != TN_INTERLEAVED) ||
+        (d.channel_order != MPCVR_TENSOR_RGB && d.channel_order != MPCVR_TENSOR_BGR) || d.reserved != 0) {
+        *why = "unknown dtype, layout or channel order, or reserved is not 0"; return MPCVR_E_INVALIDARG;
+    }
+    for (int k = 0; k < 3; k++)
+        if (!TensorFactorOk(d.scale[k]) || !TensorFactorOk(d.bias[k])) { *why = "scale and bias must be finite, and 0 or of magnitude 2^-100 .. 2^100"; return MPCVR_E_INVALIDARG; }
+    const bool planar = d.layout == TN_PLANAR;
+    const int64_t es = TensorElementSize(d.dtype), kMaxPitch = (int64_t)1 << 47;      // (h rows and three planes of that stay far inside 64 bits)
+    if (d.row_pitch < es * (planar ? 1 : 3) * w || d.row_pitch > kMaxPitch || (planar && (d.plane_pitch < 1 || d.plane_pitch > kMaxPitch))) {
+        *why = "row pitch smaller than a row, or a pitch that is not positive or beyond 2^47"; return MPCVR_E_INVALIDARG;
+    }
+    if (((uintptr_t)dst | (uintptr_t)d.row_pitch | (planar ? (uintptr_t)d.plane_pitch : 0)) & (uintptr_t)(es - 1)) {
+        *why = "tensor and pitches must be multiples of the element size"; return MPCVR_E_INVALIDARG;
+    }
+    const RtSpan s = RowsSpan(src, (size_t)srcPitch, h, (size_t)4 * w);
+    RtSpan pl[3];
+    const int np = TensorPlaneSpans(d, dst, w, h, pl);
+    for (int a = 0; a < np; a++) {
+        if (src && pl[a].Overlaps(s)) { *why = "a plane overlaps the source"; return MPCVR_E_INVALIDARG; }
+        for (int b = a + 1; b < np; b++)
+            if (pl[a].Overlaps(pl[b])) { *why = "two planes of the tensor overlap"; return MPCVR_E_INVALIDARG; }
+    }
+    if (checkOnly) return MPCVR_S_OK;
+    TensorParams p = TensorLaunchParams(d, w, h, srcPitch);
+    p.src = (const uint8_t *)src; p.dst = (uint8_t *)dst;
+    p.src16 &= (s.lo & 15) == 0;
+    p.dstvec &= ((uintptr_t)dst & (uintptr_t)(TensorVectorBytes(d.dtype) - 1)) == 0;
+    if (LaunchTensor(p, srcFmt == MPCVR_OUT_RGB10A2, d.dtype, d.layout, stream) != hipSuccess) { *why = "k_tensor launch failed"; return MPCVR_E_FAIL; }
+    return MPCVR_S_OK;
+}
+
+// Render, then the pass over the whole window behind it, ordered as RenderYuv (the comment there): on the context stream, the lanes' next
+// work behind the pass.
+HRESULT CHipVideoProcessor::RenderTensor(int /*field*/, const mpcvr_tensor_desc &desc, void *dst)
+{
+    if (!m_bInit || !m_srcParams) return Fail(MPCVR_E_NOT_VALID_STATE, "InitMediaType has not been called");
+    (void)hipSetDevice(m_device);
+    const int w = m_windowRect.Width(), h = m_windowRect.Height();
+    // everything about the tensor is answered before anything is drawn (a back buffer Render has yet to allocate cannot overlap it)
+    const bool have = m_BackBuffer.ptr && m_BackBuffer.size >= (size_t)w * 4 * h;
+    HRESULT hr;
+    const char *why = "";
+    if ((hr = TensorSurface(have ? m_BackBuffer.ptr : nullptr, w * 4, m_cfg.output_format, w, h, &desc, dst, nullptr, true, &why))) return Fail(hr, why);
+    if (!m_curSample) return MPCVR_S_FALSE;          // nothing to draw, as Render
+    if ((hr = RenderBackBuffer(true)) != MPCVR_S_OK) return hr;
+    hr = TensorSurface(m_BackBuffer.ptr, w * 4, m_cfg.output_format, w, h, &desc, dst, m_stream, false, &why);
+    m_launches++;
+    m_lanes.NoteStreamWork();
+    return hr ? Fail(hr, why) : MPCVR_S_OK;
+}
+
+// A batch as tensors (include/mpcvr.h: mpcvr_process_batch_tensor): ProcessBatchYuv with k_tensor as the chunk's pass.  Everything about
+// the arguments is answered first; the chunks, their surfaces, lanes and order are RunSurfaceChunks'.  Every plane of every frame is a
+// span the chunk writes.
+HRESULT CHipVideoProcessor::ProcessBatchTensor(int n, const void *const *srcs, const mpcvr_tensor_desc *desc, void *const *dsts)
+{
+    const BatchRecord record(*this, n > 0 ? n : 0);
+    if (!m_bInit || !m_srcParams) return Fail(MPCVR_E_NOT_VALID_STATE, "InitMediaType has not been called");
+    if (n <= 0) return Fail(MPCVR_E_INVALIDARG, "empty batch");
+    if (!srcs || !dsts || !desc) return Fail(MPCVR_E_POINTER, "null array of frames or tensors, or null description");
+    for (int i = 0; i < n; i++)
+        if (!srcs[i] || !dsts[i]) return Fail(MPCVR_E_POINTER, "null frame or tensor in batch");
+    const int w = m_windowRect.Width(), h = m_windowRect.Height();
+    BatchYuvLayout lay;
+    if (!PlanBatchTensor(w, h, n, m_yuvBudget, &lay)) return Fail(MPCVR_E_INVALIDARG, "a tensor needs a window width and height of 1 .. 32768");
+    // what the pass refuses, per frame (the surface is still to be allocated: it cannot overlap a plane) ...
+    const char *why = "";
+    for (int i = 0; i < n; i++)
+        if (HRESULT bad = TensorSurface(nullptr, lay.surfacePitch, m_cfg.output_format, w, h, desc, dsts[i], nullptr, true, &why)) return Fail(bad, why);
+    // ... and the planes of all frames against each other
+    const int np = desc->layout == TN_PLANAR ? 3 : 1;
+    std::vector<RtSpan> planes((size_t)np * (size_t)n);
+    for (int i = 0; i < n; i++) TensorPlaneSpans(*desc, dsts[i], w, h, &planes[(size_t)np * (size_t)i]);
+    if (AnyTwoSpansOverlap(planes)) return Fail(MPCVR_E_INVALIDARG, "two planes of the batch overlap");
+
+    (void)hipSetDevice(m_device);
+    if (HRESULT bad = m_planDirty ? UpdatePlan() : MPCVR_S_OK) return bad;
+    const TensorParams tp = TensorLaunchParams(*desc, w, h, lay.surfacePitch);      // (src16 holds for every chunk: every frame of a surface starts on 256 bytes)
+    const bool in10 = m_cfg.output_format == MPCVR_OUT_RGB10A2;
+    return RunSurfaceChunks(n, srcs, lay, "tensor",
+        [&](int at, int m) { return std::vector<RtSpan>(planes.begin() + (size_t)np * (size_t)at, planes.begin() + (size_t)np * (size_t)(at + m)); },
+        [&](BatchRun &run, int at) {
+            // the tensors' table through the frame tables' ring; the lease ends behind the pass
+            SlotLease table;
+            TensorFrame *fr;
+            if (HRESULT bad = m_tableRing.Next(sizeof(TensorFrame) * run.n, sizeof(TensorFrame) * 64, (void **)&fr)) return bad;
+            TensorParams p = tp;
+            for (int i = 0; i < run.n; i++) {
+                fr[i] = TensorFrame{(const uint8_t *)run.dsts[i], (uint8_t *)dsts[at + i]};
+                p.dstvec &= ((uintptr_t)dsts[at + i] & (uintptr_t)(TensorVectorBytes(desc->dtype) - 1)) == 0;      // the vector stores only if every tensor of the launch allows them
+            }
+            if (HRESULT bad = m_tableRing.Send(sizeof(TensorFrame) * run.n, run.on.stream, "tensor table", &table)) return bad;
+            p.frames = (const TensorFrame *)table.dev;
+            return CheckHip(LaunchTensor(p, in10, desc->dtype, desc->layout, run.on.stream, run.n), "k_tensor");
+        });
 }
 
 HRESULT CHipVideoProcessor::GetBackBuffer(void **ptr, int *pitch, int *w, int *h)

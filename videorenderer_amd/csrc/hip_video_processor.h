@@ -13,6 +13,7 @@
 #include "vp_encode.h"
 #include "vp_lanes.h"
 #include "vp_measure.h"
+#include "vp_tensor.h"
 #include "vp_launch.h"
 #include "vp_params.h"
 #include "vp_plan.h"
@@ -51,6 +52,11 @@ HRESULT EncodeSurface(const void *src, int srcPitch, int srcFmt, int w, int h, i
 // k_measure_maxrgb on `stream`.  rect = nullptr: the whole surface.  MPCVR_E_POINTER / MPCVR_E_INVALIDARG with nothing launched or written
 HRESULT MeasureSurface(const void *src, int srcPitch, int srcFmt, int w, int h, const mpcvr_rect *rect, uint32_t *histDev, hipStream_t stream,
                        bool checkOnly, const char **why = nullptr);
+
+// EXTENSION (mpcvr_tensor_pass, include/mpcvr.h): checks every argument, then — unless checkOnly — launches k_tensor on `stream`.
+// MPCVR_E_POINTER / MPCVR_E_INVALIDARG with nothing launched or written
+HRESULT TensorSurface(const void *src, int srcPitch, int srcFmt, int w, int h, const mpcvr_tensor_desc *desc, void *dst, hipStream_t stream,
+                      bool checkOnly, const char **why = nullptr);
 
 class CHipVideoProcessor {
 public:
@@ -92,6 +98,10 @@ public:
     // histDev (mpcvr_process_batch_yuv_stats; nullptr: none): n rows of kHistBins words, one k_measure_maxrgb launch behind each chunk's pass
     HRESULT ProcessBatchYuv(int n, const void *const *srcs, int outCformat, uint32_t extfmt, void *const *yPlanes, int yPitch, void *const *uvPlanes, int uvPitch,
                             uint32_t *histDev = nullptr);
+    // EXTENSION (mpcvr_render_tensor / mpcvr_process_batch_tensor): Render / the batch, then k_tensor (vp_tensor.h) behind it in stream order;
+    // the batch shares ProcessBatchYuv's surfaces, budget and chunk loop
+    HRESULT RenderTensor(int field, const mpcvr_tensor_desc &desc, void *dst);
+    HRESULT ProcessBatchTensor(int n, const void *const *srcs, const mpcvr_tensor_desc *desc, void *const *dsts);
     HRESULT SetBatchYuvBudget(size_t bytes) { m_yuvBudget = bytes; return MPCVR_S_OK; }
     std::string GetLastBatchInfo() const;
     HRESULT ProcessBatchDovi(int n, const void *const *srcs, void *const *dsts, int rtPitch, const mpcvr_dovi_metadata *rpus);
@@ -428,10 +438,14 @@ private:
     };
     YuvSurface m_yuvSurf[FrameLanes::kFrameLanes];
     size_t m_yuvBudget = 0;            // SetBatchYuvBudget; 0: kBatchYuvDefaultBudget
-    std::string m_yuvLastInfo;         // ";yuv_chunks=..;yuv_lanes=.." of the last batch call, if it was a ProcessBatchYuv
-    // one chunk: rp / run.dsts name the surface's frames, run.on the stream; `encode` holds the launch's pitches, size and coefficients
-    HRESULT RunYuvChunk(BatchRoutePlan &rp, BatchRun &run, YuvSurface &surf, const EncodeParams &encode, const EncodePlan &plan,
-                        void *const *yPlanes, void *const *uvPlanes, uint32_t *histRows);
+    std::string m_yuvLastInfo;         // ";yuv_chunks=..;yuv_lanes=.." (";tensor_chunks=..;tensor_lanes=..") of the last batch call, if it was a ProcessBatchYuv (ProcessBatchTensor)
+    // the chunk loop of both: surfaces, lanes and order; writesOf(at, m): what the chunk writes for the caller, pass(run, at): its pass
+    template <class WritesOf, class Pass>
+    HRESULT RunSurfaceChunks(int n, const void *const *srcs, const BatchYuvLayout &lay, const char *tag, WritesOf writesOf, Pass pass);
+    // one chunk into its surface: rp / run.dsts name the surface's frames, run.on the stream
+    HRESULT RenderChunk(BatchRoutePlan &rp, BatchRun &run, YuvSurface &surf);
+    // ... and its passes behind it: `encode` holds the launch's pitches, size and coefficients
+    HRESULT EncodeChunk(BatchRun &run, const EncodeParams &encode, const EncodePlan &plan, void *const *yPlanes, void *const *uvPlanes, uint32_t *histRows);
     // video rect ∩ window: the active picture the measure pass counts (empty: all zero)
     mpcvr_rect ActiveRect() const;
     HRESULT RunBatchRoute(BatchRoutePlan &rp, BatchRun &run);

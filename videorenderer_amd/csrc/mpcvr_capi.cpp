@@ -227,6 +227,46 @@ int32_t mpcvr_histogram_percentile(const uint32_t hist[MPCVR_HIST_BINS], uint32_
     return MPCVR_S_OK;
 }
 
+// EXTENSION: rendered frames as float tensors (include/mpcvr.h; k_tensor vp_tensor.hip, the arithmetic vp_tensor_core.h, TensorSurface and
+// CHipVideoProcessor::RenderTensor / ProcessBatchTensor hip_video_processor.cpp, PlanTensorValue / PlanBatchTensor vp_plan.cpp)
+static_assert(MPCVR_TENSOR_F32 == mpcvr::TN_F32 && MPCVR_TENSOR_F16 == mpcvr::TN_F16 && MPCVR_TENSOR_BF16 == mpcvr::TN_BF16 &&
+              MPCVR_TENSOR_PLANAR == mpcvr::TN_PLANAR && MPCVR_TENSOR_INTERLEAVED == mpcvr::TN_INTERLEAVED, "the header and vp_tensor_core.h name one set of tensor formats");
+int32_t mpcvr_plan_tensor_value(int32_t dtype, int32_t src_fmt, uint32_t code, float scale, float bias, uint32_t *bits)
+{
+    if (!bits) return MPCVR_E_POINTER;
+    return mpcvr::PlanTensorValue(dtype, src_fmt, code, scale, bias, bits) ? MPCVR_S_OK : MPCVR_E_INVALIDARG;
+}
+
+int32_t mpcvr_tensor_pass(const void *src, int32_t src_pitch, int32_t src_fmt, int32_t w, int32_t h, const mpcvr_tensor_desc *desc, void *dst, void *stream)
+{
+    return mpcvr::TensorSurface(src, src_pitch, src_fmt, w, h, desc, dst, (hipStream_t)stream, false);
+}
+
+int32_t mpcvr_render_tensor(mpcvr_ctx *ctx, int32_t field, const mpcvr_tensor_desc *desc, void *dst)
+{
+    CTX_OR_FAIL();
+    if (!desc || !dst) return MPCVR_E_POINTER;
+    return ctx->vp.RenderTensor(field, *desc, dst);
+}
+
+int32_t mpcvr_plan_batch_tensor(int32_t window_w, int32_t window_h, int32_t n, size_t budget_bytes,
+                                int32_t *surface_pitch, size_t *frame_stride, int32_t *frames_per_chunk, int32_t *chunks)
+{
+    mpcvr::BatchYuvLayout lay;
+    if (!mpcvr::PlanBatchTensor(window_w, window_h, n, budget_bytes, &lay)) return MPCVR_E_INVALIDARG;
+    if (surface_pitch) *surface_pitch = lay.surfacePitch;
+    if (frame_stride) *frame_stride = lay.frameStride;
+    if (frames_per_chunk) *frames_per_chunk = lay.framesPerChunk;
+    if (chunks) *chunks = lay.chunks;
+    return MPCVR_S_OK;
+}
+
+int32_t mpcvr_process_batch_tensor(mpcvr_ctx *ctx, int32_t n, const void *const *srcs, const mpcvr_tensor_desc *desc, void *const *dsts)
+{
+    CTX_OR_FAIL();
+    return ctx->vp.ProcessBatchTensor(n, srcs, desc, dsts);
+}
+
 int32_t mpcvr_get_param_blob(mpcvr_ctx *ctx, void *buf, size_t *size) { CTX_OR_FAIL(); return ctx->vp.GetParamBlob(buf, size); }
 int32_t mpcvr_get_fused_tables(mpcvr_ctx *ctx, void *buf, size_t *size) { CTX_OR_FAIL(); return ctx->vp.GetFusedTables(buf, size); }
 int32_t mpcvr_set_param_blob(mpcvr_ctx *ctx, const void *buf, size_t size) { CTX_OR_FAIL(); return ctx->vp.SetParamBlob(buf, size); }

@@ -33,6 +33,8 @@ bool PlanEncode(int out_cformat, int src_fmt, uint32_t extfmt, int w, int h, Enc
 struct BatchYuvLayout { int32_t surfacePitch; size_t frameStride; int32_t framesPerChunk, chunks; };
 constexpr size_t kBatchYuvDefaultBudget = (size_t)4 << 30;      // MPCVR_BATCH_YUV_DEFAULT_BUDGET (mpcvr_capi.cpp asserts they agree)
 bool PlanBatchYuv(int w, int h, int n, size_t budget, BatchYuvLayout *out);
+// the same three formulas for a window of any parity, 1 .. 32768 (mpcvr_plan_batch_tensor: the tensor pass has no 2x2 blocks)
+bool PlanBatchTensor(int w, int h, int n, size_t budget, BatchYuvLayout *out);
 
 // one frame of a launch with a frame dimension: its source surface and its two planes (pitches, size and format are the launch's)
 struct EncodeFrame { const uint8_t *src; uint8_t *y, *uv; };

@@ -9,6 +9,7 @@
 #include "../../include/mpcvr.h"
 #include "vp_encode.h"
 #include "vp_measure.h"
+#include "vp_tensor.h"
 #include "vp_crmath.h"      // the shaders' sin / cos as defined functions (the weights the resize shaders compute per pixel are computed here, once)
 
 namespace mpcvr {
@@ -226,7 +227,12 @@ void ComputeColorMatrix(const ExtFmt &ex, const FmtConvParams &f, const ProcAmp 
 // ------------------------------------------------------------------------------------------------
 bool PlanBatchYuv(int w, int h, int n, size_t budget, BatchYuvLayout *out)
 {
-    if (n <= 0 || w < 2 || h < 2 || ((w | h) & 1) || w > 32768 || h > 32768) return false;
+    return w >= 2 && h >= 2 && !((w | h) & 1) && PlanBatchTensor(w, h, n, budget, out);
+}
+
+bool PlanBatchTensor(int w, int h, int n, size_t budget, BatchYuvLayout *out)
+{
+    if (n <= 0 || w < 1 || h < 1 || w > 32768 || h > 32768) return false;
     if (!budget) budget = kBatchYuvDefaultBudget;
     out->surfacePitch = (4 * w + 15) & ~15;
     out->frameStride = ((size_t)out->surfacePitch * (size_t)h + 255) & ~(size_t)255;
@@ -278,6 +284,22 @@ int HistogramPercentile(const uint32_t *hist, uint32_t ppm)
         if (run >= need) return c;
     }
     return kHistBins - 1;
+}
+
+// ------------------------------------------------------------------------------------------------
+// EXTENSION — one element of the tensor pass on the host (include/mpcvr.h: mpcvr_plan_tensor_value): the functions of vp_tensor_core.h
+// the kernel converts with, compiled for the host.  No reference line: the reference has no float output.
+// ------------------------------------------------------------------------------------------------
+bool PlanTensorValue(int dtype, int src_fmt, uint32_t code, float scale, float bias, uint32_t *bits)
+{
+    if (src_fmt != MPCVR_OUT_BGRA8 && src_fmt != MPCVR_OUT_RGB10A2) return false;
+    if (code > (src_fmt == MPCVR_OUT_RGB10A2 ? 1023u : 255u) || !TensorFactorOk(scale) || !TensorFactorOk(bias)) return false;
+    switch (dtype) {
+    case TN_F32: *bits = TensorElementBits<TN_F32>(code, scale, bias); return true;
+    case TN_F16: *bits = TensorElementBits<TN_F16>(code, scale, bias); return true;
+    case TN_BF16: *bits = TensorElementBits<TN_BF16>(code, scale, bias); return true;
+    }
+    return false;
 }
 
 bool PlanEncode(int out_cformat, int src_fmt, uint32_t extfmt, int w, int h, EncodePlan *plan)
