@@ -392,6 +392,54 @@ int32_t mpcvr_tensor_pass(const void *src, int32_t src_pitch, int32_t src_fmt, i
  * desc and dst is answered before anything is drawn.  S_FALSE, with nothing drawn or written, when there is no sample (as mpcvr_render). */
 int32_t mpcvr_render_tensor(mpcvr_ctx *ctx, int32_t field, const mpcvr_tensor_desc *desc, void *dst);
 
+/* EXTENSION — the way back: the float tensor a model leaves on the device (super-resolution, denoising, interpolation, generation) written
+ * as a planar RGB sample, MPCVR_CF_GBRP8 / GBRP10 / GBRP16, which the convert path reads directly — the scalers, the ordered dither, the
+ * error-diffusion pass and mpcvr_render_yuv then stand behind a float picture.  The reference has no float input; there is no reference
+ * line to cite.  The definition is the text below, modelled bit for bit by tests/tensor_in_model.py (arithmetic: csrc/vp_tensor_core.h,
+ * SampleCode, which the kernel and mpcvr_plan_sample_code both compile).
+ *   The tensor is described by mpcvr_tensor_desc, unchanged: dtype, layout, channel_order, row_pitch and plane_pitch mean what they mean
+ *   for mpcvr_tensor_pass, only that the tensor is READ; scale[k] and bias[k] (k = R, G, B of the picture, whatever the channel order) apply
+ *   to the tensor's value.  w and h in 1 .. 32768, odd sizes allowed.  tensor, row_pitch and (planar) plane_pitch are multiples of the element
+ *   size es; row_pitch >= w es (planar) or 3 w es (interleaved); pitches are positive and at most 2^47.
+ *   Arithmetic, per channel, x = the element, maxcode = 255 / 1023 / 65535 for GBRP8 / GBRP10 / GBRP16:
+ *     widening   x is widened exactly to fp32 (fp16 subnormals are kept: they are normal fp32 numbers; bf16 = bits << 16).  A widened value
+ *                of magnitude below 2^-126 — an fp32 or bf16 subnormal, +0 or -0 — is taken as +0: the result does not depend on a
+ *                denormal mode.
+ *     two roundings   t = x * scale[k], rounded to fp32;  u = t + bias[k], rounded to fp32 — two IEEE round-to-nearest-even operations,
+ *                NOT a fused multiply-add.  scale[k] and bias[k] must be finite, and 0 or of magnitude in [2^-100, 2^100], as for
+ *                mpcvr_tensor_pass.  A subnormal t, kept or flushed to 0, cannot change the code: with bias[k] = 0, u = t and |t| < 2^-126
+ *                < 0.5 gives code 0 either way; otherwise |bias[k]| >= 2^-100, where fp32 numbers are at least 2^-123 apart, and |t| <
+ *                2^-126 is under half of that, so t + bias[k] rounds to bias[k] either way.  (A subnormal u is below 0.5: code 0.)
+ *     code       0 if not (u > 0): NaN, -inf, negatives, inf * 0.  maxcode if u >= maxcode: +inf included.  Otherwise u rounded to the
+ *                nearest integer, ties to even.
+ *     stored     GBRP8 one byte; GBRP10 / GBRP16 a 16-bit word, for GBRP10 with bits 10 .. 15 zero.
+ *   The sample is exactly what mpcvr_set_input(GBRP*, w, h, pitch) declares: planes G, B, R in that order, plane p at sample + p * pitch *
+ *   h, row y at + y * pitch.  sample is a multiple of the component size (1 or 2); pitch >= w * component size, and even for the 16-bit
+ *   formats.  channel_order says which of R, G, B tensor channel 0, 1, 2 is.  No byte outside the pixels is written: not the pitch
+ *   padding, nothing in front of, between or behind planes.  All addressing is 64-bit: planes and rows may lie more than 4 GiB apart.
+ *   Vector loads and stores are taken where pointers and pitches allow them (tensor on 16 bytes for F32, 8 for F16 / BF16; sample and
+ *   pitch on 4 x the component size).
+ * Refusals, with nothing launched and nothing written: MPCVR_E_POINTER for a NULL tensor, desc or sample; MPCVR_E_INVALIDARG for another
+ * cformat, dtype, layout or channel_order, reserved != 0, a size, pointer or pitch outside the rules above, a scale or bias outside the
+ * set, a plane of the tensor (first element to last element of its last row; INTERLEAVED: the whole tensor) that overlaps a plane of the
+ * sample (first pixel to last pixel of its last row), and sample planes that overlap each other. */
+/* Host, no GPU: *code = the code of one element (element_bits: the fp32 bits, or the 16 bits of F16 / BF16 in the low half) in a sample of
+ * cformat.  MPCVR_E_POINTER for a NULL code; MPCVR_E_INVALIDARG for another dtype or cformat, element_bits beyond 16 bits for F16 / BF16,
+ * a scale or bias outside the set above. */
+int32_t mpcvr_plan_sample_code(int32_t dtype, int32_t cformat, uint32_t element_bits, float scale, float bias, uint32_t *code);
+/* One standalone pass over one device tensor, like mpcvr_tensor_pass; stream = a hipStream_t or NULL.  One kernel launch
+ * (k_sample_from_tensor, csrc/vp_tensor_in.hip). */
+int32_t mpcvr_sample_pass(const void *tensor, const mpcvr_tensor_desc *desc, int32_t w, int32_t h, int32_t cformat, void *sample,
+                          int32_t pitch, void *stream);
+/* The tensor becomes the current sample of a context whose input (mpcvr_set_input) is GBRP8 / GBRP10 / GBRP16 of the tensor's width and
+ * height, at the input's pitch; any other input answers MPCVR_E_INVALIDARG, MPCVR_E_NOT_VALID_STATE before mpcvr_set_input.  The call
+ * takes an upload slot exactly as mpcvr_copy_sample(MPCVR_MEM_HOST) does — the slot ring, its device buffer, the event behind the
+ * sample's last reader — with the pass in the place of the host-to-device copy, queued on the context stream: the caller's tensor must be
+ * complete in that stream's order in front of the call and is free in that stream's order behind it.  The frame lanes, mpcvr_process,
+ * mpcvr_render, mpcvr_render_yuv and mpcvr_render_tensor then work as for any host sample.  Everything mpcvr_sample_pass refuses about
+ * tensor and desc is answered before anything is touched: the previous sample stays current. */
+int32_t mpcvr_copy_sample_tensor(mpcvr_ctx *ctx, const void *tensor, const mpcvr_tensor_desc *desc);
+
 /* Configure — DX11VideoProcessor.cpp:3800-4050: diff each field, rebuild only what changed. */
 int32_t mpcvr_configure(mpcvr_ctx *ctx, const mpcvr_settings *settings);
 
@@ -582,6 +630,24 @@ int32_t mpcvr_process_batch_yuv_stats(mpcvr_ctx *ctx, int32_t n, const void *con
 int32_t mpcvr_plan_batch_tensor(int32_t window_w, int32_t window_h, int32_t n, size_t budget_bytes,
                                 int32_t *surface_pitch, size_t *frame_stride, int32_t *frames_per_chunk, int32_t *chunks);
 int32_t mpcvr_process_batch_tensor(mpcvr_ctx *ctx, int32_t n, const void *const *srcs, const mpcvr_tensor_desc *desc, void *const *dsts);
+/* EXTENSION — a batch FROM float tensors (the pass itself: mpcvr_sample_pass above).  The input is GBRP8 / GBRP10 / GBRP16; tensors[i] is
+ * the tensor of frame i, all n described by one desc, dsts[i] its render target.  Target i holds, byte for byte, what
+ *     mpcvr_sample_pass(tensors[i], desc, w, h, cformat, sample i of the caller's, pitch), n times, then
+ *     mpcvr_process_batch(samples -> dsts, dst_pitch)
+ * leave, with ONE k_sample_from_tensor launch per chunk of frames (its frame dimension) where the composition takes n, and no samples of
+ * the caller's: they live in a context-owned surface, frame i of a chunk at i * frame_stride, frame_stride = 3 * pitch * h rounded up
+ * to 256 (mpcvr_plan_batch_from_tensors; pitch and h are the input's).  A chunk is what fits the budget of mpcvr_set_batch_yuv_budget
+ * (0: the default), at least one frame, at most n — the library's one chunk rule.  Every chunk runs in stream order on the context
+ * stream: the pass, then the chunk's mpcvr_process_batch work, so the surface's reuse by the next chunk and the next call is ordered;
+ * the batch lanes are not used.  The tensors are free in stream order behind the call; the targets are complete after mpcvr_synchronize.
+ * Refusals, answered before anything is drawn, allocated or written: MPCVR_E_NOT_VALID_STATE before mpcvr_set_input; MPCVR_E_POINTER for
+ * a NULL array, entry or desc; MPCVR_E_INVALIDARG for n <= 0, another input format, whatever mpcvr_sample_pass refuses about desc and a
+ * tensors[i], and whatever mpcvr_process_batch refuses about dsts and dst_pitch.
+ * mpcvr_get_last_batch_info afterwards: "launches" counts one pass per chunk, and ";sample_chunks=<k>" follows. */
+int32_t mpcvr_plan_batch_from_tensors(int32_t pitch, int32_t h, int32_t n, size_t budget_bytes,
+                                      size_t *frame_stride, int32_t *frames_per_chunk, int32_t *chunks);
+int32_t mpcvr_process_batch_from_tensors(mpcvr_ctx *ctx, int32_t n, const void *const *tensors, const mpcvr_tensor_desc *desc,
+                                         void *const *dsts, int32_t dst_pitch);
 
 /* Multi-GPU: the parameter blob (colour matrix, luminance scale, gamut matrix, resize phase weights,
  * dither table) a rank-0 context computes and every other rank adopts after an RCCL broadcast.

@@ -195,6 +195,7 @@ EXPORTS = [
     "mpcvr_measure_pass", "mpcvr_measure_backbuffer", "mpcvr_process_batch_yuv_stats",
     "mpcvr_light_level_from_histogram", "mpcvr_histogram_percentile",
     "mpcvr_plan_tensor_value", "mpcvr_tensor_pass", "mpcvr_render_tensor", "mpcvr_plan_batch_tensor", "mpcvr_process_batch_tensor",
+    "mpcvr_plan_sample_code", "mpcvr_sample_pass", "mpcvr_copy_sample_tensor", "mpcvr_plan_batch_from_tensors", "mpcvr_process_batch_from_tensors",
 ]
 
 _lib = None
@@ -306,6 +307,11 @@ def load_library():
         "mpcvr_render_tensor": [vp, i32, P(TensorDesc), vp],
         "mpcvr_plan_batch_tensor": [i32, i32, i32, C.c_size_t, P(i32), P(C.c_size_t), P(i32), P(i32)],
         "mpcvr_process_batch_tensor": [vp, i32, P(vp), P(TensorDesc), P(vp)],
+        "mpcvr_plan_sample_code": [i32, i32, u32, f, f, P(u32)],
+        "mpcvr_sample_pass": [vp, P(TensorDesc), i32, i32, i32, vp, i32, vp],
+        "mpcvr_copy_sample_tensor": [vp, vp, P(TensorDesc)],
+        "mpcvr_plan_batch_from_tensors": [i32, i32, i32, C.c_size_t, P(C.c_size_t), P(i32), P(i32)],
+        "mpcvr_process_batch_from_tensors": [vp, i32, P(vp), P(TensorDesc), P(vp), i32],
     }
     for name, args in sig.items():
         if lib_path != LIB_PATH and not hasattr(L, name):
@@ -508,6 +514,48 @@ def _tensor_order(channel_order):
         return {"rgb": TENSOR_RGB, "bgr": TENSOR_BGR}[channel_order]
     except KeyError:
         raise ValueError("channel_order 'rgb' or 'bgr'") from None
+
+
+def plan_sample_code(dtype, cformat, element_bits, scale, bias):
+    """(extension) The code of one tensor element in a GBRP8 / GBRP10 / GBRP16 sample (include/mpcvr.h: mpcvr_plan_sample_code):
+    element_bits are the fp32 bits, or the 16 bits of fp16 / bf16.  No GPU needed."""
+    code = C.c_uint32()
+    hr = load_library().mpcvr_plan_sample_code(int(dtype), int(cformat), int(element_bits), float(scale), float(bias), C.byref(code))
+    if hr:
+        raise MpcvrError(hr, "mpcvr_plan_sample_code")
+    return code.value
+
+
+def sample_pass(tensor, desc, w, h, cformat, sample, pitch, stream=None):
+    """(extension) The float tensor `desc` (tensor_desc) describes at `tensor` (device tensor or address) written as a planar RGB sample
+    (cformat CF_GBRP8 / GBRP10 / GBRP16; planes G, B, R, pitch * h apart) at `sample` (include/mpcvr.h: mpcvr_sample_pass).  Complete in
+    stream order."""
+    hr = load_library().mpcvr_sample_pass(C.c_void_p(_ptr(tensor)), C.byref(desc) if desc is not None else None, int(w), int(h), int(cformat),
+                                          C.c_void_p(_ptr(sample)), int(pitch), C.c_void_p(stream) if stream else None)
+    if hr:
+        raise MpcvrError(hr, "mpcvr_sample_pass")
+
+
+def plan_batch_from_tensors(pitch, h, n, budget_bytes=0):
+    """(extension) The integers of ProcessBatchFromTensors' sample surface (include/mpcvr.h: mpcvr_plan_batch_from_tensors): dict(frame_stride,
+    frames_per_chunk, chunks) for n samples of three planes of pitch * h bytes under a budget of bytes (0: the default).  No GPU needed."""
+    fpc, chunks, stride = C.c_int32(), C.c_int32(), C.c_size_t()
+    hr = load_library().mpcvr_plan_batch_from_tensors(int(pitch), int(h), int(n), int(budget_bytes), C.byref(stride), C.byref(fpc), C.byref(chunks))
+    if hr:
+        raise MpcvrError(hr, "mpcvr_plan_batch_from_tensors")
+    return dict(frame_stride=stride.value, frames_per_chunk=fpc.value, chunks=chunks.value)
+
+
+def _frame_tensor_desc(t, scale, bias, channel_order):
+    """The mpcvr_tensor_desc of one frame held by a torch tensor: (3, H, W) with a dense last dim, or (H, W, 3) with the last two dims
+    dense; dtype and pitches are read off it (a slice works).  Returns (desc, w, h)."""
+    es = t.element_size()
+    if t.dim() == 3 and t.shape[0] == 3 and t.stride(2) == 1:          # (a (3, H, 3) tensor is taken as 3 planes of H x 3)
+        return tensor_desc(_tensor_dtype(t.dtype), TENSOR_PLANAR, t.stride(1) * es, t.stride(0) * es, scale, bias, _tensor_order(channel_order)), t.shape[2], t.shape[1]
+    if t.dim() == 3 and t.shape[2] == 3 and t.stride(2) == 1 and t.stride(1) == 3:
+        return tensor_desc(_tensor_dtype(t.dtype), TENSOR_INTERLEAVED, t.stride(0) * es, 0, scale, bias, _tensor_order(channel_order)), t.shape[1], t.shape[0]
+    raise ValueError("a tensor of shape %s / strides %s is neither (3, H, W) with a dense last dim nor (H, W, 3) with the last two dims dense"
+                     % (tuple(t.shape), t.stride()))
 
 
 def plan_batch_yuv(window_w, window_h, n, budget_bytes=0):
@@ -886,6 +934,34 @@ class VideoProcessor:
         self._check(self._L.mpcvr_get_displayed_image(self._ctx, C.c_void_p(buf.ctypes.data), C.byref(size), int(deep_color), C.byref(w), C.byref(h), C.byref(bits)))
         return buf, w.value, h.value, bits.value
 
+    def CopySampleTensor(self, t, scale=(255.0,) * 3, bias=(0,) * 3, channel_order="rgb"):
+        """(extension) A model's float tensor as the current sample of a GBRP8 / GBRP10 / GBRP16 input (mpcvr_copy_sample_tensor): code =
+        round(value * scale + bias) per channel of the picture (R, G, B), clamped to the format.  `t` is a device tensor of (3, H, W) with a
+        dense last dim or (H, W, 3) with the last two dims dense, float32 / float16 / bfloat16; dtype, layout and pitches are read off it,
+        so a slice works.  The pass runs on the context stream; `t` is free in that stream's order behind the call."""
+        d, w, h = _frame_tensor_desc(t, scale, bias, channel_order)
+        if not t.is_cuda:
+            raise ValueError("a device tensor")
+        self._keep = (t, d)
+        return self._check(self._L.mpcvr_copy_sample_tensor(self._ctx, C.c_void_p(t.data_ptr()), C.byref(d)))
+
+    def ProcessBatchFromTensors(self, ts, dsts, rt_pitch, scale=(255.0,) * 3, bias=(0,) * 3, channel_order="rgb"):
+        """(extension) ProcessBatch with float tensors as the samples (mpcvr_process_batch_from_tensors): `ts` is a device tensor of
+        (N, 3, H, W) or (N, H, W, 3), or a sequence of frames of one shape, dtype and strides (_frame_tensor_desc); dsts[i] the render
+        targets.  One k_sample_from_tensor launch per chunk in front of the chunk's batch; GetLastBatchInfo adds sample_chunks."""
+        frames = [ts[i] for i in range(len(ts))]
+        n = len(frames)
+        if n < 1 or n != len(dsts):
+            raise ValueError("as many tensors as render targets, at least one")
+        d, w, h = _frame_tensor_desc(frames[0], scale, bias, channel_order)
+        for t in frames:
+            if not t.is_cuda or t.dtype != frames[0].dtype or tuple(t.shape) != tuple(frames[0].shape) or t.stride() != frames[0].stride():
+                raise ValueError("every frame a device tensor of one dtype, shape and strides")
+        arr = C.c_void_p * n
+        keep = (arr(*[t.data_ptr() for t in frames]), arr(*[_ptr(x) for x in dsts]), d, (ts, dsts))
+        self._keep = keep
+        return self._check(self._L.mpcvr_process_batch_from_tensors(self._ctx, n, keep[0], C.byref(d), keep[1], int(rt_pitch)))
+
     def ProcessBatch(self, srcs, dsts, rt_pitch):
         if isinstance(srcs, PreparedBatch):          # pointer arrays built once (PrepareBatch): nothing per call but the C call
             return self._check(self._L.mpcvr_process_batch(self._ctx, srcs.n, srcs.sa, srcs.da, rt_pitch))
@@ -982,7 +1058,7 @@ class VideoProcessor:
         return buf.value.decode()
 
     def GetLastBatchInfo(self):
-        """'frames=<n>;launches=<kernel launches>;lane=<0 | 1: the batch ran on that lane beside its predecessor, -1: on the context stream>;waits=<frames / batches still in flight on other lanes, into memory this batch's targets overlap, that it was ordered behind>[;dovi_runs=...]' of the last ProcessBatch / ProcessBatchDovi / ProcessBatchYuv call, as a dict; behind a ProcessBatchYuv also yuv_chunks and yuv_lanes (the lane of each chunk), behind a ProcessBatchTensor tensor_chunks and tensor_lanes."""
+        """'frames=<n>;launches=<kernel launches>;lane=<0 | 1: the batch ran on that lane beside its predecessor, -1: on the context stream>;waits=<frames / batches still in flight on other lanes, into memory this batch's targets overlap, that it was ordered behind>[;dovi_runs=...]' of the last ProcessBatch / ProcessBatchDovi / ProcessBatchYuv call, as a dict; behind a ProcessBatchYuv also yuv_chunks and yuv_lanes (the lane of each chunk), behind a ProcessBatchTensor tensor_chunks and tensor_lanes, behind a ProcessBatchFromTensors sample_chunks."""
         buf = C.create_string_buffer(512)
         self._check(self._L.mpcvr_get_last_batch_info(self._ctx, buf, 512))
         d = dict(kv.split("=", 1) for kv in buf.value.decode().split(";"))
@@ -991,6 +1067,8 @@ class VideoProcessor:
             out.update(yuv_chunks=int(d["yuv_chunks"]), yuv_lanes=[int(x) for x in d["yuv_lanes"].split(",") if x])
         if "tensor_chunks" in d:     # (only behind a ProcessBatchTensor, likewise)
             out.update(tensor_chunks=int(d["tensor_chunks"]), tensor_lanes=[int(x) for x in d["tensor_lanes"].split(",") if x])
+        if "sample_chunks" in d:     # (only behind a ProcessBatchFromTensors)
+            out.update(sample_chunks=int(d["sample_chunks"]))
         return out
 
     def GetLastProcessMs(self):

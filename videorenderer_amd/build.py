@@ -47,6 +47,7 @@ SOURCES = [
     ("vp_encode.hip", []),
     ("vp_measure.hip", []),
     ("vp_tensor.hip", []),
+    ("vp_tensor_in.hip", []),
     ("vp_probe.hip", []),
 ]
 

@@ -64,6 +64,7 @@ CHipVideoProcessor::~CHipVideoProcessor()
                          &m_pqLut, &m_hlgLut, &m_eotfLut, &m_stripTab, &m_axisX, &m_axisY})
         b->Release();
     for (YuvSurface &ys : m_yuvSurf) ys.buf.Release();
+    m_sampleSurf.Release();
     for (UploadSlot &u : m_up) {
         u.dev.Release();
         if (u.pinned) (void)hipHostFree(u.pinned);
@@ -2118,6 +2119,172 @@ HRESULT CHipVideoProcessor::ProcessBatchTensor(int n, const void *const *srcs, c
             p.frames = (const TensorFrame *)table.dev;
             return CheckHip(LaunchTensor(p, in10, desc->dtype, desc->layout, run.on.stream, run.n), "k_tensor");
         });
+}
+
+// ------------------------------------------------------------------------------------------------
+// EXTENSION — the way back: the float tensor a model leaves as a planar RGB sample (include/mpcvr.h: mpcvr_sample_pass,
+// mpcvr_copy_sample_tensor, mpcvr_process_batch_from_tensors; kernel: vp_tensor_in.hip).  No reference line: the reference has no float input.
+// ------------------------------------------------------------------------------------------------
+// What a k_sample_from_tensor launch is given, but for its pointers: src / dst or the frame table are the caller's, who takes srcvec / dstvec
+// back where a pointer of the launch is off the grid (here they say what the pitches allow), as in TensorLaunchParams
+static SampleParams SampleLaunchParams(const mpcvr_tensor_desc &d, int w, int h, int bytes, int maxcode, int pitch)
+{
+    SampleParams p{};
+    p.w = w; p.h = h;
+    p.row_pitch = d.row_pitch; p.plane_pitch = d.layout == TN_PLANAR ? d.plane_pitch : 0;
+    p.dst_pitch = pitch; p.dst_plane = (int64_t)pitch * h;
+    std::memcpy(p.scale, d.scale, sizeof(p.scale));
+    std::memcpy(p.bias, d.bias, sizeof(p.bias));
+    p.maxcode = (float)maxcode;
+    p.bgr = d.channel_order == MPCVR_TENSOR_BGR;
+    p.srcvec = ((p.row_pitch | p.plane_pitch) & (TensorVectorBytes(d.dtype) - 1)) == 0;
+    p.dstvec = (pitch & (4 * bytes - 1)) == 0;
+    return p;
+}
+
+HRESULT SampleSurface(const void *tensor, const mpcvr_tensor_desc *desc, int w, int h, int cformat, void *sample, int pitch, hipStream_t stream,
+                      bool checkOnly, const char **why)
+{
+    const char *dummy;
+    if (!why) why = &dummy;
+    if (!tensor || !desc || (!sample && !checkOnly)) { *why = "null tensor, description or sample"; return MPCVR_E_POINTER; }      // (checkOnly: a sample still to be allocated)
+    int bytes, maxcode;
+    if (!SampleFormat(cformat, &bytes, &maxcode)) { *why = "sample GBRP8, GBRP10 or GBRP16"; return MPCVR_E_INVALIDARG; }
+    if (w < 1 || h < 1 || w > 32768 || h > 32768) { *why = "width and height must be 1 .. 32768"; return MPCVR_E_INVALIDARG; }
+    const mpcvr_tensor_desc &d = *desc;
+    if (d.dtype < TN_F32 || d.dtype > TN_BF16 || (d.layout != TN_PLANAR && d.layout != TN_INTERLEAVED) ||
+        (d.channel_order != MPCVR_TENSOR_RGB && d.channel_order != MPCVR_TENSOR_BGR) || d.reserved != 0) {
+        *why = "unknown dtype, layout or channel order, or reserved is not 0"; return MPCVR_E_INVALIDARG;
+    }
+    for (int k = 0; k < 3; k++)
+        if (!TensorFactorOk(d.scale[k]) || !TensorFactorOk(d.bias[k])) { *why = "scale and bias must be finite, and 0 or of magnitude 2^-100 .. 2^100"; return MPCVR_E_INVALIDARG; }
+    const bool planar = d.layout == TN_PLANAR;
+    const int64_t es = TensorElementSize(d.dtype), kMaxPitch = (int64_t)1 << 47;      // (h rows and three planes of that stay far inside 64 bits)
+    if (d.row_pitch < es * (planar ? 1 : 3) * w || d.row_pitch > kMaxPitch || (planar && (d.plane_pitch < 1 || d.plane_pitch > kMaxPitch))) {
+        *why = "row pitch smaller than a row, or a pitch that is not positive or beyond 2^47"; return MPCVR_E_INVALIDARG;
+    }
+    if (((uintptr_t)tensor | (uintptr_t)d.row_pitch | (planar ? (uintptr_t)d.plane_pitch : 0)) & (uintptr_t)(es - 1)) {
+        *why = "tensor and pitches must be multiples of the element size"; return MPCVR_E_INVALIDARG;
+    }
+    if (pitch < w * bytes || (pitch & (bytes - 1)) || ((uintptr_t)sample & (uintptr_t)(bytes - 1))) {
+        *why = "sample pitch smaller than a row, or sample or pitch no multiple of the component size"; return MPCVR_E_INVALIDARG;
+    }
+    // the tensor is only read: its planes may share bytes with each other, not with a plane of the sample
+    RtSpan tp[3], sp[3];
+    const int np = TensorPlaneSpans(d, tensor, w, h, tp);
+    for (int k = 0; k < 3; k++) sp[k] = RowsSpan((const uint8_t *)sample + (size_t)k * (size_t)pitch * (size_t)h, (size_t)pitch, h, (size_t)w * bytes);
+    if (sample) {
+        for (int a = 0; a < 3; a++) {
+            for (int b = 0; b < np; b++)
+                if (sp[a].Overlaps(tp[b])) { *why = "a plane of the tensor overlaps a plane of the sample"; return MPCVR_E_INVALIDARG; }
+            for (int b = a + 1; b < 3; b++)      // (cannot happen while pitch >= a row and the planes lie pitch * h apart: checked, not assumed)
+                if (sp[a].Overlaps(sp[b])) { *why = "two planes of the sample overlap"; return MPCVR_E_INVALIDARG; }
+        }
+    }
+    if (checkOnly) return MPCVR_S_OK;
+    SampleParams p = SampleLaunchParams(d, w, h, bytes, maxcode, pitch);
+    p.src = (const uint8_t *)tensor; p.dst = (uint8_t *)sample;
+    p.srcvec &= ((uintptr_t)tensor & (uintptr_t)(TensorVectorBytes(d.dtype) - 1)) == 0;
+    p.dstvec &= ((uintptr_t)sample & (uintptr_t)(4 * bytes - 1)) == 0;
+    if (LaunchSampleFromTensor(p, d.dtype, d.layout, bytes, stream) != hipSuccess) { *why = "k_sample_from_tensor launch failed"; return MPCVR_E_FAIL; }
+    return MPCVR_S_OK;
+}
+
+// CopySample(MPCVR_MEM_HOST) with the pass in place of the host-to-device copy: the same slot ring, device buffers and events.  The pass is
+// queued on the context stream (the caller's tensor is free in stream order behind the call); `uploaded` is recorded behind it there, so a
+// frame lane waits for the pass exactly as it waits for an upload (ProcessFrame).
+HRESULT CHipVideoProcessor::CopySampleTensor(const void *tensor, const mpcvr_tensor_desc *desc)
+{
+    if (!m_bInit || !m_srcParams) return Fail(MPCVR_E_NOT_VALID_STATE, "InitMediaType has not been called");
+    if (!tensor || !desc) return Fail(MPCVR_E_POINTER, "null tensor or description");
+    // (every refusal comes before anything is touched: the current sample, its upload slot and the stream it was last drawn on stay as they are)
+    const char *why = "";
+    if (HRESULT bad = SampleSurface(tensor, desc, m_srcWidth, m_srcHeight, m_srcParams->cformat, nullptr, m_srcPitch, nullptr, true, &why)) return Fail(bad, why);
+    (void)hipSetDevice(m_device);
+    const size_t bytes = (size_t)m_srcPitch * m_srcLines;
+    HRESULT hr;
+    MarkConsumed();                                  // the previous sample is done with as far as the host is concerned
+    m_curSlot = -1;
+    m_lastRun = nullptr;
+    m_curSample = nullptr;                           // (a failure below leaves no sample rather than a slot half written)
+    const int si = m_upNext;
+    m_upNext = (m_upNext + 1) % kUploadSlots;
+    UploadSlot &u = m_up[si];
+    if (!u.uploaded) {
+        if ((hr = CheckHip(hipEventCreateWithFlags(&u.uploaded, hipEventDisableTiming), "upload event"))) return hr;
+        if ((hr = CheckHip(hipEventCreateWithFlags(&u.consumed, hipEventDisableTiming), "consume event"))) return hr;
+    }
+    // the slot's device buffer is free once the work that last used it has completed
+    if (u.inFlight && (hr = CheckHip(hipEventSynchronize(u.consumedRecorded ? u.consumed : u.uploaded), "upload slot wait"))) return hr;
+    if ((hr = CheckHip(u.dev.CheckCreate(bytes), "upload buffer"))) return hr;
+    if ((hr = SampleSurface(tensor, desc, m_srcWidth, m_srcHeight, m_srcParams->cformat, u.dev.ptr, m_srcPitch, m_stream, false, &why))) return Fail(hr, why);
+    m_launches++;
+    if ((hr = CheckHip(hipEventRecord(u.uploaded, m_stream), "upload event"))) return hr;
+    m_lanes.NoteStreamWork();
+    u.inFlight = true; u.consumedRecorded = false;
+    m_curSlot = si;
+    return PrepareSample((const uint8_t *)u.dev.ptr, &m_curSample);
+}
+
+// A batch from tensors (include/mpcvr.h: mpcvr_process_batch_from_tensors).  Everything about the arguments is answered first; then the
+// call is cut into chunks of PlanBatchSamples' size, and each chunk is ONE k_sample_from_tensor launch with a frame dimension into the
+// context-owned sample surface and the batch machinery behind it, both on the context stream: stream order covers the surface's write,
+// read and reuse by the next chunk.
+HRESULT CHipVideoProcessor::ProcessBatchFromTensors(int n, const void *const *tensors, const mpcvr_tensor_desc *desc, void *const *dsts, int rtPitch)
+{
+    const BatchRecord record(*this, n > 0 ? n : 0);
+    if (!m_bInit || !m_srcParams) return Fail(MPCVR_E_NOT_VALID_STATE, "InitMediaType has not been called");
+    if (n <= 0) return Fail(MPCVR_E_INVALIDARG, "empty batch");
+    if (!tensors || !dsts || !desc) return Fail(MPCVR_E_POINTER, "null array of tensors or frames, or null description");
+    for (int i = 0; i < n; i++)
+        if (!tensors[i] || !dsts[i]) return Fail(MPCVR_E_POINTER, "null tensor or frame in batch");
+    int bytes, maxcode;
+    if (!SampleFormat(m_srcParams->cformat, &bytes, &maxcode)) return Fail(MPCVR_E_INVALIDARG, "the input must be GBRP8, GBRP10 or GBRP16");
+    if (HRESULT bad = CheckBatchArgs(n, tensors, dsts, rtPitch)) return bad;
+    const int w = m_srcWidth, h = m_srcHeight;
+    const char *why = "";
+    for (int i = 0; i < n; i++)
+        if (HRESULT bad = SampleSurface(tensors[i], desc, w, h, m_srcParams->cformat, nullptr, m_srcPitch, nullptr, true, &why)) return Fail(bad, why);
+    BatchSampleLayout lay;
+    if (!PlanBatchSamples(m_srcPitch, h, n, m_yuvBudget, &lay)) return Fail(MPCVR_E_INVALIDARG, "sample layout");
+
+    (void)hipSetDevice(m_device);
+    if (HRESULT bad = m_planDirty ? UpdatePlan() : MPCVR_S_OK) return bad;
+    const int most = lay.framesPerChunk;
+    HRESULT hr;
+    if ((hr = CheckHip(m_sampleSurf.CheckCreate(lay.frameStride * (size_t)most), "batch sample surface"))) return hr;
+    std::vector<const void *> samples((size_t)most);
+    for (int i = 0; i < most; i++) samples[i] = (const uint8_t *)m_sampleSurf.ptr + (size_t)i * lay.frameStride;
+    // (dstvec holds for every chunk: every frame of the surface starts on 256 bytes)
+    const SampleParams sp = SampleLaunchParams(*desc, w, h, bytes, maxcode, m_srcPitch);
+    int chunks = 0;
+    for (int at = 0; at < n && !hr; at += most, chunks++) {
+        const int m = std::min(most, n - at);
+        BatchRun run{m, samples.data(), dsts + at, rtPitch};
+        run.on = RunOn{m_stream};
+        OrderOnContextStream();          // behind every frame and batch the lanes hold (the last chunk's readers of the surface are on this stream already)
+        {
+            // the tensors' table through the frame tables' ring; the lease ends behind the pass
+            SlotLease table;
+            SampleFrame *fr;
+            if ((hr = m_tableRing.Next(sizeof(SampleFrame) * m, sizeof(SampleFrame) * 64, (void **)&fr))) break;
+            SampleParams p = sp;
+            for (int i = 0; i < m; i++) {
+                fr[i] = SampleFrame{(const uint8_t *)tensors[at + i], (uint8_t *)const_cast<void *>(samples[i])};
+                p.srcvec &= ((uintptr_t)tensors[at + i] & (uintptr_t)(TensorVectorBytes(desc->dtype) - 1)) == 0;      // the vector loads only if every tensor of the launch allows them
+            }
+            if ((hr = m_tableRing.Send(sizeof(SampleFrame) * m, m_stream, "sample table", &table))) break;
+            p.frames = (const SampleFrame *)table.dev;
+            if ((hr = CheckHip(LaunchSampleFromTensor(p, desc->dtype, desc->layout, bytes, m_stream, m), "k_sample_from_tensor"))) break;
+        }
+        if (m_plan.errdiff) hr = ProcessBatchErrDiff(run);
+        else {
+            BatchRoutePlan rp = ClassifyBatch(run);
+            hr = RunBatchRoute(rp, run);
+        }
+    }
+    m_yuvLastInfo = ";sample_chunks=" + std::to_string(chunks);
+    return hr;
 }
 
 HRESULT CHipVideoProcessor::GetBackBuffer(void **ptr, int *pitch, int *w, int *h)

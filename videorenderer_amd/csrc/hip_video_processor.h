@@ -14,6 +14,7 @@
 #include "vp_lanes.h"
 #include "vp_measure.h"
 #include "vp_tensor.h"
+#include "vp_tensor_in.h"
 #include "vp_launch.h"
 #include "vp_params.h"
 #include "vp_plan.h"
@@ -56,6 +57,12 @@ HRESULT MeasureSurface(const void *src, int srcPitch, int srcFmt, int w, int h, 
 // EXTENSION (mpcvr_tensor_pass, include/mpcvr.h): checks every argument, then — unless checkOnly — launches k_tensor on `stream`.
 // MPCVR_E_POINTER / MPCVR_E_INVALIDARG with nothing launched or written
 HRESULT TensorSurface(const void *src, int srcPitch, int srcFmt, int w, int h, const mpcvr_tensor_desc *desc, void *dst, hipStream_t stream,
+                      bool checkOnly, const char **why = nullptr);
+
+// EXTENSION (mpcvr_sample_pass, include/mpcvr.h): checks every argument, then — unless checkOnly — launches k_sample_from_tensor on `stream`.
+// MPCVR_E_POINTER / MPCVR_E_INVALIDARG with nothing launched or written.  checkOnly takes sample = nullptr for a sample that is still to be
+// allocated (it cannot overlap the tensor; its alignment is the allocator's)
+HRESULT SampleSurface(const void *tensor, const mpcvr_tensor_desc *desc, int w, int h, int cformat, void *sample, int pitch, hipStream_t stream,
                       bool checkOnly, const char **why = nullptr);
 
 class CHipVideoProcessor {
@@ -102,6 +109,11 @@ public:
     // the batch shares ProcessBatchYuv's surfaces, budget and chunk loop
     HRESULT RenderTensor(int field, const mpcvr_tensor_desc &desc, void *dst);
     HRESULT ProcessBatchTensor(int n, const void *const *srcs, const mpcvr_tensor_desc *desc, void *const *dsts);
+    // EXTENSION (mpcvr_copy_sample_tensor / mpcvr_process_batch_from_tensors): a model's float tensor as the sample of a GBRP8 / 10 / 16
+    // input — k_sample_from_tensor (vp_tensor_in.h) into an upload slot in place of the host-to-device copy; a batch through a
+    // context-owned sample surface, one pass per chunk in front of the chunk's batch, everything on the context stream
+    HRESULT CopySampleTensor(const void *tensor, const mpcvr_tensor_desc *desc);
+    HRESULT ProcessBatchFromTensors(int n, const void *const *tensors, const mpcvr_tensor_desc *desc, void *const *dsts, int rtPitch);
     HRESULT SetBatchYuvBudget(size_t bytes) { m_yuvBudget = bytes; return MPCVR_S_OK; }
     std::string GetLastBatchInfo() const;
     HRESULT ProcessBatchDovi(int n, const void *const *srcs, void *const *dsts, int rtPitch, const mpcvr_dovi_metadata *rpus);
@@ -439,6 +451,7 @@ private:
     YuvSurface m_yuvSurf[FrameLanes::kFrameLanes];
     size_t m_yuvBudget = 0;            // SetBatchYuvBudget; 0: kBatchYuvDefaultBudget
     std::string m_yuvLastInfo;         // ";yuv_chunks=..;yuv_lanes=.." (";tensor_chunks=..;tensor_lanes=..") of the last batch call, if it was a ProcessBatchYuv (ProcessBatchTensor)
+    DevBuffer m_sampleSurf;            // ProcessBatchFromTensors: the samples of one chunk side by side (PlanBatchSamples), written and read in stream order on the context stream
     // the chunk loop of both: surfaces, lanes and order; writesOf(at, m): what the chunk writes for the caller, pass(run, at): its pass
     template <class WritesOf, class Pass>
     HRESULT RunSurfaceChunks(int n, const void *const *srcs, const BatchYuvLayout &lay, const char *tag, WritesOf writesOf, Pass pass);

@@ -267,6 +267,41 @@ int32_t mpcvr_process_batch_tensor(mpcvr_ctx *ctx, int32_t n, const void *const 
     return ctx->vp.ProcessBatchTensor(n, srcs, desc, dsts);
 }
 
+// EXTENSION: a model's float tensor as the sample (include/mpcvr.h; k_sample_from_tensor vp_tensor_in.hip, the arithmetic vp_tensor_core.h,
+// SampleSurface and CHipVideoProcessor::CopySampleTensor / ProcessBatchFromTensors hip_video_processor.cpp, PlanSampleCode / PlanBatchSamples vp_plan.cpp)
+int32_t mpcvr_plan_sample_code(int32_t dtype, int32_t cformat, uint32_t element_bits, float scale, float bias, uint32_t *code)
+{
+    if (!code) return MPCVR_E_POINTER;
+    return mpcvr::PlanSampleCode(dtype, cformat, element_bits, scale, bias, code) ? MPCVR_S_OK : MPCVR_E_INVALIDARG;
+}
+
+int32_t mpcvr_sample_pass(const void *tensor, const mpcvr_tensor_desc *desc, int32_t w, int32_t h, int32_t cformat, void *sample, int32_t pitch, void *stream)
+{
+    return mpcvr::SampleSurface(tensor, desc, w, h, cformat, sample, pitch, (hipStream_t)stream, false);
+}
+
+int32_t mpcvr_copy_sample_tensor(mpcvr_ctx *ctx, const void *tensor, const mpcvr_tensor_desc *desc)
+{
+    CTX_OR_FAIL();
+    return ctx->vp.CopySampleTensor(tensor, desc);
+}
+
+int32_t mpcvr_plan_batch_from_tensors(int32_t pitch, int32_t h, int32_t n, size_t budget_bytes, size_t *frame_stride, int32_t *frames_per_chunk, int32_t *chunks)
+{
+    mpcvr::BatchSampleLayout lay;
+    if (!mpcvr::PlanBatchSamples(pitch, h, n, budget_bytes, &lay)) return MPCVR_E_INVALIDARG;
+    if (frame_stride) *frame_stride = lay.frameStride;
+    if (frames_per_chunk) *frames_per_chunk = lay.framesPerChunk;
+    if (chunks) *chunks = lay.chunks;
+    return MPCVR_S_OK;
+}
+
+int32_t mpcvr_process_batch_from_tensors(mpcvr_ctx *ctx, int32_t n, const void *const *tensors, const mpcvr_tensor_desc *desc, void *const *dsts, int32_t dst_pitch)
+{
+    CTX_OR_FAIL();
+    return ctx->vp.ProcessBatchFromTensors(n, tensors, desc, dsts, dst_pitch);
+}
+
 int32_t mpcvr_get_param_blob(mpcvr_ctx *ctx, void *buf, size_t *size) { CTX_OR_FAIL(); return ctx->vp.GetParamBlob(buf, size); }
 int32_t mpcvr_get_fused_tables(mpcvr_ctx *ctx, void *buf, size_t *size) { CTX_OR_FAIL(); return ctx->vp.GetFusedTables(buf, size); }
 int32_t mpcvr_set_param_blob(mpcvr_ctx *ctx, const void *buf, size_t size) { CTX_OR_FAIL(); return ctx->vp.SetParamBlob(buf, size); }

@@ -10,6 +10,7 @@
 #include "vp_encode.h"
 #include "vp_measure.h"
 #include "vp_tensor.h"
+#include "vp_tensor_in.h"
 #include "vp_crmath.h"      // the shaders' sin / cos as defined functions (the weights the resize shaders compute per pixel are computed here, once)
 
 namespace mpcvr {
@@ -300,6 +301,43 @@ bool PlanTensorValue(int dtype, int src_fmt, uint32_t code, float scale, float b
     case TN_BF16: *bits = TensorElementBits<TN_BF16>(code, scale, bias); return true;
     }
     return false;
+}
+
+// ------------------------------------------------------------------------------------------------
+// EXTENSION — the way back: one element of the sample pass on the host (include/mpcvr.h: mpcvr_plan_sample_code), again the functions of
+// vp_tensor_core.h the kernel converts with, and the integers of the batch's sample surface.  No reference line: the reference has no float input.
+// ------------------------------------------------------------------------------------------------
+bool SampleFormat(int cformat, int *bytes, int *maxcode)
+{
+    switch (cformat) {
+    case MPCVR_CF_GBRP8: *bytes = 1; *maxcode = 255; return true;
+    case MPCVR_CF_GBRP10: *bytes = 2; *maxcode = 1023; return true;
+    case MPCVR_CF_GBRP16: *bytes = 2; *maxcode = 65535; return true;
+    }
+    return false;
+}
+
+bool PlanSampleCode(int dtype, int cformat, uint32_t element_bits, float scale, float bias, uint32_t *code)
+{
+    int bytes, maxcode;
+    if (!SampleFormat(cformat, &bytes, &maxcode) || !TensorFactorOk(scale) || !TensorFactorOk(bias)) return false;
+    if (dtype != TN_F32 && element_bits > 0xffffu) return false;
+    switch (dtype) {
+    case TN_F32: *code = SampleCode<TN_F32>(element_bits, scale, bias, (float)maxcode); return true;
+    case TN_F16: *code = SampleCode<TN_F16>(element_bits, scale, bias, (float)maxcode); return true;
+    case TN_BF16: *code = SampleCode<TN_BF16>(element_bits, scale, bias, (float)maxcode); return true;
+    }
+    return false;
+}
+
+bool PlanBatchSamples(int pitch, int h, int n, size_t budget, BatchSampleLayout *out)
+{
+    if (n <= 0 || pitch < 1 || h < 1 || h > 32768) return false;
+    if (!budget) budget = kBatchYuvDefaultBudget;
+    out->frameStride = ((size_t)3 * (size_t)pitch * (size_t)h + 255) & ~(size_t)255;
+    out->framesPerChunk = FramesPerChunk(n, out->frameStride, budget);
+    out->chunks = (n + out->framesPerChunk - 1) / out->framesPerChunk;
+    return true;
 }
 
 bool PlanEncode(int out_cformat, int src_fmt, uint32_t extfmt, int w, int h, EncodePlan *plan)

@@ -96,4 +96,72 @@ template <bool IN10> MPCVR_TN_HD uint32_t TensorCode(uint32_t texel, int k /* 0 
     return IN10 ? (texel >> (10 * k)) & 0x3ffu : (texel >> (16 - 8 * k)) & 0xffu;
 }
 
+// ------------------------------------------------------------------------------------------------
+// The way back (EXTENSION: include/mpcvr.h, mpcvr_sample_pass; kernel vp_tensor_in.hip; host mpcvr_plan_sample_code; model
+// tests/tensor_in_model.py): a tensor element to the code of a GBRP8 / GBRP10 / GBRP16 sample.
+//   x = the element widened exactly to fp32, magnitudes below 2^-126 taken as +0;  t = x * scale, rounded to fp32;  u = t + bias, rounded
+//   to fp32 (two operations, never fused);  code = 0 unless u > 0, maxcode where u >= maxcode, else u rounded to the nearest integer, ties
+//   to even.
+// A subnormal t, kept or flushed, cannot change the code: without a bias u = t and |t| < 2^-126 < 0.5 gives code 0 either way (0, a
+// positive value that rounds to 0, or a negative one); with a bias |bias| >= 2^-100, the spacing of fp32 there is at least 2^-123, and
+// |t| < 2^-126 is under half of it, so t + bias rounds to bias whether t was kept or not.
+// ------------------------------------------------------------------------------------------------
+MPCVR_TN_HD float TensorBitsFloat(uint32_t u) { float v; memcpy(&v, &u, 4); return v; }
+
+// binary16 bits -> the fp32 bits of the same value, in integers (subnormals are normal fp32 numbers; NaN payloads move up)
+MPCVR_TN_HD uint32_t TensorHalfWidenSoft(uint32_t h)
+{
+    const uint32_t sign = (h & 0x8000u) << 16, e = (h >> 10) & 0x1fu;
+    uint32_t m = h & 0x3ffu;
+    if (e == 0x1fu) return sign | 0x7f800000u | (m << 13);
+    if (e) return sign | ((e + 112u) << 23) | (m << 13);
+    if (!m) return sign;
+    uint32_t ex = 113u;                                // m * 2^-24: shift the leading bit up to the implicit one
+    while (!(m & 0x400u)) { m <<= 1; ex--; }
+    return sign | (ex << 23) | ((m & 0x3ffu) << 13);
+}
+
+// the fp32 bits of an element of the tensor (bits: the low 16 for F16 / BF16), magnitudes below 2^-126 as +0
+template <int DTYPE> MPCVR_TN_HD uint32_t SampleWiden(uint32_t bits)
+{
+    uint32_t u;
+    if (DTYPE == TN_F32) u = bits;
+    else if (DTYPE == TN_BF16) u = bits << 16;
+    else {
+#if defined(__HIP_DEVICE_COMPILE__)
+        uint16_t b = (uint16_t)bits; _Float16 h; memcpy(&h, &b, 2);
+        u = TensorFloatBits((float)h);                 // v_cvt_f32_f16: exact, fp16 subnormals kept (the kernel's mode register is the default)
+#else
+        u = TensorHalfWidenSoft(bits & 0xffffu);
+#endif
+    }
+    return (u & 0x7f800000u) ? u : 0u;                 // an empty exponent field: a subnormal or a zero of either sign
+}
+
+// u = x * scale + bias in two roundings (the pragma: as TensorValue)
+MPCVR_TN_HD float SampleValue(float x, float scale, float bias)
+{
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#else
+#pragma STDC FP_CONTRACT OFF
+#endif
+    const float t = x * scale;
+    return t + bias;
+}
+
+// maxcode as a float is exact (255, 1023, 65535); below it and above 0 the nearest integer, ties to even (v_rndne_f32 / rintf in the
+// default rounding mode), is at most maxcode
+MPCVR_TN_HD uint32_t SampleCodeOf(float u, float maxcode)
+{
+    if (!(u > 0.0f)) return 0u;                        // NaN, -inf, negatives, 0
+    if (u >= maxcode) return (uint32_t)maxcode;
+    return (uint32_t)__builtin_rintf(u);
+}
+
+template <int DTYPE> MPCVR_TN_HD uint32_t SampleCode(uint32_t bits, float scale, float bias, float maxcode)
+{
+    return SampleCodeOf(SampleValue(TensorBitsFloat(SampleWiden<DTYPE>(bits)), scale, bias), maxcode);
+}
+
 }  // namespace mpcvr
