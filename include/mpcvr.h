@@ -440,6 +440,81 @@ int32_t mpcvr_sample_pass(const void *tensor, const mpcvr_tensor_desc *desc, int
  * tensor and desc is answered before anything is touched: the previous sample stays current. */
 int32_t mpcvr_copy_sample_tensor(mpcvr_ctx *ctx, const void *tensor, const mpcvr_tensor_desc *desc);
 
+/* EXTENSION — motion-adaptive deinterlacing of a sample at field rate: from the frames prev, cur, next one progressive frame per FIELD of
+ * cur, which the convert path, the scalers, tone mapping and every batch call then take like any progressive sample.  The reference hands
+ * bob and adaptive deinterlacing to the fixed-function D3D11 video processor (m_iVPDeinterlacing, m_bDeintDouble), which DESIGN.md §7 rules
+ * out of scope, and its own shader path has only the blend (bDeintBlend, 4:2:0, frame rate): there is no reference line to cite.  The filter
+ * is the well-known edge-directed spatial prediction held inside a temporal band (the Yadif scheme), spelled out here in integers so that no
+ * outside code is needed and no bit is left open; it is modelled bit for bit by tests/deint_model.py (arithmetic: csrc/vp_deint_core.h,
+ * DeintComponent, which the kernel and mpcvr_deint_plane_host both compile).
+ *   Planes.  A sample is deinterlaced plane by plane.  A plane is `lines` rows of `comps` unsigned components of `bytes` (1 or 2) each; the
+ *   horizontal neighbour step is cs: 1 for the Y, U, V, G, B, R and gray planes, 2 for the interleaved UV plane of the bi-planar formats
+ *   (the neighbours of a U are U's).  Plane offsets and pitches are those of a sample as mpcvr_set_input declares it for (cformat, w, h,
+ *   pitch), pitch = 0 meaning the default pitch as there (mpcvr_plan_deint_planes):
+ *     bi-planar (NV12, P010, P016, P210, P216)   Y at 0: h lines of w components at pitch;  UV at pitch * h: h / div_h lines of w components
+ *                                                (w / 2 pairs) at pitch, cs = 2
+ *     three planes (YV12, YV16, YV24, YUV420P8 / 422P8 / 444P8, YUV420P10 / 16, YUV422P10 / 16, YUV444P10 / 16, GBRP8 / 10 / 16)
+ *                                                plane 0 as Y above;  planes 1 and 2: h / div_h lines of w / div_w components at pitch / div_w
+ *                                                (integer division), at pitch * h and at pitch * h + (pitch / div_w) * (h / div_h)
+ *     gray (Y8, Y10, Y16)                        the one plane
+ *   (div_w, div_h = 2, 2 for 4:2:0; 2, 1 for 4:2:2; 1, 1 otherwise.)  Every packed format — YUY2, UYVY, Y210, Y216, v210, AYUV, Y410, Y416
+ *   and the interleaved RGB formats — is refused with MPCVR_E_INVALIDARG, and so is a sample one of whose planes has fewer than 2 lines.
+ *   Components are whole 8- or 16-bit integers; mask = 0xff / 0xffff.  For the planar 10-bit formats (YUV4xxP10, GBRP10, Y10) a word is
+ *   masked to bits 0 .. 9 on load (mask = 0x3ff): the library never reads bits 10 .. 15 there, and the output has them zero — in the kept
+ *   lines too.  P010 and P210 use all 16 bits, as the library's reader does.
+ *   Arguments.  keep (0 / 1) is the parity of the lines that belong to the field being shown: they are copied from cur.  first (0 / 1) says
+ *   whether that field is the temporally first field of cur.  mode is MPCVR_DEINT_ADAPTIVE_EXT (with the spatial interlacing check) or
+ *   MPCVR_DEINT_ADAPTIVE_NOCHECK_EXT.
+ *   Per missing component — line y with (y & 1) != keep, column x — in signed 32-bit integers, >> an arithmetic shift:
+ *     A, B       the frames holding the missing-parity field just before and just after the shown field: (prev, cur) if first, else (cur, next)
+ *     ym, yp     y - 1 if y - 1 >= 0, else y + 1;   y + 1 if y + 1 < lines, else y - 1.   up = cur[ym], dn = cur[yp]
+ *     columns    an index x + k cs is clamped into the component's own channel: to [x mod cs, comps - cs + (x mod cs)]
+ *     c = up[x], e = dn[x], d = (A[y][x] + B[y][x]) >> 1
+ *     t0 = |A[y][x] - B[y][x]|;  t1 = (|prev[ym][x] - c| + |prev[yp][x] - e|) >> 1;  t2 the same with next;  diff = max(t0 >> 1, t1, t2)
+ *     score(j) = sum over k = -1, 0, 1 of |up[x + (k + j) cs] - dn[x + (k - j) cs]|;   pred(j) = (up[x + j cs] + dn[x - j cs]) >> 1
+ *     best = score(0) - 1, sp = pred(0); then for s = -1 and after it s = +1: if score(s) < best { best = score(s), sp = pred(s); and only
+ *                then, if score(2 s) < best { best = score(2 s), sp = pred(2 s) } }
+ *     check      with mode 0, and only where y - 2 >= 0 and y + 2 < lines: b = (A[y-2][x] + B[y-2][x]) >> 1, f = (A[y+2][x] + B[y+2][x]) >> 1,
+ *                mx = max(d - e, d - c, min(b - c, f - e)), mn = min(d - e, d - c, max(b - c, f - e)), diff = max(diff, mn, -mx)
+ *     out = min(max(sp, d - diff), d + diff)
+ *   diff >= 0 always, and out lies between sp and d: it stays in the component's range without a clamp.  With prev == cur == next and
+ *   mode 1 the output is cur (d = the missing line itself, diff = 0); with mode 0 it is not, on pictures with vertical detail.
+ *   The three sources are only read and may alias each other: a caller passes prev = cur at a stream's first frame and next = cur at its
+ *   last.  No byte outside the destination's pixels is written; source bytes between a row's pixels and the pitch are never read into a
+ *   pixel; all addressing is 64-bit.  Vector loads and stores are taken where pointers, plane offsets and pitches allow them (on 4 cs
+ *   bytes-per-component bytes), chosen per launch.
+ * Why this filter: it needs no motion vectors and no state beyond three frames, every tap is a neighbour in a plane (so it runs plane by
+ * plane in the sample's own format, in front of the unchanged convert path), and its integer form leaves nothing to a float mode. */
+enum { MPCVR_DEINT_ADAPTIVE_EXT = 0, MPCVR_DEINT_ADAPTIVE_NOCHECK_EXT = 1 };
+typedef struct mpcvr_deint_plane { size_t offset; int32_t pitch, comps, lines, bytes, cs, mask; } mpcvr_deint_plane;
+/* Host, no GPU: the planes of a sample, *planes of them (1 .. 3) in out[].  MPCVR_E_POINTER for a NULL planes or out; MPCVR_E_INVALIDARG
+ * for exactly what the pass refuses about format, size and pitch (the rules of mpcvr_set_input; a plane of fewer than 2 lines). */
+int32_t mpcvr_plan_deint_planes(int32_t cformat, int32_t w, int32_t h, int32_t pitch, int32_t *planes, mpcvr_deint_plane out[3]);
+/* Host, no GPU: one plane in HOST memory, rows src_pitch / dst_pitch bytes apart, by the definition above — compiled from the per-component
+ * function the kernel compiles.  dst must not overlap a source.  MPCVR_E_POINTER for a NULL pointer; MPCVR_E_INVALIDARG for bytes or cs
+ * outside {1, 2}, comps no positive multiple of cs, lines < 2, a mask outside the component, keep, first or mode outside their sets,
+ * a pitch below a row, or a pointer or pitch that is no multiple of bytes. */
+int32_t mpcvr_deint_plane_host(const void *prev, const void *cur, const void *next, int64_t src_pitch, int32_t comps, int32_t lines,
+                               int32_t bytes, int32_t cs, int32_t mask, int32_t keep, int32_t first, int32_t mode, void *dst, int64_t dst_pitch);
+/* One standalone pass over three DEVICE samples of (cformat, w, h, pitch) into a fourth of (cformat, w, h, dst_pitch); pitch and dst_pitch
+ * each obey mpcvr_set_input's pitch rules for the format (0: the default pitch).  stream = a hipStream_t or NULL.  One k_deint launch
+ * (csrc/vp_deint.hip) per distinct (bytes, cs) among the planes: one for the three-plane and gray formats, two for the bi-planar ones.
+ * Refusals, with nothing launched and nothing written: MPCVR_E_POINTER for a NULL pointer; MPCVR_E_INVALIDARG for a format, size or pitch
+ * outside the rules, a sample that is no multiple of the component size, a keep, first or mode outside its set, and a destination plane
+ * (first pixel to last pixel of its last row) that overlaps a plane of a source or another destination plane. */
+int32_t mpcvr_deint_pass(const void *prev, const void *cur, const void *next, int32_t cformat, int32_t w, int32_t h, int32_t pitch,
+                         int32_t keep, int32_t first, int32_t mode, void *dst, int32_t dst_pitch, void *stream);
+/* Field `field` (0 the first, 1 the second) of cur, deinterlaced, becomes the current sample.  field_order is 1 for top field first, 2 for
+ * bottom field first (the values of mpcvr_set_sample_format): first = (field == 0), keep = field for top field first, 1 - field for bottom
+ * field first.  prev, cur, next are DEVICE samples of the context's input layout (mpcvr_set_input); the input must be a format the pass
+ * takes.  The call takes an upload slot exactly as mpcvr_copy_sample_tensor does, with k_deint in the place of the copy, queued on the
+ * context stream and recorded with the same events: frame lanes wait for it as for an upload, and the three samples are free in that
+ * stream's order behind the call.  It neither reads nor changes the context's sample format: the sample now IS a progressive frame, so a
+ * caller leaves mpcvr_set_sample_format at 0 (or bDeintBlend off).  Every refusal — MPCVR_E_NOT_VALID_STATE before mpcvr_set_input,
+ * MPCVR_E_INVALIDARG for a field_order or field outside its set, and whatever mpcvr_deint_pass refuses — comes before anything is touched:
+ * the previous sample stays current. */
+int32_t mpcvr_copy_sample_fields(mpcvr_ctx *ctx, const void *prev, const void *cur, const void *next, int32_t field_order, int32_t field, int32_t mode);
+
 /* Configure — DX11VideoProcessor.cpp:3800-4050: diff each field, rebuild only what changed. */
 int32_t mpcvr_configure(mpcvr_ctx *ctx, const mpcvr_settings *settings);
 
@@ -648,6 +723,30 @@ int32_t mpcvr_plan_batch_from_tensors(int32_t pitch, int32_t h, int32_t n, size_
                                       size_t *frame_stride, int32_t *frames_per_chunk, int32_t *chunks);
 int32_t mpcvr_process_batch_from_tensors(mpcvr_ctx *ctx, int32_t n, const void *const *tensors, const mpcvr_tensor_desc *desc,
                                          void *const *dsts, int32_t dst_pitch);
+/* EXTENSION — a batch at field rate (the pass itself: mpcvr_deint_pass above).  frames[] holds n + 2 DEVICE samples of the context's input
+ * layout: interior frame i = 1 .. n is deinterlaced with frames[i - 1] and frames[i + 1] as its neighbours (a caller repeats the first and
+ * the last frame of a stream at the ends).  fields_per_frame is 1 (field 0 of every frame: frame rate) or 2 (both fields: field rate);
+ * dsts[] holds n * fields_per_frame render targets, target (i - 1) * fields_per_frame + f showing field f of frame i, with keep and first
+ * from field_order as for mpcvr_copy_sample_fields.  Target k holds, byte for byte, what
+ *     mpcvr_deint_pass(frames[i - 1], frames[i], frames[i + 1], ..., keep, first, mode, sample k of the caller's, pitch), n * fields_per_frame times, then
+ *     mpcvr_process_batch(samples -> dsts, dst_pitch)
+ * leave, with ONE pass per chunk of output frames — its frame dimension: one k_deint launch per distinct (bytes, cs) among the planes,
+ * reading a device table of (prev, cur, next, sample, keep, first) per output frame sent through the frame tables' ring — and no samples
+ * of the caller's: they live in the context-owned sample surface of mpcvr_process_batch_from_tensors, output frame i of a chunk at i *
+ * frame_stride, frame_stride = pitch * lines rounded up to 256 (mpcvr_plan_batch_deint; pitch and lines are the input's, lines as
+ * mpcvr_get_frame_bytes counts them: bytes / pitch).  A chunk is what fits the budget of mpcvr_set_batch_yuv_budget (0: the default), at
+ * least one frame, at most all — the library's one chunk rule.  Every chunk runs in stream order on the context stream: the pass, then the
+ * chunk's mpcvr_process_batch work; the batch lanes are not used.  The samples are free in stream order behind the call; the targets are
+ * complete after mpcvr_synchronize.  As for mpcvr_copy_sample_fields the sample format stays progressive.
+ * Refusals, answered before anything is drawn, allocated or written: MPCVR_E_NOT_VALID_STATE before mpcvr_set_input; MPCVR_E_POINTER for
+ * a NULL array or entry; MPCVR_E_INVALIDARG for n <= 0, a fields_per_frame, field_order or mode outside its set, an input format the pass
+ * does not take, a sample that is no multiple of the component size, and whatever mpcvr_process_batch refuses about dsts and dst_pitch.
+ * mpcvr_get_last_batch_info afterwards: "launches" counts the pass launches, and ";deint_chunks=<k>" follows. */
+int32_t mpcvr_plan_batch_deint(int32_t pitch, int32_t lines, int32_t n_out, size_t budget_bytes,
+                               size_t *frame_stride, int32_t *frames_per_chunk, int32_t *chunks);
+int32_t mpcvr_process_batch_deint(mpcvr_ctx *ctx, int32_t n, const void *const *frames /* n + 2 device samples */, int32_t field_order,
+                                  int32_t fields_per_frame /* 1 or 2 */, int32_t mode, void *const *dsts /* n * fields_per_frame targets */,
+                                  int32_t dst_pitch);
 
 /* Multi-GPU: the parameter blob (colour matrix, luminance scale, gamut matrix, resize phase weights,
  * dither table) a rank-0 context computes and every other rank adopts after an RCCL broadcast.

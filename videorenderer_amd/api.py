@@ -170,6 +170,16 @@ def tensor_desc(dtype, layout, row_pitch, plane_pitch=0, scale=(1 / 255,) * 3, b
     return d
 
 
+# (extension) motion-adaptive deinterlacing: the modes of mpcvr_deint_pass, and a plane as mpcvr_plan_deint_planes describes it
+DEINT_ADAPTIVE_EXT, DEINT_ADAPTIVE_NOCHECK_EXT = 0, 1
+FIELD_ORDER_TFF, FIELD_ORDER_BFF = 1, 2
+
+
+class DeintPlane(C.Structure):
+    _fields_ = [("offset", C.c_size_t), ("pitch", C.c_int32), ("comps", C.c_int32), ("lines", C.c_int32), ("bytes", C.c_int32),
+                ("cs", C.c_int32), ("mask", C.c_int32)]
+
+
 class MpcvrError(RuntimeError):
     def __init__(self, hr, msg):
         super().__init__(f"HRESULT 0x{hr & 0xffffffff:08X}: {msg}")
@@ -196,6 +206,7 @@ EXPORTS = [
     "mpcvr_light_level_from_histogram", "mpcvr_histogram_percentile",
     "mpcvr_plan_tensor_value", "mpcvr_tensor_pass", "mpcvr_render_tensor", "mpcvr_plan_batch_tensor", "mpcvr_process_batch_tensor",
     "mpcvr_plan_sample_code", "mpcvr_sample_pass", "mpcvr_copy_sample_tensor", "mpcvr_plan_batch_from_tensors", "mpcvr_process_batch_from_tensors",
+    "mpcvr_plan_deint_planes", "mpcvr_deint_plane_host", "mpcvr_deint_pass", "mpcvr_copy_sample_fields", "mpcvr_plan_batch_deint", "mpcvr_process_batch_deint",
 ]
 
 _lib = None
@@ -312,6 +323,12 @@ def load_library():
         "mpcvr_copy_sample_tensor": [vp, vp, P(TensorDesc)],
         "mpcvr_plan_batch_from_tensors": [i32, i32, i32, C.c_size_t, P(C.c_size_t), P(i32), P(i32)],
         "mpcvr_process_batch_from_tensors": [vp, i32, P(vp), P(TensorDesc), P(vp), i32],
+        "mpcvr_plan_deint_planes": [i32, i32, i32, i32, P(i32), P(DeintPlane)],
+        "mpcvr_deint_plane_host": [vp, vp, vp, C.c_int64, i32, i32, i32, i32, i32, i32, i32, i32, vp, C.c_int64],
+        "mpcvr_deint_pass": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp],
+        "mpcvr_copy_sample_fields": [vp, vp, vp, vp, i32, i32, i32],
+        "mpcvr_plan_batch_deint": [i32, i32, i32, C.c_size_t, P(C.c_size_t), P(i32), P(i32)],
+        "mpcvr_process_batch_deint": [vp, i32, P(vp), i32, i32, i32, P(vp), i32],
     }
     for name, args in sig.items():
         if lib_path != LIB_PATH and not hasattr(L, name):
@@ -543,6 +560,44 @@ def plan_batch_from_tensors(pitch, h, n, budget_bytes=0):
     hr = load_library().mpcvr_plan_batch_from_tensors(int(pitch), int(h), int(n), int(budget_bytes), C.byref(stride), C.byref(fpc), C.byref(chunks))
     if hr:
         raise MpcvrError(hr, "mpcvr_plan_batch_from_tensors")
+    return dict(frame_stride=stride.value, frames_per_chunk=fpc.value, chunks=chunks.value)
+
+
+def plan_deint_planes(cformat, w, h, pitch=0):
+    """(extension) The planes of a sample as the deinterlacing pass walks them (include/mpcvr.h: mpcvr_plan_deint_planes): a list of
+    dict(offset, pitch, comps, lines, bytes, cs, mask).  No GPU needed."""
+    n, out = C.c_int32(), (DeintPlane * 3)()
+    hr = load_library().mpcvr_plan_deint_planes(int(cformat), int(w), int(h), int(pitch), C.byref(n), out)
+    if hr:
+        raise MpcvrError(hr, "mpcvr_plan_deint_planes")
+    return [dict(offset=p.offset, pitch=p.pitch, comps=p.comps, lines=p.lines, bytes=p.bytes, cs=p.cs, mask=p.mask) for p in out[:n.value]]
+
+
+def deint_plane_host(prev, cur, nxt, src_pitch, comps, lines, nbytes, cs, mask, keep, first, mode, dst, dst_pitch):
+    """(extension) One plane in HOST memory by the definition of mpcvr_deint_pass (include/mpcvr.h: mpcvr_deint_plane_host): prev, cur, nxt
+    and dst are numpy arrays or addresses, rows src_pitch / dst_pitch bytes apart.  No GPU needed."""
+    hr = load_library().mpcvr_deint_plane_host(C.c_void_p(_ptr(prev)), C.c_void_p(_ptr(cur)), C.c_void_p(_ptr(nxt)), int(src_pitch), int(comps), int(lines),
+                                               int(nbytes), int(cs), int(mask), int(keep), int(first), int(mode), C.c_void_p(_ptr(dst)), int(dst_pitch))
+    if hr:
+        raise MpcvrError(hr, "mpcvr_deint_plane_host")
+
+
+def deint_pass(prev, cur, nxt, cformat, w, h, pitch, keep, first, mode, dst, dst_pitch, stream=None):
+    """(extension) Motion-adaptive deinterlacing of the device sample `cur` between `prev` and `nxt` into the sample at `dst`, showing the
+    field of parity `keep` (include/mpcvr.h: mpcvr_deint_pass).  Complete in stream order."""
+    hr = load_library().mpcvr_deint_pass(C.c_void_p(_ptr(prev)), C.c_void_p(_ptr(cur)), C.c_void_p(_ptr(nxt)), int(cformat), int(w), int(h), int(pitch),
+                                         int(keep), int(first), int(mode), C.c_void_p(_ptr(dst)), int(dst_pitch), C.c_void_p(stream) if stream else None)
+    if hr:
+        raise MpcvrError(hr, "mpcvr_deint_pass")
+
+
+def plan_batch_deint(pitch, lines, n_out, budget_bytes=0):
+    """(extension) The integers of ProcessBatchDeint's sample surface (include/mpcvr.h: mpcvr_plan_batch_deint): dict(frame_stride,
+    frames_per_chunk, chunks) for n_out samples of pitch * lines bytes under a budget of bytes (0: the default).  No GPU needed."""
+    fpc, chunks, stride = C.c_int32(), C.c_int32(), C.c_size_t()
+    hr = load_library().mpcvr_plan_batch_deint(int(pitch), int(lines), int(n_out), int(budget_bytes), C.byref(stride), C.byref(fpc), C.byref(chunks))
+    if hr:
+        raise MpcvrError(hr, "mpcvr_plan_batch_deint")
     return dict(frame_stride=stride.value, frames_per_chunk=fpc.value, chunks=chunks.value)
 
 
@@ -962,6 +1017,25 @@ class VideoProcessor:
         self._keep = keep
         return self._check(self._L.mpcvr_process_batch_from_tensors(self._ctx, n, keep[0], C.byref(d), keep[1], int(rt_pitch)))
 
+    def CopySampleFields(self, prev, cur, nxt, field_order, field, mode=DEINT_ADAPTIVE_EXT):
+        """(extension) Field `field` (0 the first, 1 the second) of the interlaced device sample `cur`, deinterlaced between `prev` and
+        `nxt` (pass `cur` again at a stream's ends), as the current sample (mpcvr_copy_sample_fields); field_order FIELD_ORDER_TFF / BFF.
+        The pass runs on the context stream; the samples are free in that stream's order behind the call."""
+        self._keep = (prev, cur, nxt)
+        return self._check(self._L.mpcvr_copy_sample_fields(self._ctx, C.c_void_p(_ptr(prev)), C.c_void_p(_ptr(cur)), C.c_void_p(_ptr(nxt)),
+                                                            int(field_order), int(field), int(mode)))
+
+    def ProcessBatchDeint(self, frames, dsts, rt_pitch, field_order, fields_per_frame=2, mode=DEINT_ADAPTIVE_EXT):
+        """(extension) ProcessBatch at field rate (mpcvr_process_batch_deint): `frames` are n + 2 interlaced device samples, the n interior
+        ones deinterlaced with their neighbours; dsts the n * fields_per_frame render targets, target (i - 1) * fields_per_frame + f showing
+        field f of frame i.  One pass per chunk in front of the chunk's batch; GetLastBatchInfo adds deint_chunks."""
+        n = len(frames) - 2
+        if n < 1 or len(dsts) != n * fields_per_frame:
+            raise ValueError("n + 2 samples for n * fields_per_frame render targets, n at least one")
+        keep = ((C.c_void_p * (n + 2))(*[_ptr(x) for x in frames]), (C.c_void_p * len(dsts))(*[_ptr(x) for x in dsts]), (frames, dsts))
+        self._keep = keep
+        return self._check(self._L.mpcvr_process_batch_deint(self._ctx, n, keep[0], int(field_order), int(fields_per_frame), int(mode), keep[1], int(rt_pitch)))
+
     def ProcessBatch(self, srcs, dsts, rt_pitch):
         if isinstance(srcs, PreparedBatch):          # pointer arrays built once (PrepareBatch): nothing per call but the C call
             return self._check(self._L.mpcvr_process_batch(self._ctx, srcs.n, srcs.sa, srcs.da, rt_pitch))
@@ -1069,6 +1143,8 @@ class VideoProcessor:
             out.update(tensor_chunks=int(d["tensor_chunks"]), tensor_lanes=[int(x) for x in d["tensor_lanes"].split(",") if x])
         if "sample_chunks" in d:     # (only behind a ProcessBatchFromTensors)
             out.update(sample_chunks=int(d["sample_chunks"]))
+        if "deint_chunks" in d:      # (only behind a ProcessBatchDeint)
+            out.update(deint_chunks=int(d["deint_chunks"]))
         return out
 
     def GetLastProcessMs(self):

@@ -48,6 +48,7 @@ SOURCES = [
     ("vp_measure.hip", []),
     ("vp_tensor.hip", []),
     ("vp_tensor_in.hip", []),
+    ("vp_deint.hip", []),
     ("vp_probe.hip", []),
 ]
 

@@ -2287,6 +2287,209 @@ HRESULT CHipVideoProcessor::ProcessBatchFromTensors(int n, const void *const *te
     return hr;
 }
 
+// ------------------------------------------------------------------------------------------------
+// EXTENSION — motion-adaptive deinterlacing at field rate (include/mpcvr.h: mpcvr_deint_pass, mpcvr_copy_sample_fields,
+// mpcvr_process_batch_deint; kernel: vp_deint.hip).  No reference line: the reference hands deinterlacing to the fixed-function video processor.
+// ------------------------------------------------------------------------------------------------
+// What the k_deint launches of one sample are given, but for their pointers: one DeintParams per distinct (bytes, cs) among the planes (cs[g]
+// says which), srcvec / dstvec as far as plane offsets and pitches decide them — the caller takes them back where a pointer is off the grid
+static int DeintGroupParams(const DeintPlane *sp, const DeintPlane *dp, int np, DeintParams out[2], int cs[2])
+{
+    int n = 0;
+    for (int want = 1; want <= 2; want++) {
+        DeintParams p{};
+        p.srcvec = p.dstvec = 1;
+        for (int i = 0; i < np; i++) {
+            if (sp[i].cs != want) continue;
+            const size_t grid = (size_t)(kDeintLaneSteps * want * sp[i].bytes) - 1;
+            p.plane[p.n_planes++] = DeintLaunchPlane{(int64_t)sp[i].offset, (int64_t)dp[i].offset, sp[i].pitch, dp[i].pitch, sp[i].comps / want, sp[i].lines};
+            p.srcvec &= ((sp[i].offset | (size_t)sp[i].pitch) & grid) == 0;
+            p.dstvec &= ((dp[i].offset | (size_t)dp[i].pitch) & grid) == 0;
+            p.mask = sp[i].mask;
+        }
+        if (p.n_planes) { out[n] = p; cs[n++] = want; }
+    }
+    return n;
+}
+
+HRESULT DeintSurface(const void *prev, const void *cur, const void *next, int cformat, int w, int h, int pitch, int keep, int first, int mode,
+                     void *dst, int dstPitch, hipStream_t stream, bool checkOnly, const char **why, int *launches)
+{
+    const char *dummy;
+    if (!why) why = &dummy;
+    if (launches) *launches = 0;
+    if (!prev || !cur || !next || (!dst && !checkOnly)) { *why = "null sample"; return MPCVR_E_POINTER; }      // (checkOnly: a destination still to be allocated)
+    DeintPlane sp[kDeintMaxPlanes], dp[kDeintMaxPlanes];
+    int np = 0, npd = 0;
+    if (!PlanDeintPlanes(cformat, w, h, pitch, &np, sp) || !PlanDeintPlanes(cformat, w, h, dstPitch, &npd, dp)) {
+        *why = "a planar or bi-planar format, a size and pitches by the rules of mpcvr_set_input, at least 2 lines per plane"; return MPCVR_E_INVALIDARG;
+    }
+    if ((keep != 0 && keep != 1) || (first != 0 && first != 1) || (mode != DI_ADAPTIVE && mode != DI_ADAPTIVE_NOCHECK)) {
+        *why = "keep and first are 0 or 1, mode MPCVR_DEINT_ADAPTIVE_EXT or MPCVR_DEINT_ADAPTIVE_NOCHECK_EXT"; return MPCVR_E_INVALIDARG;
+    }
+    const int bytes = sp[0].bytes;
+    if (((uintptr_t)prev | (uintptr_t)cur | (uintptr_t)next | (uintptr_t)dst) & (uintptr_t)(bytes - 1)) {
+        *why = "samples must be multiples of the component size"; return MPCVR_E_INVALIDARG;
+    }
+    // the sources are only read: they may share bytes with each other, not with a plane of the destination
+    if (dst) {
+        const void *const srcs[3] = {prev, cur, next};
+        for (int a = 0; a < np; a++) {
+            const RtSpan d = RowsSpan((const uint8_t *)dst + dp[a].offset, (size_t)dp[a].pitch, dp[a].lines, (size_t)dp[a].comps * bytes);
+            for (int s = 0; s < 3; s++)
+                for (int b = 0; b < np; b++)
+                    if (d.Overlaps(RowsSpan((const uint8_t *)srcs[s] + sp[b].offset, (size_t)sp[b].pitch, sp[b].lines, (size_t)sp[b].comps * bytes))) {
+                        *why = "a plane of the destination overlaps a plane of a source"; return MPCVR_E_INVALIDARG;
+                    }
+            for (int b = a + 1; b < np; b++)
+                if (d.Overlaps(RowsSpan((const uint8_t *)dst + dp[b].offset, (size_t)dp[b].pitch, dp[b].lines, (size_t)dp[b].comps * bytes))) {
+                    *why = "two planes of the destination overlap"; return MPCVR_E_INVALIDARG;
+                }
+        }
+    }
+    if (checkOnly) return MPCVR_S_OK;
+    DeintParams g[2];
+    int cs[2];
+    const int ng = DeintGroupParams(sp, dp, np, g, cs);
+    for (int i = 0; i < ng; i++) {
+        DeintParams &p = g[i];
+        const uintptr_t grid = (uintptr_t)(kDeintLaneSteps * cs[i] * bytes) - 1;
+        p.one = DeintFrame{(const uint8_t *)prev, (const uint8_t *)cur, (const uint8_t *)next, (uint8_t *)dst, keep, first};
+        p.srcvec &= (((uintptr_t)prev | (uintptr_t)cur | (uintptr_t)next) & grid) == 0;
+        p.dstvec &= ((uintptr_t)dst & grid) == 0;
+        if (LaunchDeint(p, bytes, cs[i], mode, stream) != hipSuccess) { *why = "k_deint launch failed"; return MPCVR_E_FAIL; }
+        if (launches) ++*launches;
+    }
+    return MPCVR_S_OK;
+}
+
+// keep and first of field `field` (0 the first, 1 the second) of a frame of `fieldOrder` (1 top field first, 2 bottom field first)
+static void FieldParity(int fieldOrder, int field, int *keep, int *first)
+{
+    *first = field == 0;
+    *keep = fieldOrder == 1 ? field : 1 - field;
+}
+
+// CopySampleTensor with k_deint as the pass: the same slot ring, device buffers and events, on the context stream.
+HRESULT CHipVideoProcessor::CopySampleFields(const void *prev, const void *cur, const void *next, int fieldOrder, int field, int mode)
+{
+    if (!m_bInit || !m_srcParams) return Fail(MPCVR_E_NOT_VALID_STATE, "InitMediaType has not been called");
+    if (!prev || !cur || !next) return Fail(MPCVR_E_POINTER, "null sample");
+    if ((fieldOrder != 1 && fieldOrder != 2) || (field != 0 && field != 1)) return Fail(MPCVR_E_INVALIDARG, "field_order is 1 or 2, field 0 or 1");
+    int keep, first;
+    FieldParity(fieldOrder, field, &keep, &first);
+    // (every refusal comes before anything is touched: the current sample, its upload slot and the stream it was last drawn on stay as they are)
+    const char *why = "";
+    const int cf = m_srcParams->cformat;
+    if (HRESULT bad = DeintSurface(prev, cur, next, cf, m_srcWidth, m_srcHeight, m_srcPitch, keep, first, mode, nullptr, m_srcPitch, nullptr, true, &why)) return Fail(bad, why);
+    (void)hipSetDevice(m_device);
+    const size_t bytes = (size_t)m_srcPitch * m_srcLines;
+    HRESULT hr;
+    MarkConsumed();                                  // the previous sample is done with as far as the host is concerned
+    m_curSlot = -1;
+    m_lastRun = nullptr;
+    m_curSample = nullptr;                           // (a failure below leaves no sample rather than a slot half written)
+    const int si = m_upNext;
+    m_upNext = (m_upNext + 1) % kUploadSlots;
+    UploadSlot &u = m_up[si];
+    if (!u.uploaded) {
+        if ((hr = CheckHip(hipEventCreateWithFlags(&u.uploaded, hipEventDisableTiming), "upload event"))) return hr;
+        if ((hr = CheckHip(hipEventCreateWithFlags(&u.consumed, hipEventDisableTiming), "consume event"))) return hr;
+    }
+    // the slot's device buffer is free once the work that last used it has completed
+    if (u.inFlight && (hr = CheckHip(hipEventSynchronize(u.consumedRecorded ? u.consumed : u.uploaded), "upload slot wait"))) return hr;
+    if ((hr = CheckHip(u.dev.CheckCreate(bytes), "upload buffer"))) return hr;
+    int launched = 0;
+    // (the slot's buffer may be one a caller was handed as a sample address long ago: the overlap rule is asked again with the real destination)
+    if ((hr = DeintSurface(prev, cur, next, cf, m_srcWidth, m_srcHeight, m_srcPitch, keep, first, mode, u.dev.ptr, m_srcPitch, m_stream, false, &why, &launched))) return Fail(hr, why);
+    m_launches += launched;
+    if ((hr = CheckHip(hipEventRecord(u.uploaded, m_stream), "upload event"))) return hr;
+    m_lanes.NoteStreamWork();
+    u.inFlight = true; u.consumedRecorded = false;
+    m_curSlot = si;
+    return PrepareSample((const uint8_t *)u.dev.ptr, &m_curSample);
+}
+
+// A batch at field rate (include/mpcvr.h: mpcvr_process_batch_deint).  Everything about the arguments is answered first; then the output
+// frames are cut into chunks of PlanBatchDeint's size, and each chunk is the pass with a frame dimension (one launch per distinct (bytes,
+// cs) among the planes) into the context-owned sample surface and the batch machinery behind it, both on the context stream, as in
+// ProcessBatchFromTensors.
+HRESULT CHipVideoProcessor::ProcessBatchDeint(int n, const void *const *frames, int fieldOrder, int fieldsPerFrame, int mode, void *const *dsts, int rtPitch)
+{
+    const bool fpfOk = fieldsPerFrame == 1 || fieldsPerFrame == 2;
+    const int nOut = n > 0 && n <= (1 << 24) && fpfOk ? n * fieldsPerFrame : 0;
+    const BatchRecord record(*this, nOut);
+    if (!m_bInit || !m_srcParams) return Fail(MPCVR_E_NOT_VALID_STATE, "InitMediaType has not been called");
+    if (n <= 0 || n > (1 << 24)) return Fail(MPCVR_E_INVALIDARG, "empty batch");
+    if (!frames || !dsts) return Fail(MPCVR_E_POINTER, "null array of samples or frames");
+    if (!fpfOk || (fieldOrder != 1 && fieldOrder != 2) || (mode != DI_ADAPTIVE && mode != DI_ADAPTIVE_NOCHECK))
+        return Fail(MPCVR_E_INVALIDARG, "fields_per_frame is 1 or 2, field_order 1 or 2, mode MPCVR_DEINT_ADAPTIVE_EXT or MPCVR_DEINT_ADAPTIVE_NOCHECK_EXT");
+    for (int i = 0; i < n + 2; i++)
+        if (!frames[i]) return Fail(MPCVR_E_POINTER, "null sample in batch");
+    for (int k = 0; k < nOut; k++)
+        if (!dsts[k]) return Fail(MPCVR_E_POINTER, "null frame in batch");
+    DeintPlane sp[kDeintMaxPlanes];
+    int np = 0;
+    if (!PlanDeintPlanes(m_srcParams->cformat, m_srcWidth, m_srcHeight, m_srcPitch, &np, sp))
+        return Fail(MPCVR_E_INVALIDARG, "the input must be a planar or bi-planar format of at least 2 lines per plane");
+    const int bytes = sp[0].bytes;
+    std::vector<const void *> curs((size_t)nOut);
+    for (int k = 0; k < nOut; k++) curs[k] = frames[1 + k / fieldsPerFrame];
+    if (HRESULT bad = CheckBatchArgs(nOut, curs.data(), dsts, rtPitch)) return bad;
+    uintptr_t bits = 0;
+    for (int i = 0; i < n + 2; i++) bits |= (uintptr_t)frames[i];
+    if (bits & (uintptr_t)(bytes - 1)) return Fail(MPCVR_E_INVALIDARG, "samples must be multiples of the component size");
+    BatchDeintLayout lay;
+    if (!PlanBatchDeint(m_srcPitch, m_srcLines, nOut, m_yuvBudget, &lay)) return Fail(MPCVR_E_INVALIDARG, "sample layout");
+
+    (void)hipSetDevice(m_device);
+    if (HRESULT bad = m_planDirty ? UpdatePlan() : MPCVR_S_OK) return bad;
+    const int most = lay.framesPerChunk;
+    HRESULT hr;
+    if ((hr = CheckHip(m_sampleSurf.CheckCreate(lay.frameStride * (size_t)most), "batch sample surface"))) return hr;
+    std::vector<const void *> samples((size_t)most);
+    for (int i = 0; i < most; i++) samples[i] = (const uint8_t *)m_sampleSurf.ptr + (size_t)i * lay.frameStride;
+    // (dstvec holds for every chunk: every frame of the surface starts on 256 bytes; srcvec only if every sample of the call allows it)
+    DeintParams g[2];
+    int cs[2];
+    const int ng = DeintGroupParams(sp, sp, np, g, cs);
+    for (int i = 0; i < ng; i++) g[i].srcvec &= (bits & ((uintptr_t)(kDeintLaneSteps * cs[i] * bytes) - 1)) == 0;
+    int chunks = 0;
+    for (int at = 0; at < nOut && !hr; at += most, chunks++) {
+        const int m = std::min(most, nOut - at);
+        BatchRun run{m, samples.data(), dsts + at, rtPitch};
+        run.on = RunOn{m_stream};
+        OrderOnContextStream();          // behind every frame and batch the lanes hold (the last chunk's readers of the surface are on this stream already)
+        {
+            // the frames' table through the frame tables' ring; the lease ends behind the pass
+            SlotLease table;
+            DeintFrame *fr;
+            if ((hr = m_tableRing.Next(sizeof(DeintFrame) * m, sizeof(DeintFrame) * 64, (void **)&fr))) break;
+            for (int i = 0; i < m; i++) {
+                const int k = at + i, f = 1 + k / fieldsPerFrame;
+                int keep, first;
+                FieldParity(fieldOrder, k % fieldsPerFrame, &keep, &first);
+                fr[i] = DeintFrame{(const uint8_t *)frames[f - 1], (const uint8_t *)frames[f], (const uint8_t *)frames[f + 1],
+                                   (uint8_t *)const_cast<void *>(samples[i]), keep, first};
+            }
+            if ((hr = m_tableRing.Send(sizeof(DeintFrame) * m, m_stream, "deint table", &table))) break;
+            for (int i = 0; i < ng && !hr; i++) {
+                DeintParams p = g[i];
+                p.frames = (const DeintFrame *)table.dev;
+                hr = CheckHip(LaunchDeint(p, bytes, cs[i], mode, m_stream, m), "k_deint");
+            }
+            if (hr) break;
+        }
+        if (m_plan.errdiff) hr = ProcessBatchErrDiff(run);
+        else {
+            BatchRoutePlan rp = ClassifyBatch(run);
+            hr = RunBatchRoute(rp, run);
+        }
+    }
+    m_yuvLastInfo = ";deint_chunks=" + std::to_string(chunks);
+    return hr;
+}
+
 HRESULT CHipVideoProcessor::GetBackBuffer(void **ptr, int *pitch, int *w, int *h)
 {
     if (!m_BackBuffer.ptr) return Fail(MPCVR_E_NOT_VALID_STATE, "Render has not been called");

@@ -15,6 +15,7 @@
 #include "vp_measure.h"
 #include "vp_tensor.h"
 #include "vp_tensor_in.h"
+#include "vp_deint.h"
 #include "vp_launch.h"
 #include "vp_params.h"
 #include "vp_plan.h"
@@ -65,6 +66,12 @@ HRESULT TensorSurface(const void *src, int srcPitch, int srcFmt, int w, int h, c
 HRESULT SampleSurface(const void *tensor, const mpcvr_tensor_desc *desc, int w, int h, int cformat, void *sample, int pitch, hipStream_t stream,
                       bool checkOnly, const char **why = nullptr);
 
+// EXTENSION (mpcvr_deint_pass, include/mpcvr.h): checks every argument, then — unless checkOnly — launches k_deint on `stream`, once per
+// distinct (bytes, cs) among the planes; *launches (optional) is told how many.  MPCVR_E_POINTER / MPCVR_E_INVALIDARG with nothing launched
+// or written.  checkOnly takes dst = nullptr for a sample that is still to be allocated (it cannot overlap a source)
+HRESULT DeintSurface(const void *prev, const void *cur, const void *next, int cformat, int w, int h, int pitch, int keep, int first, int mode,
+                     void *dst, int dstPitch, hipStream_t stream, bool checkOnly, const char **why = nullptr, int *launches = nullptr);
+
 class CHipVideoProcessor {
 public:
     CHipVideoProcessor();
@@ -114,6 +121,11 @@ public:
     // context-owned sample surface, one pass per chunk in front of the chunk's batch, everything on the context stream
     HRESULT CopySampleTensor(const void *tensor, const mpcvr_tensor_desc *desc);
     HRESULT ProcessBatchFromTensors(int n, const void *const *tensors, const mpcvr_tensor_desc *desc, void *const *dsts, int rtPitch);
+    // EXTENSION (mpcvr_copy_sample_fields / mpcvr_process_batch_deint): one field of an interlaced sample, deinterlaced by k_deint (vp_deint.h)
+    // into an upload slot in place of the host-to-device copy, as the current sample; a batch at field rate through the context-owned
+    // sample surface, the pass (its frame dimension) in front of each chunk's batch, everything on the context stream
+    HRESULT CopySampleFields(const void *prev, const void *cur, const void *next, int fieldOrder, int field, int mode);
+    HRESULT ProcessBatchDeint(int n, const void *const *frames, int fieldOrder, int fieldsPerFrame, int mode, void *const *dsts, int rtPitch);
     HRESULT SetBatchYuvBudget(size_t bytes) { m_yuvBudget = bytes; return MPCVR_S_OK; }
     std::string GetLastBatchInfo() const;
     HRESULT ProcessBatchDovi(int n, const void *const *srcs, void *const *dsts, int rtPitch, const mpcvr_dovi_metadata *rpus);
@@ -451,7 +463,7 @@ private:
     YuvSurface m_yuvSurf[FrameLanes::kFrameLanes];
     size_t m_yuvBudget = 0;            // SetBatchYuvBudget; 0: kBatchYuvDefaultBudget
     std::string m_yuvLastInfo;         // ";yuv_chunks=..;yuv_lanes=.." (";tensor_chunks=..;tensor_lanes=..") of the last batch call, if it was a ProcessBatchYuv (ProcessBatchTensor)
-    DevBuffer m_sampleSurf;            // ProcessBatchFromTensors: the samples of one chunk side by side (PlanBatchSamples), written and read in stream order on the context stream
+    DevBuffer m_sampleSurf;            // ProcessBatchFromTensors / ProcessBatchDeint: the samples of one chunk side by side (PlanBatchSamples), written and read in stream order on the context stream
     // the chunk loop of both: surfaces, lanes and order; writesOf(at, m): what the chunk writes for the caller, pass(run, at): its pass
     template <class WritesOf, class Pass>
     HRESULT RunSurfaceChunks(int n, const void *const *srcs, const BatchYuvLayout &lay, const char *tag, WritesOf writesOf, Pass pass);

@@ -302,6 +302,63 @@ int32_t mpcvr_process_batch_from_tensors(mpcvr_ctx *ctx, int32_t n, const void *
     return ctx->vp.ProcessBatchFromTensors(n, tensors, desc, dsts, dst_pitch);
 }
 
+// EXTENSION: motion-adaptive deinterlacing at field rate (include/mpcvr.h; k_deint vp_deint.hip, the arithmetic vp_deint_core.h, DeintSurface and
+// CHipVideoProcessor::CopySampleFields / ProcessBatchDeint hip_video_processor.cpp, PlanDeintPlanes / PlanBatchDeint vp_plan.cpp)
+static_assert(MPCVR_DEINT_ADAPTIVE_EXT == mpcvr::DI_ADAPTIVE && MPCVR_DEINT_ADAPTIVE_NOCHECK_EXT == mpcvr::DI_ADAPTIVE_NOCHECK, "the header and vp_deint_core.h name one set of modes");
+int32_t mpcvr_plan_deint_planes(int32_t cformat, int32_t w, int32_t h, int32_t pitch, int32_t *planes, mpcvr_deint_plane out[3])
+{
+    if (!planes || !out) return MPCVR_E_POINTER;
+    mpcvr::DeintPlane pl[mpcvr::kDeintMaxPlanes];
+    int n = 0;
+    if (!mpcvr::PlanDeintPlanes(cformat, w, h, pitch, &n, pl)) return MPCVR_E_INVALIDARG;
+    for (int i = 0; i < n; i++) out[i] = mpcvr_deint_plane{pl[i].offset, pl[i].pitch, pl[i].comps, pl[i].lines, pl[i].bytes, pl[i].cs, pl[i].mask};
+    *planes = n;
+    return MPCVR_S_OK;
+}
+
+int32_t mpcvr_deint_plane_host(const void *prev, const void *cur, const void *next, int64_t src_pitch, int32_t comps, int32_t lines, int32_t bytes, int32_t cs,
+                               int32_t mask, int32_t keep, int32_t first, int32_t mode, void *dst, int64_t dst_pitch)
+{
+    if (!prev || !cur || !next || !dst) return MPCVR_E_POINTER;
+    if ((bytes != 1 && bytes != 2) || (cs != 1 && cs != 2) || comps < cs || comps % cs || lines < 2 || (keep != 0 && keep != 1) || (first != 0 && first != 1) ||
+        (mode != mpcvr::DI_ADAPTIVE && mode != mpcvr::DI_ADAPTIVE_NOCHECK) || mask < 0 || mask > (bytes == 1 ? 0xff : 0xffff) ||
+        src_pitch < (int64_t)comps * bytes || dst_pitch < (int64_t)comps * bytes || ((src_pitch | dst_pitch) & (bytes - 1)) ||
+        (((uintptr_t)prev | (uintptr_t)cur | (uintptr_t)next | (uintptr_t)dst) & (uintptr_t)(bytes - 1)))
+        return MPCVR_E_INVALIDARG;
+    mpcvr::DeintPlaneHost((const uint8_t *)prev, (const uint8_t *)cur, (const uint8_t *)next, src_pitch, comps, lines, bytes, cs, mask, keep, first, mode,
+                          (uint8_t *)dst, dst_pitch);
+    return MPCVR_S_OK;
+}
+
+int32_t mpcvr_deint_pass(const void *prev, const void *cur, const void *next, int32_t cformat, int32_t w, int32_t h, int32_t pitch,
+                         int32_t keep, int32_t first, int32_t mode, void *dst, int32_t dst_pitch, void *stream)
+{
+    return mpcvr::DeintSurface(prev, cur, next, cformat, w, h, pitch, keep, first, mode, dst, dst_pitch, (hipStream_t)stream, false);
+}
+
+int32_t mpcvr_copy_sample_fields(mpcvr_ctx *ctx, const void *prev, const void *cur, const void *next, int32_t field_order, int32_t field, int32_t mode)
+{
+    CTX_OR_FAIL();
+    return ctx->vp.CopySampleFields(prev, cur, next, field_order, field, mode);
+}
+
+int32_t mpcvr_plan_batch_deint(int32_t pitch, int32_t lines, int32_t n_out, size_t budget_bytes, size_t *frame_stride, int32_t *frames_per_chunk, int32_t *chunks)
+{
+    mpcvr::BatchDeintLayout lay;
+    if (!mpcvr::PlanBatchDeint(pitch, lines, n_out, budget_bytes, &lay)) return MPCVR_E_INVALIDARG;
+    if (frame_stride) *frame_stride = lay.frameStride;
+    if (frames_per_chunk) *frames_per_chunk = lay.framesPerChunk;
+    if (chunks) *chunks = lay.chunks;
+    return MPCVR_S_OK;
+}
+
+int32_t mpcvr_process_batch_deint(mpcvr_ctx *ctx, int32_t n, const void *const *frames, int32_t field_order, int32_t fields_per_frame, int32_t mode,
+                                  void *const *dsts, int32_t dst_pitch)
+{
+    CTX_OR_FAIL();
+    return ctx->vp.ProcessBatchDeint(n, frames, field_order, fields_per_frame, mode, dsts, dst_pitch);
+}
+
 int32_t mpcvr_get_param_blob(mpcvr_ctx *ctx, void *buf, size_t *size) { CTX_OR_FAIL(); return ctx->vp.GetParamBlob(buf, size); }
 int32_t mpcvr_get_fused_tables(mpcvr_ctx *ctx, void *buf, size_t *size) { CTX_OR_FAIL(); return ctx->vp.GetFusedTables(buf, size); }
 int32_t mpcvr_set_param_blob(mpcvr_ctx *ctx, const void *buf, size_t size) { CTX_OR_FAIL(); return ctx->vp.SetParamBlob(buf, size); }

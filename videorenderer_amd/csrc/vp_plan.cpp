@@ -11,6 +11,7 @@
 #include "vp_measure.h"
 #include "vp_tensor.h"
 #include "vp_tensor_in.h"
+#include "vp_deint.h"
 #include "vp_crmath.h"      // the shaders' sin / cos as defined functions (the weights the resize shaders compute per pixel are computed here, once)
 
 namespace mpcvr {
@@ -337,6 +338,48 @@ bool PlanBatchSamples(int pitch, int h, int n, size_t budget, BatchSampleLayout 
     out->frameStride = ((size_t)3 * (size_t)pitch * (size_t)h + 255) & ~(size_t)255;
     out->framesPerChunk = FramesPerChunk(n, out->frameStride, budget);
     out->chunks = (n + out->framesPerChunk - 1) / out->framesPerChunk;
+    return true;
+}
+
+// ------------------------------------------------------------------------------------------------
+// EXTENSION — motion-adaptive deinterlacing (include/mpcvr.h: mpcvr_plan_deint_planes, mpcvr_plan_batch_deint): the planes of a sample as
+// InitMediaType lays it out, and the integers of the batch's sample surface.  No reference line: the reference leaves deinterlacing to
+// the fixed-function video processor.
+// ------------------------------------------------------------------------------------------------
+bool PlanDeintPlanes(int cformat, int w, int h, int pitch, int *planes, DeintPlane out[kDeintMaxPlanes])
+{
+    const FmtConvParams *f = GetFmtConvParams(cformat);
+    if (!f || (f->layout != LAY_PLANAR && f->layout != LAY_GRAY)) return false;          // every packed format
+    // the size and pitch rules of InitMediaType (hip_video_processor.cpp)
+    if (w <= 0 || h <= 0 || w > 16384 || h > 16384) return false;
+    if ((f->div_w == 2 && (w & 1)) || (f->div_h == 2 && (h & 1))) return false;
+    if (pitch == 0) pitch = DefaultPitch(*f, w);
+    if (pitch < w * f->Packsize) return false;                                             // (a negative pitch is defined for the RGB formats only)
+    if (f->bytes == 2 && (pitch & 1)) return false;
+    if (f->planes == 3 && f->bytes == 2 && ((pitch / f->div_w) & 1)) return false;
+    const int mask = f->bytes == 1 ? 0xff : (f->CDepth == 10 && f->shift == 6) ? 0x3ff : 0xffff;      // planar 10-bit words: bits 0 .. 9, as the reader takes them
+    const int ch = h / f->div_h;
+    if (h < 2 || (f->planes > 1 && ch < 2)) return false;
+    int n = 0;
+    out[n++] = DeintPlane{0, pitch, w, h, f->bytes, 1, mask};
+    const size_t luma = (size_t)pitch * (size_t)h;
+    if (f->planes == 2) out[n++] = DeintPlane{luma, pitch, w / f->div_w * 2, ch, f->bytes, 2, mask};      // U,V pairs at the luma pitch
+    if (f->planes == 3) {
+        const int cp = pitch / f->div_w;
+        out[n++] = DeintPlane{luma, cp, w / f->div_w, ch, f->bytes, 1, mask};
+        out[n++] = DeintPlane{luma + (size_t)cp * (size_t)ch, cp, w / f->div_w, ch, f->bytes, 1, mask};
+    }
+    *planes = n;
+    return true;
+}
+
+bool PlanBatchDeint(int pitch, int lines, int nOut, size_t budget, BatchDeintLayout *out)
+{
+    if (nOut <= 0 || pitch < 1 || lines < 1) return false;
+    if (!budget) budget = kBatchYuvDefaultBudget;
+    out->frameStride = ((size_t)pitch * (size_t)lines + 255) & ~(size_t)255;
+    out->framesPerChunk = FramesPerChunk(nOut, out->frameStride, budget);
+    out->chunks = (nOut + out->framesPerChunk - 1) / out->framesPerChunk;
     return true;
 }
 
