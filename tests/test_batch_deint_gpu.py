@@ -164,3 +164,44 @@ def test_refusals_draw_nothing(mpcvr, torch_cuda):
     torch.cuda.synchronize()
     assert all(torch.equal(a, b) for a, b in zip(dsts, before))
     vp.close()
+
+
+def test_error_diffusion_behind_the_deint_chunks(mpcvr, torch_cuda):
+    """bUseDither = 2: each chunk's samples go through the error-diffusion plan's own chunks and its pass instead of a batch route.  Two
+    interior 16 x 8 P010 frames at field rate (four pictures) into 32 x 16 windows, in one chunk and in two chunks of two; each target
+    equals, byte for byte, the deinterlacing passes followed by mpcvr_process_batch with the same settings."""
+    from videorenderer_amd import api
+    torch = torch_cuda
+    w, h, n, fpf, order, mode, cformat = 16, 8, 2, 2, 1, 0, P010
+    n_out = n * fpf
+    fr = [torch.from_numpy(x).cuda() for x in M.noise_samples(api.plan_deint_planes(cformat, w, h), n + 2, 77)]
+    vp = api.VideoProcessor(api.default_settings(iUpscaling=4, bUseDither=2))
+    vp.InitMediaType(cformat, w, h)
+    vp.SetWindowRect((0, 0, 2 * w, 2 * h))
+    vp.SetVideoRect((0, 0, 2 * w, 2 * h))
+    assert "errdiff" in vp.GetVPInfo()
+    nbytes, pitch = vp.GetFrameBytes()
+    lines = nbytes // pitch
+    samples = [torch.zeros(nbytes, dtype=torch.uint8, device="cuda") for _ in range(n_out)]
+    for k in range(n_out):
+        i = 1 + k // fpf
+        keep, first = M.field_parity(order, k % fpf)
+        api.deint_pass(fr[i - 1], fr[i], fr[i + 1], cformat, w, h, pitch, keep, first, mode, samples[k], pitch, torch.cuda.current_stream().cuda_stream)
+    dsts = targets(torch, n_out, (2 * w, 2 * h))
+    torch.cuda.synchronize()
+    vp.ProcessBatch(samples, dsts, 2 * w * 4)
+    vp.Synchronize()
+    want = [x.cpu().numpy() for x in dsts]
+    assert not np.array_equal(want[0], want[1])
+    stride = api.plan_batch_deint(pitch, lines, n_out, 0)["frame_stride"]
+    for budget, per, chunks in ((0, n_out, 1), (2 * stride + stride // 2, 2, 2)):
+        assert api.plan_batch_deint(pitch, lines, n_out, budget) == dict(frame_stride=stride, frames_per_chunk=per, chunks=chunks)
+        vp.SetBatchYuvBudget(budget)
+        dsts = targets(torch, n_out, (2 * w, 2 * h))
+        torch.cuda.synchronize()
+        vp.ProcessBatchDeint(fr, dsts, 2 * w * 4, order, fpf, mode)
+        vp.Synchronize()
+        assert vp.GetLastBatchInfo()["deint_chunks"] == chunks
+        for k in range(n_out):
+            assert want[k].any() and np.array_equal(dsts[k].cpu().numpy(), want[k]), (budget, k)
+    vp.close()

@@ -160,3 +160,42 @@ def test_refusals_draw_nothing(mpcvr, torch_cuda):
     vp.Synchronize()
     assert all(bool(x.any()) for x in dsts) and vp.GetLastBatchInfo()["sample_chunks"] == 1
     vp.close()
+
+
+def test_error_diffusion_behind_the_sample_chunks(mpcvr, torch_cuda):
+    """bUseDither = 2: each chunk's samples go through the error-diffusion plan's own chunks and its pass instead of a batch route.  Four
+    16 x 8 GBRP16 frames into 32 x 16 windows, in one chunk and in two chunks of two; each target equals, byte for byte, the sample passes
+    followed by mpcvr_process_batch with the same settings."""
+    from videorenderer_amd import api
+    torch = torch_cuda
+    w, h, n, cformat = 16, 8, 4, M.GBRP16
+    scale, bias = K.identity_factors(cformat)
+    a = np.random.default_rng(31).random((n, 3, h, w), dtype=np.float32) * np.float32(1.2) - np.float32(0.1)
+    ts = torch.from_numpy(a).cuda().to(torch.float16)
+    vp = api.VideoProcessor(api.default_settings(iUpscaling=4, bUseDither=2))
+    vp.InitMediaType(cformat, w, h)
+    vp.SetWindowRect((0, 0, 2 * w, 2 * h))
+    vp.SetVideoRect((0, 0, 2 * w, 2 * h))
+    assert "errdiff" in vp.GetVPInfo()
+    nbytes, pitch = vp.GetFrameBytes()
+    samples = [torch.zeros(nbytes, dtype=torch.uint8, device="cuda") for _ in range(n)]
+    for i in range(n):
+        d, _, _ = api._frame_tensor_desc(ts[i], scale, bias, "rgb")
+        api.sample_pass(ts[i], d, w, h, cformat, samples[i], pitch, torch.cuda.current_stream().cuda_stream)
+    new = lambda: [torch.zeros((2 * h, 2 * w, 4), dtype=torch.uint8, device="cuda") for _ in range(n)]
+    dsts = new()
+    vp.ProcessBatch(samples, dsts, 2 * w * 4)
+    vp.Synchronize()
+    want = [x.cpu().numpy() for x in dsts]
+    assert not np.array_equal(want[0], want[1])
+    stride = api.plan_batch_from_tensors(pitch, h, n, 0)["frame_stride"]
+    for budget, per, chunks in ((0, n, 1), (2 * stride + stride // 2, 2, 2)):
+        assert api.plan_batch_from_tensors(pitch, h, n, budget) == dict(frame_stride=stride, frames_per_chunk=per, chunks=chunks)
+        vp.SetBatchYuvBudget(budget)
+        dsts = new()
+        vp.ProcessBatchFromTensors(ts, dsts, 2 * w * 4, scale, bias)
+        vp.Synchronize()
+        assert vp.GetLastBatchInfo()["sample_chunks"] == chunks
+        for i in range(n):
+            assert want[i].any() and np.array_equal(dsts[i].cpu().numpy(), want[i]), (budget, i)
+    vp.close()

@@ -500,3 +500,97 @@ def test_flush_drops_the_sample_and_the_next_host_sample_draws(mpcvr, oracle, to
         vp.Process(dsts[1], ww * 4)
         vp.Synchronize()
         check([d.cpu().numpy() for d in dsts], want, vp.GetVPInfo(), "around Flush")
+
+
+# ---- 9: one slot ring under three kinds of sample ---------------------------------------------------------------------------------------------
+def test_host_tensor_and_field_samples_share_the_slot_ring_gpu_behind(mpcvr, torch_cuda, stall_mats):
+    """mpcvr_copy_sample(MPCVR_MEM_HOST), mpcvr_copy_sample_tensor and mpcvr_copy_sample_fields fill the SAME three upload slots.  Seven
+    samples of a 16 x 8 GBRP8 input (the one format all three take) in the order host, tensor, fields, host, tensor, fields, host — more
+    than two turns of the ring — each drawn into its own 32 x 16 target before the next arrives, the GPU behind the host for the first turn.
+    Expected, element for element: the same sample written into device memory by the caller (the bytes themselves, mpcvr_sample_pass,
+    mpcvr_deint_pass), handed to a FRESH context as MPCVR_MEM_DEVICE and drawn alone.  A refused mpcvr_copy_sample_fields between two of
+    them (field = 2) changes nothing: the next draw shows the sample before it."""
+    from tests import deint_model as DM
+    from tests import tensor_in_model as TM
+    from videorenderer_amd import api
+    torch = torch_cuda
+    L = api.load_library()
+    w, h, cformat, kinds = 16, 8, TM.GBRP8, ("host", "tensor", "fields")
+    ww, wh = 2 * w, 2 * h
+    planes = api.plan_deint_planes(cformat, w, h)
+    nbytes, pitch = DM.sample_size(planes), planes[0]["pitch"]
+    stream = torch.cuda.current_stream().cuda_stream
+    rng = np.random.default_rng(909)
+
+    def context():
+        vp = api.VideoProcessor(api.default_settings(iUpscaling=2), device=0)
+        vp.InitMediaType(cformat, w, h)
+        vp.SetWindowRect((0, 0, ww, wh))
+        vp.SetVideoRect((0, 0, ww, wh))
+        assert vp.GetFrameBytes() == (nbytes, pitch)
+        return vp
+
+    # the seven samples, and each as the bytes a caller would hand over as device memory
+    given, as_device = [], []
+    for k in range(N_FRAMES):
+        kind = kinds[k % 3]
+        dev = torch.zeros(nbytes, dtype=torch.uint8, device="cuda")
+        if kind == "host":
+            data = rng.integers(0, 256, nbytes, dtype=np.uint8)
+            dev.copy_(torch.from_numpy(data))
+            given.append(data)
+        elif kind == "tensor":
+            t = torch.from_numpy(rng.random((3, h, w), dtype=np.float32) * np.float32(1.2) - np.float32(0.1)).cuda().to(torch.float16)
+            d, _, _ = api._frame_tensor_desc(t, (255.0,) * 3, (0.0,) * 3, "rgb")
+            api.sample_pass(t, d, w, h, cformat, dev, pitch, stream)
+            given.append(t)
+        else:
+            s = [torch.from_numpy(x).cuda() for x in DM.noise_samples(planes, 3, 60 + k)]
+            order, field, mode = 1 + k % 2, (k // 3) % 2, k % 2
+            keep, first = DM.field_parity(order, field)
+            api.deint_pass(s[0], s[1], s[2], cformat, w, h, 0, keep, first, mode, dev, 0, stream)
+            given.append((s, order, field, mode))
+        as_device.append(dev)
+    want = []
+    for dev in as_device:
+        ref = context()
+        dst = torch.full((wh, ww, 4), BG, dtype=torch.uint8, device="cuda")
+        ref.CopySample(dev, pitch, mem_kind=api.MEM_DEVICE)
+        ref.Process(dst, ww * 4)
+        ref.Synchronize()
+        want.append((dst.cpu().numpy(), ref.GetVPInfo()))
+        ref.close()
+    for k in range(N_FRAMES):
+        for step in (1, RING):
+            if k + step < N_FRAMES:
+                assert not np.array_equal(want[k][0], want[k + step][0]), f"expected frames {k} and {k + step} are the same picture"
+
+    vp = context()
+    try:
+        vp.GetVPInfo()                      # UpdatePlan synchronizes the context stream: not inside the window
+        dsts = targets(torch, N_FRAMES + 1, ww, wh)
+        again = dsts.pop()
+        ev = gpu_behind(torch, stall_mats)
+        for k in range(N_FRAMES):
+            kind = kinds[k % 3]
+            if kind == "host":
+                vp.CopySample(given[k], pitch, mem_kind=api.MEM_HOST)
+            elif kind == "tensor":
+                vp.CopySampleTensor(given[k])
+            else:
+                s, order, field, mode = given[k]
+                vp.CopySampleFields(s[0], s[1], s[2], order, field, mode)
+            vp.Process(dsts[k], ww * 4)
+            if k == 1:                      # between the tensor sample and the fields sample: refused, the tensor sample stays current
+                s = given[2][0]
+                assert L.mpcvr_copy_sample_fields(vp._ctx, C.c_void_p(s[0].data_ptr()), C.c_void_p(s[1].data_ptr()), C.c_void_p(s[2].data_ptr()), 1, 2, 0) == api.E_INVALIDARG
+                vp.Process(again, ww * 4)
+            if k == RING - 1:
+                still_behind(ev, "host, tensor, fields")        # (the next CopySample waits for sample 0, that is for the stall)
+        vp.Synchronize()
+        info = vp.GetVPInfo()
+    finally:
+        torch.cuda.synchronize()
+        vp.close()
+    check([d.cpu().numpy() for d in dsts], want, info, "host / tensor / fields samples")
+    check([again.cpu().numpy()], [want[1]], info, "the draw behind a refused mpcvr_copy_sample_fields")

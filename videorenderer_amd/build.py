@@ -23,6 +23,7 @@ SOURCES = [
     ("vp_plan_tables.cpp", ["-ffp-contract=off"]),
     ("vp_dovi.cpp", ["-ffp-contract=off", "-std=c++20"]),
     ("hip_video_processor.cpp", []),
+    ("hip_video_processor_ext.cpp", []),
     ("vp_lanes.cpp", []),
     ("mpcvr_capi.cpp", []),
     ("vp_kernels.hip", ["-ffp-contract=off", "-DMPCVR_EXACT_FP"]),

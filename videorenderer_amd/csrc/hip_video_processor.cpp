@@ -1,7 +1,8 @@
 // hip_video_processor.cpp — pass sequencing and resource management of the shader video processor on
 // HIP.  Restates the control flow of CDX11VideoProcessor::{InitMediaType, Configure, CopySample,
 // Process, ConvertColorPass, ResizeShaderPass, FinalPass, GetCurentImage}
-// (Source/DX11VideoProcessor.cpp) without the D3D11 plumbing.
+// (Source/DX11VideoProcessor.cpp) without the D3D11 plumbing; the batch machinery is here as well.  The calls without a
+// counterpart in the reference (the EXTENSIONS of include/mpcvr.h) are in hip_video_processor_ext.cpp.
 #include "hip_video_processor.h"
 
 #include <hip/hip_runtime.h>
@@ -797,16 +798,9 @@ HRESULT CHipVideoProcessor::CopySample(const void *data, int pitch, int memKind)
         return PrepareSample((const uint8_t *)data, &m_curSample);
     }
     if (!m_copyStream && (hr = CheckHip(hipStreamCreateWithFlags(&m_copyStream, hipStreamNonBlocking), "copy stream"))) return hr;
-    const int si = m_upNext;
-    m_upNext = (m_upNext + 1) % kUploadSlots;
+    int si;
+    if ((hr = AcquireUploadSlot(bytes, &si))) return hr;
     UploadSlot &u = m_up[si];
-    if (!u.uploaded) {
-        if ((hr = CheckHip(hipEventCreateWithFlags(&u.uploaded, hipEventDisableTiming), "upload event"))) return hr;
-        if ((hr = CheckHip(hipEventCreateWithFlags(&u.consumed, hipEventDisableTiming), "consume event"))) return hr;
-    }
-    // the slot's staging / device buffers are free once the work that last used them has completed
-    if (u.inFlight && (hr = CheckHip(hipEventSynchronize(u.consumedRecorded ? u.consumed : u.uploaded), "upload slot wait"))) return hr;
-    if ((hr = CheckHip(u.dev.CheckCreate(bytes), "upload buffer"))) return hr;
     const void *from = data;
     if (memKind == MPCVR_MEM_HOST) {
         if (u.pinnedSize < bytes) {
@@ -824,8 +818,30 @@ HRESULT CHipVideoProcessor::CopySample(const void *data, int pitch, int memKind)
     if ((hr = CheckHip(hipMemcpyAsync(u.dev.ptr, from, bytes, hipMemcpyHostToDevice, m_copyStream), "upload"))) return hr;
     (void)hipEventRecord(m_evUp1, m_copyStream);
     m_upTimed = true;
-    if ((hr = CheckHip(hipEventRecord(u.uploaded, m_copyStream), "upload event"))) return hr;
-    if ((hr = CheckHip(hipStreamWaitEvent(m_stream, u.uploaded, 0), "stream wait"))) return hr;
+    return PublishUploadSlot(si, m_copyStream);
+}
+
+HRESULT CHipVideoProcessor::AcquireUploadSlot(size_t bytes, int *si)
+{
+    *si = m_upNext;
+    m_upNext = (m_upNext + 1) % kUploadSlots;
+    UploadSlot &u = m_up[*si];
+    HRESULT hr;
+    if (!u.uploaded) {
+        if ((hr = CheckHip(hipEventCreateWithFlags(&u.uploaded, hipEventDisableTiming), "upload event"))) return hr;
+        if ((hr = CheckHip(hipEventCreateWithFlags(&u.consumed, hipEventDisableTiming), "consume event"))) return hr;
+    }
+    // the slot's staging / device buffers are free once the work that last used them has completed
+    if (u.inFlight && (hr = CheckHip(hipEventSynchronize(u.consumedRecorded ? u.consumed : u.uploaded), "upload slot wait"))) return hr;
+    return CheckHip(u.dev.CheckCreate(bytes), "upload buffer");
+}
+
+HRESULT CHipVideoProcessor::PublishUploadSlot(int si, hipStream_t recordedOn)
+{
+    UploadSlot &u = m_up[si];
+    HRESULT hr;
+    if ((hr = CheckHip(hipEventRecord(u.uploaded, recordedOn), "upload event"))) return hr;
+    if (recordedOn != m_stream && (hr = CheckHip(hipStreamWaitEvent(m_stream, u.uploaded, 0), "stream wait"))) return hr;
     u.inFlight = true; u.consumedRecorded = false;
     m_curSlot = si;
     return PrepareSample((const uint8_t *)u.dev.ptr, &m_curSample);
@@ -1467,10 +1483,9 @@ HRESULT CHipVideoProcessor::TableRing::Send(size_t bytes, hipStream_t stream, co
 
 HRESULT CHipVideoProcessor::UploadFrameTable(int n, const void *const *srcs, void *const *dsts, uint8_t *dst_base, size_t dst_stride, hipStream_t stream, SlotLease *lease)
 {
-    FusedFrame *fr;
-    if (HRESULT hr = m_tableRing.Next(sizeof(FusedFrame) * n, sizeof(FusedFrame) * 64, (void **)&fr)) return hr;
-    for (int i = 0; i < n; i++) { fr[i].src = srcs ? (const uint8_t *)srcs[i] : nullptr; fr[i].dst = dsts ? dsts[i] : (void *)(dst_base + (size_t)i * dst_stride); }
-    return m_tableRing.Send(sizeof(FusedFrame) * n, stream, "frame table", lease);
+    return m_tableRing.SendRows<FusedFrame>(n, stream, "frame table", lease, [&](FusedFrame *fr) {
+        for (int i = 0; i < n; i++) { fr[i].src = srcs ? (const uint8_t *)srcs[i] : nullptr; fr[i].dst = dsts ? dsts[i] : (void *)(dst_base + (size_t)i * dst_stride); }
+    });
 }
 
 // The exact-2x kernel's tables as it keeps them in LDS, computed once per plan instead of by every workgroup of every launch
@@ -1710,783 +1725,6 @@ HRESULT CHipVideoProcessor::RenderBackBuffer(bool onContextStream)
     const size_t clearBytes = (fresh || m_videoRect != CRect(0, 0, w, h)) ? bytes : 0;     // queued on the stream the frame runs on
     hr = ProcessFrame(m_BackBuffer.ptr, w * 4, nullptr, nullptr, clearBytes, onContextStream);
     if (hr >= 0) { m_backW = w; m_backH = h; m_backFmt = m_cfg.output_format; }        // what GetDisplayedImage will find there
-    return hr;
-}
-
-// ------------------------------------------------------------------------------------------------
-// EXTENSION — the frame as NV12 / P010 for an encoder (include/mpcvr.h: mpcvr_encode_pass, mpcvr_render_yuv; kernel: vp_encode.hip).
-// No reference line: the reference has no RGB -> YUV path.
-// ------------------------------------------------------------------------------------------------
-// What a k_encode420 launch is given, but for its pointers: the caller adds src / y / uv or the frame table, and takes src16 / dst8 back
-// where a pointer of the launch is off 16 / 8 bytes (here they say what the pitches allow)
-static EncodeParams EncodeLaunchParams(const EncodePlan &plan, int w, int h, int srcPitch, int yPitch, int uvPitch)
-{
-    EncodeParams p{};
-    p.src_pitch = srcPitch; p.y_pitch = yPitch; p.uv_pitch = uvPitch;
-    p.w = w; p.h = h;
-    std::memcpy(p.coef, plan.coef, sizeof(p.coef));
-    std::memcpy(p.off, plan.off, sizeof(p.off));
-    p.src16 = (srcPitch & 15) == 0;
-    p.dst8 = ((yPitch | uvPitch) & 7) == 0;
-    return p;
-}
-
-HRESULT EncodeSurface(const void *src, int srcPitch, int srcFmt, int w, int h, int outCformat, uint32_t extfmt, void *yPlane, int yPitch,
-                      void *uvPlane, int uvPitch, hipStream_t stream, bool checkOnly, const char **why)
-{
-    const char *dummy;
-    if (!why) why = &dummy;
-    if ((!src && !checkOnly) || !yPlane || !uvPlane) { *why = "null surface or plane"; return MPCVR_E_POINTER; }      // (checkOnly: a source still to be allocated)
-    if (w < 2 || h < 2 || ((w | h) & 1) || w > 32768 || h > 32768) { *why = "width and height must be even, 2 .. 32768"; return MPCVR_E_INVALIDARG; }
-    EncodePlan plan;
-    if (!PlanEncode(outCformat, srcFmt, extfmt, w, h, &plan)) { *why = "output NV12 or P010 with a YCbCr description, source BGRA8 or RGB10A2"; return MPCVR_E_INVALIDARG; }
-    const int rowBytes = plan.out10 ? 2 * w : w;        // of the Y plane and of the UV plane alike (w / 2 pairs)
-    if (srcPitch < 4 * w || yPitch < rowBytes || uvPitch < rowBytes) { *why = "pitch smaller than a row"; return MPCVR_E_INVALIDARG; }
-    if (((uintptr_t)src | (uintptr_t)yPlane | (uintptr_t)uvPlane | (uintptr_t)srcPitch | (uintptr_t)yPitch | (uintptr_t)uvPitch) & 3) {
-        *why = "surface, planes and pitches must be multiples of 4"; return MPCVR_E_INVALIDARG;
-    }
-    const RtSpan s = RowsSpan(src, (size_t)srcPitch, h, (size_t)4 * w);
-    const RtSpan y = RowsSpan(yPlane, (size_t)yPitch, h, (size_t)rowBytes), c = RowsSpan(uvPlane, (size_t)uvPitch, h / 2, (size_t)rowBytes);
-    if (y.Overlaps(c) || (src && (y.Overlaps(s) || c.Overlaps(s)))) { *why = "the planes overlap each other or the source"; return MPCVR_E_INVALIDARG; }
-    if (checkOnly) return MPCVR_S_OK;
-    EncodeParams p = EncodeLaunchParams(plan, w, h, srcPitch, yPitch, uvPitch);
-    p.src = (const uint8_t *)src; p.y = (uint8_t *)yPlane; p.uv = (uint8_t *)uvPlane;
-    p.src16 &= (s.lo & 15) == 0;
-    p.dst8 &= ((y.lo | c.lo) & 7) == 0;
-    if (LaunchEncode420(p, plan.in10, plan.out10, plan.siting, stream) != hipSuccess) { *why = "k_encode420 launch failed"; return MPCVR_E_FAIL; }
-    return MPCVR_S_OK;
-}
-
-// Render, then the pass over the whole window behind it.  The frame stays off the lanes (like the snapshot's): the pass reads the back
-// buffer, and the lanes' bookkeeping orders WRITES into the same memory — a following Render on another lane would not wait for a reader.
-// On the context stream everything queued later, lanes included (NoteStreamWork), runs behind the pass.
-HRESULT CHipVideoProcessor::RenderYuv(int /*field*/, int outCformat, uint32_t extfmt, void *yPlane, int yPitch, void *uvPlane, int uvPitch)
-{
-    if (!m_bInit || !m_srcParams) return Fail(MPCVR_E_NOT_VALID_STATE, "InitMediaType has not been called");
-    (void)hipSetDevice(m_device);
-    const int w = m_windowRect.Width(), h = m_windowRect.Height();
-    if (w < 2 || h < 2 || ((w | h) & 1)) return Fail(MPCVR_E_INVALIDARG, "a 4:2:0 frame needs an even window width and height");
-    if (!m_curSample) return MPCVR_S_FALSE;          // nothing to draw, as Render
-    // everything about the planes is answered before anything is drawn (a back buffer Render has yet to allocate cannot overlap them)
-    const bool have = m_BackBuffer.ptr && m_BackBuffer.size >= (size_t)w * 4 * h;
-    HRESULT hr;
-    const char *why = "";
-    if ((hr = EncodeSurface(have ? m_BackBuffer.ptr : nullptr, w * 4, m_cfg.output_format, w, h, outCformat, extfmt, yPlane, yPitch, uvPlane, uvPitch, nullptr, true, &why)))
-        return Fail(hr, why);
-    if ((hr = RenderBackBuffer(true)) != MPCVR_S_OK) return hr;
-    hr = EncodeSurface(m_BackBuffer.ptr, w * 4, m_cfg.output_format, w, h, outCformat, extfmt, yPlane, yPitch, uvPlane, uvPitch, m_stream, false, &why);
-    m_launches++;
-    m_lanes.NoteStreamWork();
-    return hr ? Fail(hr, why) : MPCVR_S_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// EXTENSION — measuring a rendered frame: the histogram of max(R, G, B) (include/mpcvr.h: mpcvr_measure_pass, mpcvr_measure_backbuffer;
-// kernel: vp_measure.hip).  No reference line: the reference's statistics are an overlay.
-// ------------------------------------------------------------------------------------------------
-// What a k_measure_maxrgb launch is given, but for its pointers: src / hist and the frame stride are the caller's, as in EncodeLaunchParams
-static MeasureParams MeasureLaunchParams(int srcPitch, int w, const mpcvr_rect &r)
-{
-    MeasureParams p{};
-    p.src_pitch = srcPitch; p.w = w;
-    p.left = r.left; p.top = r.top; p.right = r.right; p.bottom = r.bottom;
-    p.src16 = (srcPitch & 15) == 0;
-    return p;
-}
-
-HRESULT MeasureSurface(const void *src, int srcPitch, int srcFmt, int w, int h, const mpcvr_rect *rect, uint32_t *histDev, hipStream_t stream,
-                       bool checkOnly, const char **why)
-{
-    const char *dummy;
-    if (!why) why = &dummy;
-    if (!src || !histDev) { *why = "null surface or histogram"; return MPCVR_E_POINTER; }
-    if (srcFmt != MPCVR_OUT_BGRA8 && srcFmt != MPCVR_OUT_RGB10A2) { *why = "source BGRA8 or RGB10A2"; return MPCVR_E_INVALIDARG; }
-    if (w < 1 || h < 1 || w > 32768 || h > 32768) { *why = "width and height must be 1 .. 32768"; return MPCVR_E_INVALIDARG; }
-    if (srcPitch < 4 * w) { *why = "pitch smaller than a row"; return MPCVR_E_INVALIDARG; }
-    if (((uintptr_t)src | (uintptr_t)histDev | (uintptr_t)srcPitch) & 3) { *why = "surface, pitch and histogram must be multiples of 4"; return MPCVR_E_INVALIDARG; }
-    const mpcvr_rect whole{0, 0, w, h};
-    const mpcvr_rect r = rect ? *rect : whole;
-    if (r.left < 0 || r.top < 0 || r.right > w || r.bottom > h || r.left >= r.right || r.top >= r.bottom) {
-        *why = "the rectangle is empty or leaves the surface"; return MPCVR_E_INVALIDARG;
-    }
-    const RtSpan s = RowsSpan(src, (size_t)srcPitch, h, (size_t)4 * w), bins{(uintptr_t)histDev, (uintptr_t)histDev + sizeof(uint32_t) * kHistBins};
-    if (bins.Overlaps(s)) { *why = "the histogram overlaps the surface"; return MPCVR_E_INVALIDARG; }
-    if (checkOnly) return MPCVR_S_OK;
-    MeasureParams p = MeasureLaunchParams(srcPitch, w, r);
-    p.src = (const uint8_t *)src; p.hist = histDev;
-    p.src16 &= (s.lo & 15) == 0;
-    if (LaunchMeasure(p, srcFmt == MPCVR_OUT_RGB10A2, stream) != hipSuccess) { *why = "k_measure_maxrgb launch failed"; return MPCVR_E_FAIL; }
-    return MPCVR_S_OK;
-}
-
-mpcvr_rect CHipVideoProcessor::ActiveRect() const
-{
-    mpcvr_rect a{std::max(m_videoRect.left, 0), std::max(m_videoRect.top, 0), std::min(m_videoRect.right, m_windowRect.Width()),
-                 std::min(m_videoRect.bottom, m_windowRect.Height())};
-    if (a.right <= a.left || a.bottom <= a.top) a = mpcvr_rect{0, 0, 0, 0};
-    return a;
-}
-
-// The pass over the back buffer as the last Render / RenderYuv left it.  It READS memory the frame lanes may still be writing and a later
-// Render on a lane may overwrite, and the lanes order writers only — so, as RenderYuv: behind the lanes on the context stream
-// (OrderOnContextStream), and everything queued later, lanes included, behind the pass (NoteStreamWork).
-HRESULT CHipVideoProcessor::MeasureBackBuffer(uint32_t *histDev)
-{
-    if (!m_bInit || !m_srcParams) return Fail(MPCVR_E_NOT_VALID_STATE, "InitMediaType has not been called");
-    if (!histDev) return Fail(MPCVR_E_POINTER, "null histogram");
-    const int w = m_windowRect.Width(), h = m_windowRect.Height();
-    // no frame yet, or none of this window's size and format (the back buffer is addressed by the window)
-    if (!m_BackBuffer.ptr || m_backW != w || m_backH != h || m_backFmt != m_cfg.output_format || w < 1 || h < 1) return MPCVR_S_FALSE;
-    (void)hipSetDevice(m_device);
-    const mpcvr_rect r = ActiveRect();
-    const bool empty = r.right <= r.left;
-    const char *why = "";
-    HRESULT hr;
-    // (an empty active area: the checks run against the whole window, then only the clear is queued)
-    if ((hr = MeasureSurface(m_BackBuffer.ptr, w * 4, m_backFmt, w, h, empty ? nullptr : &r, histDev, nullptr, true, &why))) return Fail(hr, why);
-    OrderOnContextStream();
-    if (empty) hr = CheckHip(hipMemsetAsync(histDev, 0, sizeof(uint32_t) * kHistBins, m_stream), "clear histogram");
-    else {
-        hr = MeasureSurface(m_BackBuffer.ptr, w * 4, m_backFmt, w, h, &r, histDev, m_stream, false, &why);
-        if (hr) hr = Fail(hr, why); else m_launches++;
-    }
-    m_lanes.NoteStreamWork();
-    return hr;
-}
-
-// A batch as NV12 / P010 (include/mpcvr.h: mpcvr_process_batch_yuv).  Everything about the arguments is answered first; then the call is cut
-// into chunks of PlanBatchYuv's size, and each chunk is: the batch machinery into frames of a context-owned surface, ONE k_encode420 launch
-// with a frame dimension behind it on the same stream.  A chunk whose route may take a batch lane (BatchLaneEligible) takes the next lane in
-// turn and that lane's own surface — the lane's stream order covers the surface's write, read and reuse, and the render of the next chunk
-// runs beside this one's pass on the other lane; the lanes order the chunk on the bytes it WRITES for the caller, its planes.  Every other
-// chunk runs on the context stream into the first surface, behind whatever the lanes hold (OrderOnContextStream), the lanes' next work behind it.
-// With histograms (mpcvr_process_batch_yuv_stats): ONE k_measure_maxrgb launch behind the chunk's pass on the same stream, its frame dimension
-// over the chunk's frames in the surface (they sit at frameStride: a base, a stride and the chunk's first row are all it needs).  The rows
-// are one more span the chunk writes for the caller: the lanes order on them as on the planes.
-HRESULT CHipVideoProcessor::ProcessBatchYuv(int n, const void *const *srcs, int outCformat, uint32_t extfmt, void *const *yPlanes, int yPitch,
-                                            void *const *uvPlanes, int uvPitch, uint32_t *histDev)
-{
-    const BatchRecord record(*this, n > 0 ? n : 0);
-    if (!m_bInit || !m_srcParams) return Fail(MPCVR_E_NOT_VALID_STATE, "InitMediaType has not been called");
-    if (n <= 0) return Fail(MPCVR_E_INVALIDARG, "empty batch");
-    if (!srcs || !yPlanes || !uvPlanes) return Fail(MPCVR_E_POINTER, "null array of frames or planes");
-    for (int i = 0; i < n; i++)
-        if (!srcs[i] || !yPlanes[i] || !uvPlanes[i]) return Fail(MPCVR_E_POINTER, "null frame or plane in batch");
-    if ((uintptr_t)histDev & 3) return Fail(MPCVR_E_INVALIDARG, "the histogram must be 4-byte aligned");
-    const int w = m_windowRect.Width(), h = m_windowRect.Height();
-    BatchYuvLayout lay;
-    if (!PlanBatchYuv(w, h, n, m_yuvBudget, &lay)) return Fail(MPCVR_E_INVALIDARG, "a 4:2:0 frame needs an even window width and height, 2 .. 32768");
-    // what the pass refuses, per frame (the surface is still to be allocated: it cannot overlap a plane) ...
-    const char *why = "";
-    for (int i = 0; i < n; i++)
-        if (HRESULT bad = EncodeSurface(nullptr, lay.surfacePitch, m_cfg.output_format, w, h, outCformat, extfmt, yPlanes[i], yPitch, uvPlanes[i], uvPitch, nullptr, true, &why))
-            return Fail(bad, why);
-    EncodePlan plan;
-    if (!PlanEncode(outCformat, m_cfg.output_format, extfmt, w, h, &plan)) return Fail(MPCVR_E_INVALIDARG, "output NV12 or P010 with a YCbCr description");
-    // ... and the 2n planes against each other: a plane counts as the bytes from its first pixel to the last pixel of its last row
-    const size_t rowBytes = plan.out10 ? (size_t)2 * w : (size_t)w;
-    const std::vector<RtSpan> planes = BatchPlaneSpans(n, yPlanes, yPitch, uvPlanes, uvPitch, h, rowBytes);
-    if (AnyTwoSpansOverlap(planes)) return Fail(MPCVR_E_INVALIDARG, "two planes of the batch overlap");
-    constexpr size_t kHistRow = sizeof(uint32_t) * kHistBins;
-    if (histDev) {
-        const RtSpan rows{(uintptr_t)histDev, (uintptr_t)histDev + kHistRow * (size_t)n};
-        for (const RtSpan &pl : planes)
-            if (pl.Overlaps(rows)) return Fail(MPCVR_E_INVALIDARG, "the histogram rows overlap a plane of the batch");
-    }
-
-    (void)hipSetDevice(m_device);
-    HRESULT hr = MPCVR_S_OK;
-    if (m_planDirty && (hr = UpdatePlan())) return hr;
-    const EncodeParams ep = EncodeLaunchParams(plan, w, h, lay.surfacePitch, yPitch, uvPitch);      // (src16 holds for every chunk: every frame of a surface starts on 256 bytes)
-    return RunSurfaceChunks(n, srcs, lay, "yuv",
-        [&](int at, int m) {
-            std::vector<RtSpan> writes(planes.begin() + 2 * (size_t)at, planes.begin() + 2 * (size_t)(at + m));
-            if (histDev) writes.push_back(RtSpan{(uintptr_t)histDev + kHistRow * (size_t)at, (uintptr_t)histDev + kHistRow * (size_t)(at + m)});
-            return writes;
-        },
-        [&](BatchRun &run, int at) { return EncodeChunk(run, ep, plan, yPlanes + at, uvPlanes + at, histDev ? histDev + (size_t)kHistBins * (size_t)at : nullptr); });
-}
-
-// The chunk loop of the batch calls that render into a context-owned surface and run one pass per chunk behind it (ProcessBatchYuv,
-// ProcessBatchTensor): writesOf(at, m) names the bytes the chunk of frames [at, at + m) writes for the caller, pass(run, at) queues the
-// chunk's pass on run.on.stream (run.dsts: the chunk's frames in the surface).  `tag` names the call in GetLastBatchInfo.
-template <class WritesOf, class Pass>
-HRESULT CHipVideoProcessor::RunSurfaceChunks(int n, const void *const *srcs, const BatchYuvLayout &lay, const char *tag, WritesOf writesOf, Pass pass)
-{
-    HRESULT hr = MPCVR_S_OK;
-    const int most = lay.framesPerChunk;
-    std::vector<void *> frames((size_t)most);
-    auto surfaceFrames = [&](YuvSurface &s) -> HRESULT {       // the surface for `most` frames, and their addresses
-        const size_t had = s.buf.ptr ? s.buf.size : 0;
-        if (HRESULT bad = CheckHip(s.buf.CheckCreate(lay.frameStride * (size_t)most), "batch RGB surface")) return bad;
-        if (s.buf.size != had) s.cleared = false;
-        for (int i = 0; i < most; i++) frames[i] = (uint8_t *)s.buf.ptr + (size_t)i * lay.frameStride;
-        return MPCVR_S_OK;
-    };
-    std::string lanes;
-    int chunks = 0;
-    for (int at = 0; at < n && !hr; at += most, chunks++) {
-        const int m = std::min(most, n - at);
-        BatchRun run{m, srcs + at, frames.data(), lay.surfacePitch};
-        YuvSurface *surf = &m_yuvSurf[0];
-        if ((hr = surfaceFrames(*surf))) break;
-        BatchRoutePlan rp = m_plan.errdiff ? BatchRoutePlan{} : ClassifyBatch(run);     // (an error-diffusion plan classifies its own chunks: the default is no lane route)
-        const int bl = PlaceBatch(rp, run, writesOf(at, m));
-        if (bl > 0) {                                   // another lane, another surface: the route is planned for the targets it draws into
-            surf = &m_yuvSurf[bl];
-            if ((hr = surfaceFrames(*surf))) break;
-            rp = ClassifyBatch(run);
-        }
-        if (chunks < 64) lanes += (chunks ? "," : "") + std::to_string(bl);
-        if (!(hr = RenderChunk(rp, run, *surf))) hr = pass(run, at);
-        NoteBatchQueued(bl);
-    }
-    m_yuvLastInfo = std::string(";") + tag + "_chunks=" + std::to_string(chunks) + ";" + tag + "_lanes=" + lanes;
-    return hr;
-}
-
-// the chunk's frames into the surface: the batch machinery on run.on.stream
-HRESULT CHipVideoProcessor::RenderChunk(BatchRoutePlan &rp, BatchRun &run, YuvSurface &surf)
-{
-    hipStream_t const stream = run.on.stream;
-    // Process never writes the letterbox: black once per allocation and per window / video rect, in front of the first chunk that draws there
-    if (!surf.cleared || surf.window != m_windowRect || surf.video != m_videoRect) {
-        if (HRESULT hr = CheckHip(hipMemsetAsync(surf.buf.ptr, 0, surf.buf.size, stream), "clear batch RGB surface")) return hr;
-        surf.cleared = true; surf.window = m_windowRect; surf.video = m_videoRect;
-    }
-    // (the error-diffusion plan runs its own chunks and its pass on the context stream: `run` is on it, BatchLaneEligible refuses such a plan)
-    return m_plan.errdiff ? ProcessBatchErrDiff(run) : RunBatchRoute(rp, run);
-}
-
-HRESULT CHipVideoProcessor::EncodeChunk(BatchRun &run, const EncodeParams &encode, const EncodePlan &plan, void *const *yPlanes, void *const *uvPlanes,
-                                        uint32_t *histRows)
-{
-    hipStream_t const stream = run.on.stream;
-    HRESULT hr;
-    // the planes' table through the frame tables' ring; the lease ends behind the pass
-    SlotLease table;
-    EncodeFrame *fr;
-    if ((hr = m_tableRing.Next(sizeof(EncodeFrame) * run.n, sizeof(EncodeFrame) * 64, (void **)&fr))) return hr;
-    EncodeParams ep = encode;
-    for (int i = 0; i < run.n; i++) {
-        fr[i] = EncodeFrame{(const uint8_t *)run.dsts[i], (uint8_t *)yPlanes[i], (uint8_t *)uvPlanes[i]};
-        ep.dst8 &= (((uintptr_t)yPlanes[i] | (uintptr_t)uvPlanes[i]) & 7) == 0;       // the 8-byte stores only if every plane of the launch allows them
-    }
-    if ((hr = m_tableRing.Send(sizeof(EncodeFrame) * run.n, stream, "plane table", &table))) return hr;
-    ep.frames = (const EncodeFrame *)table.dev;
-    if ((hr = CheckHip(LaunchEncode420(ep, plan.in10, plan.out10, plan.siting, stream, run.n), "k_encode420")) || !histRows) return hr;
-    // the chunk's histograms: the frames of the surface are run.dsts[0] + i * frame stride (RunSurfaceChunks lays them out so: on 256 bytes)
-    MeasureParams mp = MeasureLaunchParams(encode.src_pitch, encode.w, ActiveRect());
-    mp.src = (const uint8_t *)run.dsts[0]; mp.hist = histRows;
-    mp.frame_stride = run.n > 1 ? (size_t)((const uint8_t *)run.dsts[1] - (const uint8_t *)run.dsts[0]) : 0;
-    int launched = 0;
-    const hipError_t e = LaunchMeasure(mp, plan.in10, stream, run.n, &launched);
-    // (counted as the kernel launches it was: none for an empty active area, whose rows are only cleared)
-    return launched ? CheckHip(e, "k_measure_maxrgb") : CheckHip(e, "clear histogram rows");
-}
-
-// ------------------------------------------------------------------------------------------------
-// EXTENSION — the frame as the float tensor a model takes (include/mpcvr.h: mpcvr_tensor_pass, mpcvr_render_tensor,
-// mpcvr_process_batch_tensor; kernel: vp_tensor.hip).  No reference line: the reference has no float output.
-// ------------------------------------------------------------------------------------------------
-// the planes of one tensor (first element to last element of the last row): three for C,H,W, the whole tensor for H,W,C; returns how many
-static int TensorPlaneSpans(const mpcvr_tensor_desc &d, const void *dst, int w, int h, RtSpan out[3])
-{
-    const size_t es = (size_t)TensorElementSize(d.dtype);
-    if (d.layout == TN_INTERLEAVED) { out[0] = RowsSpan(dst, (size_t)d.row_pitch, h, 3 * es * (size_t)w); return 1; }
-    for (int k = 0; k < 3; k++) out[k] = RowsSpan((const uint8_t *)dst + (size_t)k * (size_t)d.plane_pitch, (size_t)d.row_pitch, h, es * (size_t)w);
-    return 3;
-}
-
-// What a k_tensor launch is given, but for its pointers: src / dst or the frame table are the caller's, who takes src16 / dstvec back where
-// a pointer of the launch is off the grid (here they say what the pitches allow), as in EncodeLaunchParams
-static TensorParams TensorLaunchParams(const mpcvr_tensor_desc &d, int w, int h, int srcPitch)
-{
-    TensorParams p{};
-    p.src_pitch = srcPitch; p.w = w; p.h = h;
-    p.row_pitch = d.row_pitch; p.plane_pitch = d.layout == TN_PLANAR ? d.plane_pitch : 0;
-    std::memcpy(p.scale, d.scale, sizeof(p.scale));
-    std::memcpy(p.bias, d.bias, sizeof(p.bias));
-    p.bgr = d.channel_order == MPCVR_TENSOR_BGR;
-    p.src16 = (srcPitch & 15) == 0;
-    p.dstvec = ((p.row_pitch | p.plane_pitch) & (TensorVectorBytes(d.dtype) - 1)) == 0;
-    return p;
-}
-
-HRESULT TensorSurface(const void *src, int srcPitch, int srcFmt, int w, int h, const mpcvr_tensor_desc *desc, void *dst, hipStream_t stream,
-                      bool checkOnly, const char **why)
-{
-    const char *dummy;
-    if (!why) why = &dummy;
-    if ((!src && !checkOnly) || !desc || !dst) { *why = "null surface, description or tensor"; return MPCVR_E_POINTER; }      // (checkOnly: a source still to be allocated)
-    if (srcFmt != MPCVR_OUT_BGRA8 && srcFmt != MPCVR_OUT_RGB10A2) { *why = "source BGRA8 or RGB10A2"; return MPCVR_E_INVALIDARG; }
-    if (w < 1 || h < 1 || w > 32768 || h > 32768) { *why = "width and height must be 1 .. 32768"; return MPCVR_E_INVALIDARG; }
-    if (srcPitch < 4 * w) { *why = "pitch smaller than a row"; return MPCVR_E_INVALIDARG; }
-    if (((uintptr_t)src | (uintptr_t)srcPitch) & 3) { *why = "surface and pitch must be multiples of 4"; return MPCVR_E_INVALIDARG; }
-    const mpcvr_tensor_desc &d = *desc;
-    if (d.dtype < TN_F32 || d.dtype > TN_BF16 || (d.layout != TN_PLANAR && d.layout != TN_INTERLEAVED) ||
-        (d.channel_order != MPCVR_TENSOR_RGB && d.channel_order != MPCVR_TENSOR_BGR) || d.reserved != 0) {
-        *why = "unknown dtype, layout or channel order, or reserved is not 0"; return MPCVR_E_INVALIDARG;
-    }
-    for (int k = 0; k < 3; k++)
-        if (!TensorFactorOk(d.scale[k]) || !TensorFactorOk(d.bias[k])) { *why = "scale and bias must be finite, and 0 or of magnitude 2^-100 .. 2^100"; return MPCVR_E_INVALIDARG; }
-    const bool planar = d.layout == TN_PLANAR;
-    const int64_t es = TensorElementSize(d.dtype), kMaxPitch = (int64_t)1 << 47;      // (h rows and three planes of that stay far inside 64 bits)
-    if (d.row_pitch < es * (planar ? 1 : 3) * w || d.row_pitch > kMaxPitch || (planar && (d.plane_pitch < 1 || d.plane_pitch > kMaxPitch))) {
-        *why = "row pitch smaller than a row, or a pitch that is not positive or beyond 2^47"; return MPCVR_E_INVALIDARG;
-    }
-    if (((uintptr_t)dst | (uintptr_t)d.row_pitch | (planar ? (uintptr_t)d.plane_pitch : 0)) & (uintptr_t)(es - 1)) {
-        *why = "tensor and pitches must be multiples of the element size"; return MPCVR_E_INVALIDARG;
-    }
-    const RtSpan s = RowsSpan(src, (size_t)srcPitch, h, (size_t)4 * w);
-    RtSpan pl[3];
-    const int np = TensorPlaneSpans(d, dst, w, h, pl);
-    for (int a = 0; a < np; a++) {
-        if (src && pl[a].Overlaps(s)) { *why = "a plane overlaps the source"; return MPCVR_E_INVALIDARG; }
-        for (int b = a + 1; b < np; b++)
-            if (pl[a].Overlaps(pl[b])) { *why = "two planes of the tensor overlap"; return MPCVR_E_INVALIDARG; }
-    }
-    if (checkOnly) return MPCVR_S_OK;
-    TensorParams p = TensorLaunchParams(d, w, h, srcPitch);
-    p.src = (const uint8_t *)src; p.dst = (uint8_t *)dst;
-    p.src16 &= (s.lo & 15) == 0;
-    p.dstvec &= ((uintptr_t)dst & (uintptr_t)(TensorVectorBytes(d.dtype) - 1)) == 0;
-    if (LaunchTensor(p, srcFmt == MPCVR_OUT_RGB10A2, d.dtype, d.layout, stream) != hipSuccess) { *why = "k_tensor launch failed"; return MPCVR_E_FAIL; }
-    return MPCVR_S_OK;
-}
-
-// Render, then the pass over the whole window behind it, ordered as RenderYuv (the comment there): on the context stream, the lanes' next
-// work behind the pass.
-HRESULT CHipVideoProcessor::RenderTensor(int /*field*/, const mpcvr_tensor_desc &desc, void *dst)
-{
-    if (!m_bInit || !m_srcParams) return Fail(MPCVR_E_NOT_VALID_STATE, "InitMediaType has not been called");
-    (void)hipSetDevice(m_device);
-    const int w = m_windowRect.Width(), h = m_windowRect.Height();
-    // everything about the tensor is answered before anything is drawn (a back buffer Render has yet to allocate cannot overlap it)
-    const bool have = m_BackBuffer.ptr && m_BackBuffer.size >= (size_t)w * 4 * h;
-    HRESULT hr;
-    const char *why = "";
-    if ((hr = TensorSurface(have ? m_BackBuffer.ptr : nullptr, w * 4, m_cfg.output_format, w, h, &desc, dst, nullptr, true, &why))) return Fail(hr, why);
-    if (!m_curSample) return MPCVR_S_FALSE;          // nothing to draw, as Render
-    if ((hr = RenderBackBuffer(true)) != MPCVR_S_OK) return hr;
-    hr = TensorSurface(m_BackBuffer.ptr, w * 4, m_cfg.output_format, w, h, &desc, dst, m_stream, false, &why);
-    m_launches++;
-    m_lanes.NoteStreamWork();
-    return hr ? Fail(hr, why) : MPCVR_S_OK;
-}
-
-// A batch as tensors (include/mpcvr.h: mpcvr_process_batch_tensor): ProcessBatchYuv with k_tensor as the chunk's pass.  Everything about
-// the arguments is answered first; the chunks, their surfaces, lanes and order are RunSurfaceChunks'.  Every plane of every frame is a
-// span the chunk writes.
-HRESULT CHipVideoProcessor::ProcessBatchTensor(int n, const void *const *srcs, const mpcvr_tensor_desc *desc, void *const *dsts)
-{
-    const BatchRecord record(*this, n > 0 ? n : 0);
-    if (!m_bInit || !m_srcParams) return Fail(MPCVR_E_NOT_VALID_STATE, "InitMediaType has not been called");
-    if (n <= 0) return Fail(MPCVR_E_INVALIDARG, "empty batch");
-    if (!srcs || !dsts || !desc) return Fail(MPCVR_E_POINTER, "null array of frames or tensors, or null description");
-    for (int i = 0; i < n; i++)
-        if (!srcs[i] || !dsts[i]) return Fail(MPCVR_E_POINTER, "null frame or tensor in batch");
-    const int w = m_windowRect.Width(), h = m_windowRect.Height();
-    BatchYuvLayout lay;
-    if (!PlanBatchTensor(w, h, n, m_yuvBudget, &lay)) return Fail(MPCVR_E_INVALIDARG, "a tensor needs a window width and height of 1 .. 32768");
-    // what the pass refuses, per frame (the surface is still to be allocated: it cannot overlap a plane) ...
-    const char *why = "";
-    for (int i = 0; i < n; i++)
-        if (HRESULT bad = TensorSurface(nullptr, lay.surfacePitch, m_cfg.output_format, w, h, desc, dsts[i], nullptr, true, &why)) return Fail(bad, why);
-    // ... and the planes of all frames against each other
-    const int np = desc->layout == TN_PLANAR ? 3 : 1;
-    std::vector<RtSpan> planes((size_t)np * (size_t)n);
-    for (int i = 0; i < n; i++) TensorPlaneSpans(*desc, dsts[i], w, h, &planes[(size_t)np * (size_t)i]);
-    if (AnyTwoSpansOverlap(planes)) return Fail(MPCVR_E_INVALIDARG, "two planes of the batch overlap");
-
-    (void)hipSetDevice(m_device);
-    if (HRESULT bad = m_planDirty ? UpdatePlan() : MPCVR_S_OK) return bad;
-    const TensorParams tp = TensorLaunchParams(*desc, w, h, lay.surfacePitch);      // (src16 holds for every chunk: every frame of a surface starts on 256 bytes)
-    const bool in10 = m_cfg.output_format == MPCVR_OUT_RGB10A2;
-    return RunSurfaceChunks(n, srcs, lay, "tensor",
-        [&](int at, int m) { return std::vector<RtSpan>(planes.begin() + (size_t)np * (size_t)at, planes.begin() + (size_t)np * (size_t)(at + m)); },
-        [&](BatchRun &run, int at) {
-            // the tensors' table through the frame tables' ring; the lease ends behind the pass
-            SlotLease table;
-            TensorFrame *fr;
-            if (HRESULT bad = m_tableRing.Next(sizeof(TensorFrame) * run.n, sizeof(TensorFrame) * 64, (void **)&fr)) return bad;
-            TensorParams p = tp;
-            for (int i = 0; i < run.n; i++) {
-                fr[i] = TensorFrame{(const uint8_t *)run.dsts[i], (uint8_t *)dsts[at + i]};
-                p.dstvec &= ((uintptr_t)dsts[at + i] & (uintptr_t)(TensorVectorBytes(desc->dtype) - 1)) == 0;      // the vector stores only if every tensor of the launch allows them
-            }
-            if (HRESULT bad = m_tableRing.Send(sizeof(TensorFrame) * run.n, run.on.stream, "tensor table", &table)) return bad;
-            p.frames = (const TensorFrame *)table.dev;
-            return CheckHip(LaunchTensor(p, in10, desc->dtype, desc->layout, run.on.stream, run.n), "k_tensor");
-        });
-}
-
-// ------------------------------------------------------------------------------------------------
-// EXTENSION — the way back: the float tensor a model leaves as a planar RGB sample (include/mpcvr.h: mpcvr_sample_pass,
-// mpcvr_copy_sample_tensor, mpcvr_process_batch_from_tensors; kernel: vp_tensor_in.hip).  No reference line: the reference has no float input.
-// ------------------------------------------------------------------------------------------------
-// What a k_sample_from_tensor launch is given, but for its pointers: src / dst or the frame table are the caller's, who takes srcvec / dstvec
-// back where a pointer of the launch is off the grid (here they say what the pitches allow), as in TensorLaunchParams
-static SampleParams SampleLaunchParams(const mpcvr_tensor_desc &d, int w, int h, int bytes, int maxcode, int pitch)
-{
-    SampleParams p{};
-    p.w = w; p.h = h;
-    p.row_pitch = d.row_pitch; p.plane_pitch = d.layout == TN_PLANAR ? d.plane_pitch : 0;
-    p.dst_pitch = pitch; p.dst_plane = (int64_t)pitch * h;
-    std::memcpy(p.scale, d.scale, sizeof(p.scale));
-    std::memcpy(p.bias, d.bias, sizeof(p.bias));
-    p.maxcode = (float)maxcode;
-    p.bgr = d.channel_order == MPCVR_TENSOR_BGR;
-    p.srcvec = ((p.row_pitch | p.plane_pitch) & (TensorVectorBytes(d.dtype) - 1)) == 0;
-    p.dstvec = (pitch & (4 * bytes - 1)) == 0;
-    return p;
-}
-
-HRESULT SampleSurface(const void *tensor, const mpcvr_tensor_desc *desc, int w, int h, int cformat, void *sample, int pitch, hipStream_t stream,
-                      bool checkOnly, const char **why)
-{
-    const char *dummy;
-    if (!why) why = &dummy;
-    if (!tensor || !desc || (!sample && !checkOnly)) { *why = "null tensor, description or sample"; return MPCVR_E_POINTER; }      // (checkOnly: a sample still to be allocated)
-    int bytes, maxcode;
-    if (!SampleFormat(cformat, &bytes, &maxcode)) { *why = "sample GBRP8, GBRP10 or GBRP16"; return MPCVR_E_INVALIDARG; }
-    if (w < 1 || h < 1 || w > 32768 || h > 32768) { *why = "width and height must be 1 .. 32768"; return MPCVR_E_INVALIDARG; }
-    const mpcvr_tensor_desc &d = *desc;
-    if (d.dtype < TN_F32 || d.dtype > TN_BF16 || (d.layout != TN_PLANAR && d.layout != TN_INTERLEAVED) ||
-        (d.channel_order != MPCVR_TENSOR_RGB && d.channel_order != MPCVR_TENSOR_BGR) || d.reserved != 0) {
-        *why = "unknown dtype, layout or channel order, or reserved is not 0"; return MPCVR_E_INVALIDARG;
-    }
-    for (int k = 0; k < 3; k++)
-        if (!TensorFactorOk(d.scale[k]) || !TensorFactorOk(d.bias[k])) { *why = "scale and bias must be finite, and 0 or of magnitude 2^-100 .. 2^100"; return MPCVR_E_INVALIDARG; }
-    const bool planar = d.layout == TN_PLANAR;
-    const int64_t es = TensorElementSize(d.dtype), kMaxPitch = (int64_t)1 << 47;      // (h rows and three planes of that stay far inside 64 bits)
-    if (d.row_pitch < es * (planar ? 1 : 3) * w || d.row_pitch > kMaxPitch || (planar && (d.plane_pitch < 1 || d.plane_pitch > kMaxPitch))) {
-        *why = "row pitch smaller than a row, or a pitch that is not positive or beyond 2^47"; return MPCVR_E_INVALIDARG;
-    }
-    if (((uintptr_t)tensor | (uintptr_t)d.row_pitch | (planar ? (uintptr_t)d.plane_pitch : 0)) & (uintptr_t)(es - 1)) {
-        *why = "tensor and pitches must be multiples of the element size"; return MPCVR_E_INVALIDARG;
-    }
-    if (pitch < w * bytes || (pitch & (bytes - 1)) || ((uintptr_t)sample & (uintptr_t)(bytes - 1))) {
-        *why = "sample pitch smaller than a row, or sample or pitch no multiple of the component size"; return MPCVR_E_INVALIDARG;
-    }
-    // the tensor is only read: its planes may share bytes with each other, not with a plane of the sample
-    RtSpan tp[3], sp[3];
-    const int np = TensorPlaneSpans(d, tensor, w, h, tp);
-    for (int k = 0; k < 3; k++) sp[k] = RowsSpan((const uint8_t *)sample + (size_t)k * (size_t)pitch * (size_t)h, (size_t)pitch, h, (size_t)w * bytes);
-    if (sample) {
-        for (int a = 0; a < 3; a++) {
-            for (int b = 0; b < np; b++)
-                if (sp[a].Overlaps(tp[b])) { *why = "a plane of the tensor overlaps a plane of the sample"; return MPCVR_E_INVALIDARG; }
-            for (int b = a + 1; b < 3; b++)      // (cannot happen while pitch >= a row and the planes lie pitch * h apart: checked, not assumed)
-                if (sp[a].Overlaps(sp[b])) { *why = "two planes of the sample overlap"; return MPCVR_E_INVALIDARG; }
-        }
-    }
-    if (checkOnly) return MPCVR_S_OK;
-    SampleParams p = SampleLaunchParams(d, w, h, bytes, maxcode, pitch);
-    p.src = (const uint8_t *)tensor; p.dst = (uint8_t *)sample;
-    p.srcvec &= ((uintptr_t)tensor & (uintptr_t)(TensorVectorBytes(d.dtype) - 1)) == 0;
-    p.dstvec &= ((uintptr_t)sample & (uintptr_t)(4 * bytes - 1)) == 0;
-    if (LaunchSampleFromTensor(p, d.dtype, d.layout, bytes, stream) != hipSuccess) { *why = "k_sample_from_tensor launch failed"; return MPCVR_E_FAIL; }
-    return MPCVR_S_OK;
-}
-
-// CopySample(MPCVR_MEM_HOST) with the pass in place of the host-to-device copy: the same slot ring, device buffers and events.  The pass is
-// queued on the context stream (the caller's tensor is free in stream order behind the call); `uploaded` is recorded behind it there, so a
-// frame lane waits for the pass exactly as it waits for an upload (ProcessFrame).
-HRESULT CHipVideoProcessor::CopySampleTensor(const void *tensor, const mpcvr_tensor_desc *desc)
-{
-    if (!m_bInit || !m_srcParams) return Fail(MPCVR_E_NOT_VALID_STATE, "InitMediaType has not been called");
-    if (!tensor || !desc) return Fail(MPCVR_E_POINTER, "null tensor or description");
-    // (every refusal comes before anything is touched: the current sample, its upload slot and the stream it was last drawn on stay as they are)
-    const char *why = "";
-    if (HRESULT bad = SampleSurface(tensor, desc, m_srcWidth, m_srcHeight, m_srcParams->cformat, nullptr, m_srcPitch, nullptr, true, &why)) return Fail(bad, why);
-    (void)hipSetDevice(m_device);
-    const size_t bytes = (size_t)m_srcPitch * m_srcLines;
-    HRESULT hr;
-    MarkConsumed();                                  // the previous sample is done with as far as the host is concerned
-    m_curSlot = -1;
-    m_lastRun = nullptr;
-    m_curSample = nullptr;                           // (a failure below leaves no sample rather than a slot half written)
-    const int si = m_upNext;
-    m_upNext = (m_upNext + 1) % kUploadSlots;
-    UploadSlot &u = m_up[si];
-    if (!u.uploaded) {
-        if ((hr = CheckHip(hipEventCreateWithFlags(&u.uploaded, hipEventDisableTiming), "upload event"))) return hr;
-        if ((hr = CheckHip(hipEventCreateWithFlags(&u.consumed, hipEventDisableTiming), "consume event"))) return hr;
-    }
-    // the slot's device buffer is free once the work that last used it has completed
-    if (u.inFlight && (hr = CheckHip(hipEventSynchronize(u.consumedRecorded ? u.consumed : u.uploaded), "upload slot wait"))) return hr;
-    if ((hr = CheckHip(u.dev.CheckCreate(bytes), "upload buffer"))) return hr;
-    if ((hr = SampleSurface(tensor, desc, m_srcWidth, m_srcHeight, m_srcParams->cformat, u.dev.ptr, m_srcPitch, m_stream, false, &why))) return Fail(hr, why);
-    m_launches++;
-    if ((hr = CheckHip(hipEventRecord(u.uploaded, m_stream), "upload event"))) return hr;
-    m_lanes.NoteStreamWork();
-    u.inFlight = true; u.consumedRecorded = false;
-    m_curSlot = si;
-    return PrepareSample((const uint8_t *)u.dev.ptr, &m_curSample);
-}
-
-// A batch from tensors (include/mpcvr.h: mpcvr_process_batch_from_tensors).  Everything about the arguments is answered first; then the
-// call is cut into chunks of PlanBatchSamples' size, and each chunk is ONE k_sample_from_tensor launch with a frame dimension into the
-// context-owned sample surface and the batch machinery behind it, both on the context stream: stream order covers the surface's write,
-// read and reuse by the next chunk.
-HRESULT CHipVideoProcessor::ProcessBatchFromTensors(int n, const void *const *tensors, const mpcvr_tensor_desc *desc, void *const *dsts, int rtPitch)
-{
-    const BatchRecord record(*this, n > 0 ? n : 0);
-    if (!m_bInit || !m_srcParams) return Fail(MPCVR_E_NOT_VALID_STATE, "InitMediaType has not been called");
-    if (n <= 0) return Fail(MPCVR_E_INVALIDARG, "empty batch");
-    if (!tensors || !dsts || !desc) return Fail(MPCVR_E_POINTER, "null array of tensors or frames, or null description");
-    for (int i = 0; i < n; i++)
-        if (!tensors[i] || !dsts[i]) return Fail(MPCVR_E_POINTER, "null tensor or frame in batch");
-    int bytes, maxcode;
-    if (!SampleFormat(m_srcParams->cformat, &bytes, &maxcode)) return Fail(MPCVR_E_INVALIDARG, "the input must be GBRP8, GBRP10 or GBRP16");
-    if (HRESULT bad = CheckBatchArgs(n, tensors, dsts, rtPitch)) return bad;
-    const int w = m_srcWidth, h = m_srcHeight;
-    const char *why = "";
-    for (int i = 0; i < n; i++)
-        if (HRESULT bad = SampleSurface(tensors[i], desc, w, h, m_srcParams->cformat, nullptr, m_srcPitch, nullptr, true, &why)) return Fail(bad, why);
-    BatchSampleLayout lay;
-    if (!PlanBatchSamples(m_srcPitch, h, n, m_yuvBudget, &lay)) return Fail(MPCVR_E_INVALIDARG, "sample layout");
-
-    (void)hipSetDevice(m_device);
-    if (HRESULT bad = m_planDirty ? UpdatePlan() : MPCVR_S_OK) return bad;
-    const int most = lay.framesPerChunk;
-    HRESULT hr;
-    if ((hr = CheckHip(m_sampleSurf.CheckCreate(lay.frameStride * (size_t)most), "batch sample surface"))) return hr;
-    std::vector<const void *> samples((size_t)most);
-    for (int i = 0; i < most; i++) samples[i] = (const uint8_t *)m_sampleSurf.ptr + (size_t)i * lay.frameStride;
-    // (dstvec holds for every chunk: every frame of the surface starts on 256 bytes)
-    const SampleParams sp = SampleLaunchParams(*desc, w, h, bytes, maxcode, m_srcPitch);
-    int chunks = 0;
-    for (int at = 0; at < n && !hr; at += most, chunks++) {
-        const int m = std::min(most, n - at);
-        BatchRun run{m, samples.data(), dsts + at, rtPitch};
-        run.on = RunOn{m_stream};
-        OrderOnContextStream();          // behind every frame and batch the lanes hold (the last chunk's readers of the surface are on this stream already)
-        {
-            // the tensors' table through the frame tables' ring; the lease ends behind the pass
-            SlotLease table;
-            SampleFrame *fr;
-            if ((hr = m_tableRing.Next(sizeof(SampleFrame) * m, sizeof(SampleFrame) * 64, (void **)&fr))) break;
-            SampleParams p = sp;
-            for (int i = 0; i < m; i++) {
-                fr[i] = SampleFrame{(const uint8_t *)tensors[at + i], (uint8_t *)const_cast<void *>(samples[i])};
-                p.srcvec &= ((uintptr_t)tensors[at + i] & (uintptr_t)(TensorVectorBytes(desc->dtype) - 1)) == 0;      // the vector loads only if every tensor of the launch allows them
-            }
-            if ((hr = m_tableRing.Send(sizeof(SampleFrame) * m, m_stream, "sample table", &table))) break;
-            p.frames = (const SampleFrame *)table.dev;
-            if ((hr = CheckHip(LaunchSampleFromTensor(p, desc->dtype, desc->layout, bytes, m_stream, m), "k_sample_from_tensor"))) break;
-        }
-        if (m_plan.errdiff) hr = ProcessBatchErrDiff(run);
-        else {
-            BatchRoutePlan rp = ClassifyBatch(run);
-            hr = RunBatchRoute(rp, run);
-        }
-    }
-    m_yuvLastInfo = ";sample_chunks=" + std::to_string(chunks);
-    return hr;
-}
-
-// ------------------------------------------------------------------------------------------------
-// EXTENSION — motion-adaptive deinterlacing at field rate (include/mpcvr.h: mpcvr_deint_pass, mpcvr_copy_sample_fields,
-// mpcvr_process_batch_deint; kernel: vp_deint.hip).  No reference line: the reference hands deinterlacing to the fixed-function video processor.
-// ------------------------------------------------------------------------------------------------
-// What the k_deint launches of one sample are given, but for their pointers: one DeintParams per distinct (bytes, cs) among the planes (cs[g]
-// says which), srcvec / dstvec as far as plane offsets and pitches decide them — the caller takes them back where a pointer is off the grid
-static int DeintGroupParams(const DeintPlane *sp, const DeintPlane *dp, int np, DeintParams out[2], int cs[2])
-{
-    int n = 0;
-    for (int want = 1; want <= 2; want++) {
-        DeintParams p{};
-        p.srcvec = p.dstvec = 1;
-        for (int i = 0; i < np; i++) {
-            if (sp[i].cs != want) continue;
-            const size_t grid = (size_t)(kDeintLaneSteps * want * sp[i].bytes) - 1;
-            p.plane[p.n_planes++] = DeintLaunchPlane{(int64_t)sp[i].offset, (int64_t)dp[i].offset, sp[i].pitch, dp[i].pitch, sp[i].comps / want, sp[i].lines};
-            p.srcvec &= ((sp[i].offset | (size_t)sp[i].pitch) & grid) == 0;
-            p.dstvec &= ((dp[i].offset | (size_t)dp[i].pitch) & grid) == 0;
-            p.mask = sp[i].mask;
-        }
-        if (p.n_planes) { out[n] = p; cs[n++] = want; }
-    }
-    return n;
-}
-
-HRESULT DeintSurface(const void *prev, const void *cur, const void *next, int cformat, int w, int h, int pitch, int keep, int first, int mode,
-                     void *dst, int dstPitch, hipStream_t stream, bool checkOnly, const char **why, int *launches)
-{
-    const char *dummy;
-    if (!why) why = &dummy;
-    if (launches) *launches = 0;
-    if (!prev || !cur || !next || (!dst && !checkOnly)) { *why = "null sample"; return MPCVR_E_POINTER; }      // (checkOnly: a destination still to be allocated)
-    DeintPlane sp[kDeintMaxPlanes], dp[kDeintMaxPlanes];
-    int np = 0, npd = 0;
-    if (!PlanDeintPlanes(cformat, w, h, pitch, &np, sp) || !PlanDeintPlanes(cformat, w, h, dstPitch, &npd, dp)) {
-        *why = "a planar or bi-planar format, a size and pitches by the rules of mpcvr_set_input, at least 2 lines per plane"; return MPCVR_E_INVALIDARG;
-    }
-    if ((keep != 0 && keep != 1) || (first != 0 && first != 1) || (mode != DI_ADAPTIVE && mode != DI_ADAPTIVE_NOCHECK)) {
-        *why = "keep and first are 0 or 1, mode MPCVR_DEINT_ADAPTIVE_EXT or MPCVR_DEINT_ADAPTIVE_NOCHECK_EXT"; return MPCVR_E_INVALIDARG;
-    }
-    const int bytes = sp[0].bytes;
-    if (((uintptr_t)prev | (uintptr_t)cur | (uintptr_t)next | (uintptr_t)dst) & (uintptr_t)(bytes - 1)) {
-        *why = "samples must be multiples of the component size"; return MPCVR_E_INVALIDARG;
-    }
-    // the sources are only read: they may share bytes with each other, not with a plane of the destination
-    if (dst) {
-        const void *const srcs[3] = {prev, cur, next};
-        for (int a = 0; a < np; a++) {
-            const RtSpan d = RowsSpan((const uint8_t *)dst + dp[a].offset, (size_t)dp[a].pitch, dp[a].lines, (size_t)dp[a].comps * bytes);
-            for (int s = 0; s < 3; s++)
-                for (int b = 0; b < np; b++)
-                    if (d.Overlaps(RowsSpan((const uint8_t *)srcs[s] + sp[b].offset, (size_t)sp[b].pitch, sp[b].lines, (size_t)sp[b].comps * bytes))) {
-                        *why = "a plane of the destination overlaps a plane of a source"; return MPCVR_E_INVALIDARG;
-                    }
-            for (int b = a + 1; b < np; b++)
-                if (d.Overlaps(RowsSpan((const uint8_t *)dst + dp[b].offset, (size_t)dp[b].pitch, dp[b].lines, (size_t)dp[b].comps * bytes))) {
-                    *why = "two planes of the destination overlap"; return MPCVR_E_INVALIDARG;
-                }
-        }
-    }
-    if (checkOnly) return MPCVR_S_OK;
-    DeintParams g[2];
-    int cs[2];
-    const int ng = DeintGroupParams(sp, dp, np, g, cs);
-    for (int i = 0; i < ng; i++) {
-        DeintParams &p = g[i];
-        const uintptr_t grid = (uintptr_t)(kDeintLaneSteps * cs[i] * bytes) - 1;
-        p.one = DeintFrame{(const uint8_t *)prev, (const uint8_t *)cur, (const uint8_t *)next, (uint8_t *)dst, keep, first};
-        p.srcvec &= (((uintptr_t)prev | (uintptr_t)cur | (uintptr_t)next) & grid) == 0;
-        p.dstvec &= ((uintptr_t)dst & grid) == 0;
-        if (LaunchDeint(p, bytes, cs[i], mode, stream) != hipSuccess) { *why = "k_deint launch failed"; return MPCVR_E_FAIL; }
-        if (launches) ++*launches;
-    }
-    return MPCVR_S_OK;
-}
-
-// keep and first of field `field` (0 the first, 1 the second) of a frame of `fieldOrder` (1 top field first, 2 bottom field first)
-static void FieldParity(int fieldOrder, int field, int *keep, int *first)
-{
-    *first = field == 0;
-    *keep = fieldOrder == 1 ? field : 1 - field;
-}
-
-// CopySampleTensor with k_deint as the pass: the same slot ring, device buffers and events, on the context stream.
-HRESULT CHipVideoProcessor::CopySampleFields(const void *prev, const void *cur, const void *next, int fieldOrder, int field, int mode)
-{
-    if (!m_bInit || !m_srcParams) return Fail(MPCVR_E_NOT_VALID_STATE, "InitMediaType has not been called");
-    if (!prev || !cur || !next) return Fail(MPCVR_E_POINTER, "null sample");
-    if ((fieldOrder != 1 && fieldOrder != 2) || (field != 0 && field != 1)) return Fail(MPCVR_E_INVALIDARG, "field_order is 1 or 2, field 0 or 1");
-    int keep, first;
-    FieldParity(fieldOrder, field, &keep, &first);
-    // (every refusal comes before anything is touched: the current sample, its upload slot and the stream it was last drawn on stay as they are)
-    const char *why = "";
-    const int cf = m_srcParams->cformat;
-    if (HRESULT bad = DeintSurface(prev, cur, next, cf, m_srcWidth, m_srcHeight, m_srcPitch, keep, first, mode, nullptr, m_srcPitch, nullptr, true, &why)) return Fail(bad, why);
-    (void)hipSetDevice(m_device);
-    const size_t bytes = (size_t)m_srcPitch * m_srcLines;
-    HRESULT hr;
-    MarkConsumed();                                  // the previous sample is done with as far as the host is concerned
-    m_curSlot = -1;
-    m_lastRun = nullptr;
-    m_curSample = nullptr;                           // (a failure below leaves no sample rather than a slot half written)
-    const int si = m_upNext;
-    m_upNext = (m_upNext + 1) % kUploadSlots;
-    UploadSlot &u = m_up[si];
-    if (!u.uploaded) {
-        if ((hr = CheckHip(hipEventCreateWithFlags(&u.uploaded, hipEventDisableTiming), "upload event"))) return hr;
-        if ((hr = CheckHip(hipEventCreateWithFlags(&u.consumed, hipEventDisableTiming), "consume event"))) return hr;
-    }
-    // the slot's device buffer is free once the work that last used it has completed
-    if (u.inFlight && (hr = CheckHip(hipEventSynchronize(u.consumedRecorded ? u.consumed : u.uploaded), "upload slot wait"))) return hr;
-    if ((hr = CheckHip(u.dev.CheckCreate(bytes), "upload buffer"))) return hr;
-    int launched = 0;
-    // (the slot's buffer may be one a caller was handed as a sample address long ago: the overlap rule is asked again with the real destination)
-    if ((hr = DeintSurface(prev, cur, next, cf, m_srcWidth, m_srcHeight, m_srcPitch, keep, first, mode, u.dev.ptr, m_srcPitch, m_stream, false, &why, &launched))) return Fail(hr, why);
-    m_launches += launched;
-    if ((hr = CheckHip(hipEventRecord(u.uploaded, m_stream), "upload event"))) return hr;
-    m_lanes.NoteStreamWork();
-    u.inFlight = true; u.consumedRecorded = false;
-    m_curSlot = si;
-    return PrepareSample((const uint8_t *)u.dev.ptr, &m_curSample);
-}
-
-// A batch at field rate (include/mpcvr.h: mpcvr_process_batch_deint).  Everything about the arguments is answered first; then the output
-// frames are cut into chunks of PlanBatchDeint's size, and each chunk is the pass with a frame dimension (one launch per distinct (bytes,
-// cs) among the planes) into the context-owned sample surface and the batch machinery behind it, both on the context stream, as in
-// ProcessBatchFromTensors.
-HRESULT CHipVideoProcessor::ProcessBatchDeint(int n, const void *const *frames, int fieldOrder, int fieldsPerFrame, int mode, void *const *dsts, int rtPitch)
-{
-    const bool fpfOk = fieldsPerFrame == 1 || fieldsPerFrame == 2;
-    const int nOut = n > 0 && n <= (1 << 24) && fpfOk ? n * fieldsPerFrame : 0;
-    const BatchRecord record(*this, nOut);
-    if (!m_bInit || !m_srcParams) return Fail(MPCVR_E_NOT_VALID_STATE, "InitMediaType has not been called");
-    if (n <= 0 || n > (1 << 24)) return Fail(MPCVR_E_INVALIDARG, "empty batch");
-    if (!frames || !dsts) return Fail(MPCVR_E_POINTER, "null array of samples or frames");
-    if (!fpfOk || (fieldOrder != 1 && fieldOrder != 2) || (mode != DI_ADAPTIVE && mode != DI_ADAPTIVE_NOCHECK))
-        return Fail(MPCVR_E_INVALIDARG, "fields_per_frame is 1 or 2, field_order 1 or 2, mode MPCVR_DEINT_ADAPTIVE_EXT or MPCVR_DEINT_ADAPTIVE_NOCHECK_EXT");
-    for (int i = 0; i < n + 2; i++)
-        if (!frames[i]) return Fail(MPCVR_E_POINTER, "null sample in batch");
-    for (int k = 0; k < nOut; k++)
-        if (!dsts[k]) return Fail(MPCVR_E_POINTER, "null frame in batch");
-    DeintPlane sp[kDeintMaxPlanes];
-    int np = 0;
-    if (!PlanDeintPlanes(m_srcParams->cformat, m_srcWidth, m_srcHeight, m_srcPitch, &np, sp))
-        return Fail(MPCVR_E_INVALIDARG, "the input must be a planar or bi-planar format of at least 2 lines per plane");
-    const int bytes = sp[0].bytes;
-    std::vector<const void *> curs((size_t)nOut);
-    for (int k = 0; k < nOut; k++) curs[k] = frames[1 + k / fieldsPerFrame];
-    if (HRESULT bad = CheckBatchArgs(nOut, curs.data(), dsts, rtPitch)) return bad;
-    uintptr_t bits = 0;
-    for (int i = 0; i < n + 2; i++) bits |= (uintptr_t)frames[i];
-    if (bits & (uintptr_t)(bytes - 1)) return Fail(MPCVR_E_INVALIDARG, "samples must be multiples of the component size");
-    BatchDeintLayout lay;
-    if (!PlanBatchDeint(m_srcPitch, m_srcLines, nOut, m_yuvBudget, &lay)) return Fail(MPCVR_E_INVALIDARG, "sample layout");
-
-    (void)hipSetDevice(m_device);
-    if (HRESULT bad = m_planDirty ? UpdatePlan() : MPCVR_S_OK) return bad;
-    const int most = lay.framesPerChunk;
-    HRESULT hr;
-    if ((hr = CheckHip(m_sampleSurf.CheckCreate(lay.frameStride * (size_t)most), "batch sample surface"))) return hr;
-    std::vector<const void *> samples((size_t)most);
-    for (int i = 0; i < most; i++) samples[i] = (const uint8_t *)m_sampleSurf.ptr + (size_t)i * lay.frameStride;
-    // (dstvec holds for every chunk: every frame of the surface starts on 256 bytes; srcvec only if every sample of the call allows it)
-    DeintParams g[2];
-    int cs[2];
-    const int ng = DeintGroupParams(sp, sp, np, g, cs);
-    for (int i = 0; i < ng; i++) g[i].srcvec &= (bits & ((uintptr_t)(kDeintLaneSteps * cs[i] * bytes) - 1)) == 0;
-    int chunks = 0;
-    for (int at = 0; at < nOut && !hr; at += most, chunks++) {
-        const int m = std::min(most, nOut - at);
-        BatchRun run{m, samples.data(), dsts + at, rtPitch};
-        run.on = RunOn{m_stream};
-        OrderOnContextStream();          // behind every frame and batch the lanes hold (the last chunk's readers of the surface are on this stream already)
-        {
-            // the frames' table through the frame tables' ring; the lease ends behind the pass
-            SlotLease table;
-            DeintFrame *fr;
-            if ((hr = m_tableRing.Next(sizeof(DeintFrame) * m, sizeof(DeintFrame) * 64, (void **)&fr))) break;
-            for (int i = 0; i < m; i++) {
-                const int k = at + i, f = 1 + k / fieldsPerFrame;
-                int keep, first;
-                FieldParity(fieldOrder, k % fieldsPerFrame, &keep, &first);
-                fr[i] = DeintFrame{(const uint8_t *)frames[f - 1], (const uint8_t *)frames[f], (const uint8_t *)frames[f + 1],
-                                   (uint8_t *)const_cast<void *>(samples[i]), keep, first};
-            }
-            if ((hr = m_tableRing.Send(sizeof(DeintFrame) * m, m_stream, "deint table", &table))) break;
-            for (int i = 0; i < ng && !hr; i++) {
-                DeintParams p = g[i];
-                p.frames = (const DeintFrame *)table.dev;
-                hr = CheckHip(LaunchDeint(p, bytes, cs[i], mode, m_stream, m), "k_deint");
-            }
-            if (hr) break;
-        }
-        if (m_plan.errdiff) hr = ProcessBatchErrDiff(run);
-        else {
-            BatchRoutePlan rp = ClassifyBatch(run);
-            hr = RunBatchRoute(rp, run);
-        }
-    }
-    m_yuvLastInfo = ";deint_chunks=" + std::to_string(chunks);
     return hr;
 }
 

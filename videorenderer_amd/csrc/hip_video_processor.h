@@ -276,6 +276,15 @@ private:
         HRESULT Next(size_t bytes, size_t atLeast, void **pinned);
         // its first `bytes` to the device on `stream` (`what` names the copy in an error); *lease: the device copy on loan.  The turn passes on
         HRESULT Send(size_t bytes, hipStream_t stream, const char *what, SlotLease *lease);
+        // both around fill(Row *rows), which writes the table's n rows into the pinned copy: (const Row *)lease->dev is the table on the device
+        template <class Row, class Fill>
+        HRESULT SendRows(int n, hipStream_t stream, const char *what, SlotLease *lease, Fill fill)
+        {
+            Row *rows;
+            if (HRESULT hr = Next(sizeof(Row) * n, sizeof(Row) * 64, (void **)&rows)) return hr;
+            fill(rows);
+            return Send(sizeof(Row) * n, stream, what, lease);
+        }
         size_t Sent() const { return m_sent; }
         void Release();
     private:
@@ -353,6 +362,11 @@ private:
     int m_upNext = 0, m_curSlot = -1;
     hipStream_t m_copyStream = nullptr;
     void MarkConsumed();
+    // What CopySample's host branches, CopySampleTensor and CopySampleFields share.  Acquire: the slot whose turn it is (*si), free to be rewritten
+    // (the host has waited for the work that last used it), its device buffer of `bytes` or more.  Publish, once its new content is queued on
+    // `recordedOn`: `uploaded` recorded there (another stream than the context's: that one waits for it), the slot current, its buffer the sample
+    HRESULT AcquireUploadSlot(size_t bytes, int *si);
+    HRESULT PublishUploadSlot(int si, hipStream_t recordedOn);
     const uint8_t *m_curSample = nullptr;   // device pointer of the current sample (own buffer or zero-copy)
     DevBuffer m_TexConvertOutput, m_TexResize, m_BackBuffer, m_Snapshot;
     int m_backW = 0, m_backH = 0, m_backFmt = 0;       // the last frame Render put into m_BackBuffer: size and format (GetDisplayedImage)
@@ -464,9 +478,12 @@ private:
     size_t m_yuvBudget = 0;            // SetBatchYuvBudget; 0: kBatchYuvDefaultBudget
     std::string m_yuvLastInfo;         // ";yuv_chunks=..;yuv_lanes=.." (";tensor_chunks=..;tensor_lanes=..") of the last batch call, if it was a ProcessBatchYuv (ProcessBatchTensor)
     DevBuffer m_sampleSurf;            // ProcessBatchFromTensors / ProcessBatchDeint: the samples of one chunk side by side (PlanBatchSamples), written and read in stream order on the context stream
-    // the chunk loop of both: surfaces, lanes and order; writesOf(at, m): what the chunk writes for the caller, pass(run, at): its pass
+    // the chunk loop of ProcessBatchYuv / ProcessBatchTensor: surfaces, lanes and order; writesOf(at, m): what the chunk writes for the caller, pass(run, at): its pass
     template <class WritesOf, class Pass>
     HRESULT RunSurfaceChunks(int n, const void *const *srcs, const BatchYuvLayout &lay, const char *tag, WritesOf writesOf, Pass pass);
+    // its mirror, the chunk loop of ProcessBatchFromTensors / ProcessBatchDeint: pass(at, m, samples, stream) writes the chunk's samples into m_sampleSurf
+    template <class Pass>
+    HRESULT RunSampleChunks(int n, const ChunkLayout &lay, void *const *dsts, int rtPitch, const char *tag, Pass pass);
     // one chunk into its surface: rp / run.dsts name the surface's frames, run.on the stream
     HRESULT RenderChunk(BatchRoutePlan &rp, BatchRun &run, YuvSurface &surf);
     // ... and its passes behind it: `encode` holds the launch's pitches, size and coefficients

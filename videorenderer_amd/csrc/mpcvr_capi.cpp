@@ -168,17 +168,24 @@ int32_t mpcvr_process_batch_dovi(mpcvr_ctx *ctx, int32_t n, const void *const *s
 }
 
 // EXTENSION: a batch as NV12 / P010 (include/mpcvr.h; PlanBatchYuv vp_plan.cpp, CHipVideoProcessor::ProcessBatchYuv)
-static_assert(MPCVR_BATCH_YUV_DEFAULT_BUDGET == mpcvr::kBatchYuvDefaultBudget, "the header and vp_encode.h name one default budget");
-int32_t mpcvr_plan_batch_yuv(int32_t window_w, int32_t window_h, int32_t n, size_t budget_bytes,
-                             int32_t *surface_pitch, size_t *frame_stride, int32_t *frames_per_chunk, int32_t *chunks)
+static_assert(MPCVR_BATCH_YUV_DEFAULT_BUDGET == mpcvr::kBatchYuvDefaultBudget, "the header and vp_plan.h name one default budget");
+// what the four mpcvr_plan_batch_* functions hand back of a planned layout (each pointer optional)
+static int32_t ChunkLayoutOut(bool planned, const mpcvr::ChunkLayout &lay, size_t *frame_stride, int32_t *frames_per_chunk, int32_t *chunks)
 {
-    mpcvr::BatchYuvLayout lay;
-    if (!mpcvr::PlanBatchYuv(window_w, window_h, n, budget_bytes, &lay)) return MPCVR_E_INVALIDARG;
-    if (surface_pitch) *surface_pitch = lay.surfacePitch;
+    if (!planned) return MPCVR_E_INVALIDARG;
     if (frame_stride) *frame_stride = lay.frameStride;
     if (frames_per_chunk) *frames_per_chunk = lay.framesPerChunk;
     if (chunks) *chunks = lay.chunks;
     return MPCVR_S_OK;
+}
+
+int32_t mpcvr_plan_batch_yuv(int32_t window_w, int32_t window_h, int32_t n, size_t budget_bytes,
+                             int32_t *surface_pitch, size_t *frame_stride, int32_t *frames_per_chunk, int32_t *chunks)
+{
+    mpcvr::BatchYuvLayout lay;
+    const bool planned = mpcvr::PlanBatchYuv(window_w, window_h, n, budget_bytes, &lay);
+    if (planned && surface_pitch) *surface_pitch = lay.surfacePitch;
+    return ChunkLayoutOut(planned, lay, frame_stride, frames_per_chunk, chunks);
 }
 
 int32_t mpcvr_set_batch_yuv_budget(mpcvr_ctx *ctx, size_t bytes) { CTX_OR_FAIL(); return ctx->vp.SetBatchYuvBudget(bytes); }
@@ -191,7 +198,7 @@ int32_t mpcvr_process_batch_yuv(mpcvr_ctx *ctx, int32_t n, const void *const *sr
 }
 
 // EXTENSION: the histogram of max(R, G, B) of rendered frames and what a host derives from it (include/mpcvr.h; k_measure_maxrgb
-// vp_measure.hip, MeasureSurface hip_video_processor.cpp, the host functions vp_plan.cpp)
+// vp_measure.hip, MeasureSurface hip_video_processor_ext.cpp, the host functions vp_plan.cpp)
 static_assert(MPCVR_HIST_BINS == mpcvr::kHistBins, "the header and vp_measure.h name one histogram size");
 int32_t mpcvr_process_batch_yuv_stats(mpcvr_ctx *ctx, int32_t n, const void *const *srcs, int32_t out_cformat, uint32_t extfmt,
                                       void *const *y_planes, int32_t y_pitch, void *const *uv_planes, int32_t uv_pitch, uint32_t *hist_dev)
@@ -228,7 +235,7 @@ int32_t mpcvr_histogram_percentile(const uint32_t hist[MPCVR_HIST_BINS], uint32_
 }
 
 // EXTENSION: rendered frames as float tensors (include/mpcvr.h; k_tensor vp_tensor.hip, the arithmetic vp_tensor_core.h, TensorSurface and
-// CHipVideoProcessor::RenderTensor / ProcessBatchTensor hip_video_processor.cpp, PlanTensorValue / PlanBatchTensor vp_plan.cpp)
+// CHipVideoProcessor::RenderTensor / ProcessBatchTensor hip_video_processor_ext.cpp, PlanTensorValue / PlanBatchTensor vp_plan.cpp)
 static_assert(MPCVR_TENSOR_F32 == mpcvr::TN_F32 && MPCVR_TENSOR_F16 == mpcvr::TN_F16 && MPCVR_TENSOR_BF16 == mpcvr::TN_BF16 &&
               MPCVR_TENSOR_PLANAR == mpcvr::TN_PLANAR && MPCVR_TENSOR_INTERLEAVED == mpcvr::TN_INTERLEAVED, "the header and vp_tensor_core.h name one set of tensor formats");
 int32_t mpcvr_plan_tensor_value(int32_t dtype, int32_t src_fmt, uint32_t code, float scale, float bias, uint32_t *bits)
@@ -253,12 +260,9 @@ int32_t mpcvr_plan_batch_tensor(int32_t window_w, int32_t window_h, int32_t n, s
                                 int32_t *surface_pitch, size_t *frame_stride, int32_t *frames_per_chunk, int32_t *chunks)
 {
     mpcvr::BatchYuvLayout lay;
-    if (!mpcvr::PlanBatchTensor(window_w, window_h, n, budget_bytes, &lay)) return MPCVR_E_INVALIDARG;
-    if (surface_pitch) *surface_pitch = lay.surfacePitch;
-    if (frame_stride) *frame_stride = lay.frameStride;
-    if (frames_per_chunk) *frames_per_chunk = lay.framesPerChunk;
-    if (chunks) *chunks = lay.chunks;
-    return MPCVR_S_OK;
+    const bool planned = mpcvr::PlanBatchTensor(window_w, window_h, n, budget_bytes, &lay);
+    if (planned && surface_pitch) *surface_pitch = lay.surfacePitch;
+    return ChunkLayoutOut(planned, lay, frame_stride, frames_per_chunk, chunks);
 }
 
 int32_t mpcvr_process_batch_tensor(mpcvr_ctx *ctx, int32_t n, const void *const *srcs, const mpcvr_tensor_desc *desc, void *const *dsts)
@@ -268,7 +272,7 @@ int32_t mpcvr_process_batch_tensor(mpcvr_ctx *ctx, int32_t n, const void *const 
 }
 
 // EXTENSION: a model's float tensor as the sample (include/mpcvr.h; k_sample_from_tensor vp_tensor_in.hip, the arithmetic vp_tensor_core.h,
-// SampleSurface and CHipVideoProcessor::CopySampleTensor / ProcessBatchFromTensors hip_video_processor.cpp, PlanSampleCode / PlanBatchSamples vp_plan.cpp)
+// SampleSurface and CHipVideoProcessor::CopySampleTensor / ProcessBatchFromTensors hip_video_processor_ext.cpp, PlanSampleCode / PlanBatchSamples vp_plan.cpp)
 int32_t mpcvr_plan_sample_code(int32_t dtype, int32_t cformat, uint32_t element_bits, float scale, float bias, uint32_t *code)
 {
     if (!code) return MPCVR_E_POINTER;
@@ -288,12 +292,8 @@ int32_t mpcvr_copy_sample_tensor(mpcvr_ctx *ctx, const void *tensor, const mpcvr
 
 int32_t mpcvr_plan_batch_from_tensors(int32_t pitch, int32_t h, int32_t n, size_t budget_bytes, size_t *frame_stride, int32_t *frames_per_chunk, int32_t *chunks)
 {
-    mpcvr::BatchSampleLayout lay;
-    if (!mpcvr::PlanBatchSamples(pitch, h, n, budget_bytes, &lay)) return MPCVR_E_INVALIDARG;
-    if (frame_stride) *frame_stride = lay.frameStride;
-    if (frames_per_chunk) *frames_per_chunk = lay.framesPerChunk;
-    if (chunks) *chunks = lay.chunks;
-    return MPCVR_S_OK;
+    mpcvr::ChunkLayout lay;
+    return ChunkLayoutOut(mpcvr::PlanBatchSamples(pitch, h, n, budget_bytes, &lay), lay, frame_stride, frames_per_chunk, chunks);
 }
 
 int32_t mpcvr_process_batch_from_tensors(mpcvr_ctx *ctx, int32_t n, const void *const *tensors, const mpcvr_tensor_desc *desc, void *const *dsts, int32_t dst_pitch)
@@ -303,7 +303,7 @@ int32_t mpcvr_process_batch_from_tensors(mpcvr_ctx *ctx, int32_t n, const void *
 }
 
 // EXTENSION: motion-adaptive deinterlacing at field rate (include/mpcvr.h; k_deint vp_deint.hip, the arithmetic vp_deint_core.h, DeintSurface and
-// CHipVideoProcessor::CopySampleFields / ProcessBatchDeint hip_video_processor.cpp, PlanDeintPlanes / PlanBatchDeint vp_plan.cpp)
+// CHipVideoProcessor::CopySampleFields / ProcessBatchDeint hip_video_processor_ext.cpp, PlanDeintPlanes / PlanBatchDeint vp_plan.cpp)
 static_assert(MPCVR_DEINT_ADAPTIVE_EXT == mpcvr::DI_ADAPTIVE && MPCVR_DEINT_ADAPTIVE_NOCHECK_EXT == mpcvr::DI_ADAPTIVE_NOCHECK, "the header and vp_deint_core.h name one set of modes");
 int32_t mpcvr_plan_deint_planes(int32_t cformat, int32_t w, int32_t h, int32_t pitch, int32_t *planes, mpcvr_deint_plane out[3])
 {
@@ -344,12 +344,8 @@ int32_t mpcvr_copy_sample_fields(mpcvr_ctx *ctx, const void *prev, const void *c
 
 int32_t mpcvr_plan_batch_deint(int32_t pitch, int32_t lines, int32_t n_out, size_t budget_bytes, size_t *frame_stride, int32_t *frames_per_chunk, int32_t *chunks)
 {
-    mpcvr::BatchDeintLayout lay;
-    if (!mpcvr::PlanBatchDeint(pitch, lines, n_out, budget_bytes, &lay)) return MPCVR_E_INVALIDARG;
-    if (frame_stride) *frame_stride = lay.frameStride;
-    if (frames_per_chunk) *frames_per_chunk = lay.framesPerChunk;
-    if (chunks) *chunks = lay.chunks;
-    return MPCVR_S_OK;
+    mpcvr::ChunkLayout lay;
+    return ChunkLayoutOut(mpcvr::PlanBatchDeint(pitch, lines, n_out, budget_bytes, &lay), lay, frame_stride, frames_per_chunk, chunks);
 }
 
 int32_t mpcvr_process_batch_deint(mpcvr_ctx *ctx, int32_t n, const void *const *frames, int32_t field_order, int32_t fields_per_frame, int32_t mode,

@@ -8,6 +8,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "vp_plan.h"
 #include "vp_deint_core.h"
 
 namespace mpcvr {
@@ -29,9 +30,8 @@ struct DeintPlane { size_t offset; int32_t pitch, comps, lines, bytes, cs, mask;
 // not take, a size or pitch outside the rules, a plane of fewer than 2 lines.  Host only (vp_plan.cpp)
 bool PlanDeintPlanes(int cformat, int w, int h, int pitch, int *planes, DeintPlane out[kDeintMaxPlanes]);
 // the context-owned sample surface of mpcvr_process_batch_deint: output frame i of a chunk at i * frameStride (pitch * lines bytes rounded
-// up to 256), chunks by the library's chunk rule (FramesPerChunk) under `budget` (0: kBatchYuvDefaultBudget)
-struct BatchDeintLayout { size_t frameStride; int32_t framesPerChunk, chunks; };
-bool PlanBatchDeint(int pitch, int lines, int nOut, size_t budget, BatchDeintLayout *out);
+// up to 256), chunks by PlanChunks (vp_plan.h) under `budget`
+bool PlanBatchDeint(int pitch, int lines, int nOut, size_t budget, ChunkLayout *out);
 
 // one output frame of a launch with a frame dimension: three samples, the sample to write, the shown field
 struct DeintFrame { const uint8_t *prev, *cur, *next; uint8_t *dst; int32_t keep, first; };
@@ -49,7 +49,7 @@ struct DeintParams {
     int32_t dstvec;                                    // ... every destination plane: one vector store per lane and row
 };
 // bytes 1 / 2, cs 1 / 2, mode DI_ADAPTIVE / DI_ADAPTIVE_NOCHECK.  The caller has checked sizes, pitches and overlaps (DeintSurface,
-// hip_video_processor.cpp); one launch for as many frames as the grid's z extent holds, one more per further such lot
+// hip_video_processor_ext.cpp); one launch for as many frames as the grid's z extent holds, one more per further such lot
 hipError_t LaunchDeint(const DeintParams &p, int bytes, int cs, int mode, hipStream_t stream, int n_frames = 1);
 
 }  // namespace mpcvr

@@ -6,6 +6,8 @@
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
+#include "vp_plan.h"
+
 namespace mpcvr {
 
 constexpr int kEncodeShift = 16;                       // S: fractional bits of the coefficients
@@ -30,8 +32,7 @@ bool PlanEncode(int out_cformat, int src_fmt, uint32_t extfmt, int w, int h, Enc
 // The layout integers of include/mpcvr.h (mpcvr_plan_batch_yuv): the context-owned RGB surface a batch is rendered into on its way to the
 // planes, and how a batch of n frames is cut into chunks under a budget of bytes.  Host only (vp_plan.cpp).  false: n <= 0 or a window
 // that is odd or outside 2 .. 32768
-struct BatchYuvLayout { int32_t surfacePitch; size_t frameStride; int32_t framesPerChunk, chunks; };
-constexpr size_t kBatchYuvDefaultBudget = (size_t)4 << 30;      // MPCVR_BATCH_YUV_DEFAULT_BUDGET (mpcvr_capi.cpp asserts they agree)
+struct BatchYuvLayout : ChunkLayout { int32_t surfacePitch; };
 bool PlanBatchYuv(int w, int h, int n, size_t budget, BatchYuvLayout *out);
 // the same three formulas for a window of any parity, 1 .. 32768 (mpcvr_plan_batch_tensor: the tensor pass has no 2x2 blocks)
 bool PlanBatchTensor(int w, int h, int n, size_t budget, BatchYuvLayout *out);

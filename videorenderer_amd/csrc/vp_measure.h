@@ -37,7 +37,7 @@ int MeasureGroupCols(int rect_w, int rect_h, int n_frames);
 
 // Clears the n_frames x kHistBins words (one hipMemsetAsync on `stream`) and counts behind it: one launch for up to 65535 frames.  An empty
 // rectangle leaves the cleared words and launches nothing.  *launches (may be null): kernel launches queued.  The caller checks pointers,
-// pitch and that the rectangle lies inside the surface (MeasureSurface, hip_video_processor.cpp).
+// pitch and that the rectangle lies inside the surface (MeasureSurface, hip_video_processor_ext.cpp).
 hipError_t LaunchMeasure(const MeasureParams &p, bool in10, hipStream_t stream, int n_frames = 1, int *launches = nullptr);
 
 // ---- host only, no device work (vp_plan.cpp) ----

@@ -234,13 +234,9 @@ bool PlanBatchYuv(int w, int h, int n, size_t budget, BatchYuvLayout *out)
 
 bool PlanBatchTensor(int w, int h, int n, size_t budget, BatchYuvLayout *out)
 {
-    if (n <= 0 || w < 1 || h < 1 || w > 32768 || h > 32768) return false;
-    if (!budget) budget = kBatchYuvDefaultBudget;
+    if (w < 1 || h < 1 || w > 32768 || h > 32768) return false;
     out->surfacePitch = (4 * w + 15) & ~15;
-    out->frameStride = ((size_t)out->surfacePitch * (size_t)h + 255) & ~(size_t)255;
-    out->framesPerChunk = FramesPerChunk(n, out->frameStride, budget);
-    out->chunks = (n + out->framesPerChunk - 1) / out->framesPerChunk;
-    return true;
+    return PlanChunks(n, (size_t)out->surfacePitch * (size_t)h, budget, out);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -331,14 +327,9 @@ bool PlanSampleCode(int dtype, int cformat, uint32_t element_bits, float scale, 
     return false;
 }
 
-bool PlanBatchSamples(int pitch, int h, int n, size_t budget, BatchSampleLayout *out)
+bool PlanBatchSamples(int pitch, int h, int n, size_t budget, ChunkLayout *out)
 {
-    if (n <= 0 || pitch < 1 || h < 1 || h > 32768) return false;
-    if (!budget) budget = kBatchYuvDefaultBudget;
-    out->frameStride = ((size_t)3 * (size_t)pitch * (size_t)h + 255) & ~(size_t)255;
-    out->framesPerChunk = FramesPerChunk(n, out->frameStride, budget);
-    out->chunks = (n + out->framesPerChunk - 1) / out->framesPerChunk;
-    return true;
+    return pitch >= 1 && h >= 1 && h <= 32768 && PlanChunks(n, (size_t)3 * (size_t)pitch * (size_t)h, budget, out);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -373,14 +364,9 @@ bool PlanDeintPlanes(int cformat, int w, int h, int pitch, int *planes, DeintPla
     return true;
 }
 
-bool PlanBatchDeint(int pitch, int lines, int nOut, size_t budget, BatchDeintLayout *out)
+bool PlanBatchDeint(int pitch, int lines, int nOut, size_t budget, ChunkLayout *out)
 {
-    if (nOut <= 0 || pitch < 1 || lines < 1) return false;
-    if (!budget) budget = kBatchYuvDefaultBudget;
-    out->frameStride = ((size_t)pitch * (size_t)lines + 255) & ~(size_t)255;
-    out->framesPerChunk = FramesPerChunk(nOut, out->frameStride, budget);
-    out->chunks = (nOut + out->framesPerChunk - 1) / out->framesPerChunk;
-    return true;
+    return pitch >= 1 && lines >= 1 && PlanChunks(nOut, (size_t)pitch * (size_t)lines, budget, out);
 }
 
 bool PlanEncode(int out_cformat, int src_fmt, uint32_t extfmt, int w, int h, EncodePlan *plan)

@@ -218,5 +218,18 @@ inline int FramesPerChunk(int n, size_t bytesPerFrame, size_t budget)
     const size_t fit = budget / (bytesPerFrame ? bytesPerFrame : 1);
     return (int)(fit < 1 ? 1 : fit > (size_t)n ? (size_t)n : fit);
 }
+// EXTENSION (include/mpcvr.h: mpcvr_plan_batch_yuv / _tensor / _from_tensors / _deint): how a batch call cuts n frames into chunks that go
+// through a context-owned surface.  Frame i of a chunk lies at i * frameStride (frameBytes rounded up to 256); n frames run as `chunks`
+// chunks of up to framesPerChunk, by the chunk rule under `budget` (0: the default).  false: n <= 0
+struct ChunkLayout { size_t frameStride; int32_t framesPerChunk, chunks; };
+constexpr size_t kBatchYuvDefaultBudget = (size_t)4 << 30;      // MPCVR_BATCH_YUV_DEFAULT_BUDGET (mpcvr_capi.cpp asserts they agree)
+inline bool PlanChunks(int n, size_t frameBytes, size_t budget, ChunkLayout *out)
+{
+    if (n <= 0) return false;
+    out->frameStride = (frameBytes + 255) & ~(size_t)255;
+    out->framesPerChunk = FramesPerChunk(n, out->frameStride, budget ? budget : kBatchYuvDefaultBudget);
+    out->chunks = (n + out->framesPerChunk - 1) / out->framesPerChunk;
+    return true;
+}
 
 }  // namespace mpcvr

@@ -40,7 +40,7 @@ struct TensorParams {
     const TensorFrame *frames;
 };
 // src and src_pitch multiples of 4, dst and its pitches multiples of the element size, the planes apart from each other and from the source
-// (the caller checks: TensorSurface, hip_video_processor.cpp); one launch for up to 65535 frames (the grid's z extent), one more per further 65535
+// (the caller checks: TensorSurface, hip_video_processor_ext.cpp); one launch for up to 65535 frames (the grid's z extent), one more per further 65535
 hipError_t LaunchTensor(const TensorParams &p, bool in10, int dtype, int layout, hipStream_t stream, int n_frames = 1);
 
 // ---- host only, no device work (vp_plan.cpp) ----

@@ -9,6 +9,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "vp_plan.h"
 #include "vp_tensor.h"
 
 namespace mpcvr {
@@ -39,7 +40,7 @@ struct SampleParams {
     const SampleFrame *frames;
 };
 // bytes: 1 (GBRP8) or 2 (GBRP10 / GBRP16) per component.  The caller has checked sizes, alignments and overlaps (SampleSurface,
-// hip_video_processor.cpp); one launch for up to 65535 frames (the grid's z extent), one more per further 65535
+// hip_video_processor_ext.cpp); one launch for up to 65535 frames (the grid's z extent), one more per further 65535
 hipError_t LaunchSampleFromTensor(const SampleParams &p, int dtype, int layout, int bytes, hipStream_t stream, int n_frames = 1);
 
 // ---- host only, no device work (vp_plan.cpp) ----
@@ -49,8 +50,7 @@ bool SampleFormat(int cformat, int *bytes, int *maxcode);
 // beyond 16 for a 16-bit dtype, a factor TensorFactorOk refuses
 bool PlanSampleCode(int dtype, int cformat, uint32_t element_bits, float scale, float bias, uint32_t *code);
 // the context-owned sample surface of mpcvr_process_batch_from_tensors: frame i of a chunk at i * frameStride (3 planes of pitch * h bytes,
-// rounded up to 256), chunks by the library's chunk rule (FramesPerChunk) under `budget` (0: kBatchYuvDefaultBudget)
-struct BatchSampleLayout { size_t frameStride; int32_t framesPerChunk, chunks; };
-bool PlanBatchSamples(int pitch, int h, int n, size_t budget, BatchSampleLayout *out);
+// rounded up to 256), chunks by PlanChunks (vp_plan.h) under `budget`
+bool PlanBatchSamples(int pitch, int h, int n, size_t budget, ChunkLayout *out);
 
 }  // namespace mpcvr
