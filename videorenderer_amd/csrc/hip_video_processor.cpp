@@ -766,7 +766,6 @@ void CHipVideoProcessor::FillFusedParams(const uint8_t *sample, void *rt, int rt
     static const bool no_baked = [] { const char *e = std::getenv("MPCVR_FUSED_NO_BAKED"); return e && *e && *e != '0'; }();     // (A/B: the kernel's own staging loops)
     fp->baked = (m_fusedTabValid && !no_baked) ? m_fusedTab.ptr : nullptr;
     fp->baked_lut = m_fusedTabLut;
-    fp->frames_host = nullptr;
     fp->dst_aligned16 = (((uintptr_t)rt) & 15) == 0;        // batches: ProcessBatch checks every target
     fp->src_aligned16 = (((uintptr_t)sample) & 15) == 0;
     // vectorised convert: dword loads need 4-byte aligned rows and a source rect starting on a 4-px boundary
@@ -881,7 +880,7 @@ HRESULT CHipVideoProcessor::ConvertColorPass(const uint8_t *sample, const RunOn 
     if (!(m_cfg.flags & MPCVR_FLAG_NO_FUSED)) {           // the fused kernel's block convert, when the source qualifies
         const FusedParams fp = ConvertOutputParams(sample, out.ptr, on.inflight);
         if (ConvertBlocksSupported(fp, false))
-            return CheckHip(LaunchConvertBlocks(fp, nullptr, FusedFrame{sample, out.ptr}, 1, on.stream), "k_convert_blocks");
+            return CheckHip(LaunchConvertBlocks(fp, LaunchFrames::One(sample, out.ptr), on.stream), "k_convert_blocks");
     }
     return CheckHip(LaunchConvert(P, out, on.stream, (m_cfg.flags & MPCVR_FLAG_NO_FUSED) != 0), "k_convert");
 }
@@ -914,8 +913,8 @@ HRESULT CHipVideoProcessor::ResizeShaderPass(const uint8_t *sample, void *rt, in
         // convert output (or RGB source texture) -> both draws -> final pass in the arbitrary-ratio fused kernel, no convert stage
         ssp.surf_stride = df.convStride;
         if (df.lastTab) ssp.fp.dst_aligned16 = df.aligned;
-        const FusedFrame one = df.lastTab ? FusedFrame{nullptr, nullptr} : FusedFrame{(const uint8_t *)conv.ptr, last.dst};
-        hr = CheckHip(LaunchFusedStrip(ssp, df.lastTab, one, df.n, on.stream), "k_fused_strip<surface>");
+        const LaunchFrames frames = df.lastTab ? LaunchFrames::Device(df.lastTab, df.n) : LaunchFrames::One((const uint8_t *)conv.ptr, last.dst);
+        hr = CheckHip(LaunchFusedStrip(ssp, frames, on.stream), "k_fused_strip<surface>");
     } else if (m_plan.two_pass && !plain && !m_tables.firstJinc && !m_tables.secondJinc && m_tables.firstAxis == 0 && !m_tables.firstSwap &&
         Resize2DSupported(conv, m_tapsX, m_tapsY, last)) {
         // both draws in one LDS-tiled kernel: m_TexResize stays on chip
@@ -1005,10 +1004,8 @@ HRESULT CHipVideoProcessor::ProcessOne(const uint8_t *sample, void *rt, int rtPi
         FillFusedParams(sample, rt, rtPitch, &fp, on.inflight);
         // UpdatePlan asked FusedUp2xSupported without a target (pitch 0): what depends on THIS call's target is asked here, as the strip and
         // same-size routes below ask it — rows that span 4 GiB go to the convert kernel and the resize draws, which store through size_t
-        if (StoreRowsFit32(fp.store, fp.out_h)) {
-            const FusedFrame fr{sample, rt};        // a single frame travels by value in the kernel arguments
-            return CheckHip(LaunchFusedUp2x(fp, nullptr, fr, 1, on.stream), "k_fused_up2x");
-        }
+        if (StoreRowsFit32(fp.store, fp.out_h))       // (a single frame travels by value in the kernel arguments)
+            return CheckHip(LaunchFusedUp2x(fp, LaunchFrames::One(sample, rt), on.stream), "k_fused_up2x");
         m_fusedAside = true;
     }
     if (m_strip) {
@@ -1019,7 +1016,7 @@ HRESULT CHipVideoProcessor::ProcessOne(const uint8_t *sample, void *rt, int rtPi
         const StoreParams last = m_plan.hdr_tonemap ? MakeStore(post.ptr, post.pitch, m_plan.internal_fmt, false) : final;
         FusedStripParams sp{};
         if (FillStripParams(sample, last.dst, last.dst_pitch, last, &sp, on.inflight)) {
-            if ((hr = CheckHip(LaunchFusedStrip(sp, nullptr, FusedFrame{sample, last.dst}, 1, on.stream), "k_fused_strip"))) return hr;
+            if ((hr = CheckHip(LaunchFusedStrip(sp, LaunchFrames::One(sample, last.dst), on.stream), "k_fused_strip"))) return hr;
             if (!m_plan.hdr_tonemap) return MPCVR_S_OK;
             return CheckHip(LaunchHdr10ToneMap(post, m_hdrTm, w2, h2, final, on.stream), "k_hdr10_tonemap");
         }
@@ -1029,7 +1026,7 @@ HRESULT CHipVideoProcessor::ProcessOne(const uint8_t *sample, void *rt, int rtPi
         FusedParams fp{};
         FillFusedParams(sample, rt, rtPitch, &fp, on.inflight);
         if (ConvertBlocksSupported(fp, true))
-            return CheckHip(LaunchConvertBlocks(fp, nullptr, FusedFrame{sample, rt}, 1, on.stream), "k_convert_blocks");
+            return CheckHip(LaunchConvertBlocks(fp, LaunchFrames::One(sample, rt), on.stream), "k_convert_blocks");
         ConvertParams P;
         FillConvertParams(sample, &P);
         return CheckHip(LaunchConvertDirect(P, MakeStore(rt, rtPitch, m_plan.swap_fmt, true), on.stream), "k_convert_direct");
@@ -1086,7 +1083,7 @@ HRESULT CHipVideoProcessor::ProcessFrame(void *pRenderTarget, int rtPitch, const
         // EXTENSION (bUseDither = 2): the draws render into the window-sized R10G10B10A2 intermediate, as for a 10-bit swap chain; the
         // error-diffusion pass takes it to the render target
         if (!(hr = PrepareErrDiff(1)) && !(hr = ProcessOne(m_curSample, m_edBase, m_edPitch, on)))
-            hr = ErrDiffPass(1, nullptr, FusedFrame{m_edBase, pRenderTarget}, rtPitch, on.stream);
+            hr = ErrDiffPass(LaunchFrames::One(m_edBase, pRenderTarget), rtPitch, on.stream);
     } else
         hr = ProcessOne(m_curSample, pRenderTarget, rtPitch, on);
     if (timeIt) (void)hipEventRecord(m_evStop, on.stream);
@@ -1253,20 +1250,13 @@ HRESULT CHipVideoProcessor::RunBatchRoute(BatchRoutePlan &rp, BatchRun &run)
         rp.direct.conv.dovi = rp.conv.conv.dovi = run.dvTab; rp.direct.dovi_cm = rp.conv.dovi_cm = run.dvCm;
     }
     SlotLease table;        // the batch's frame table, where it travels through the ring: on loan until the end of this function, behind the launches that read it
+    FusedFrame rows[kHostTableMax]; LaunchFrames frames;       // ... and where it travels in the kernel arguments (BatchFrames)
     switch (rp.route) {
     case BatchRoute::DirectConvert:
-        if (n <= kHostTableMax) {
-            // same-size frames: one convert launch with the frame table in its kernel arguments (32 frames for the block convert, 128 where the
-            // streaming kernel takes the launch — it answers hipErrorInvalidValue otherwise and the table is uploaded below)
-            FusedFrame tab[kHostTableMax];
-            for (int i = 0; i < n; i++) tab[i] = FusedFrame{(const uint8_t *)srcs[i], dsts[i]};
-            start();
-            const hipError_t e = LaunchConvertBlocks(rp.direct, nullptr, FusedFrame{nullptr, nullptr}, n, stream, 0, tab);
-            if (e != hipErrorInvalidValue || n <= 32) { hr = CheckHip(e, "k_convert_blocks"); break; }
-        }
-        if ((hr = UploadFrameTable(n, srcs, dsts, nullptr, 0, stream, &table))) break;
+        // same-size frames: one convert launch, the frame table in its kernel arguments where the kernel that takes the launch carries n rows
+        if ((hr = BatchFrames(n, srcs, dsts, ConvertBlocksByValueMax(rp.direct), stream, rows, &table, &frames))) break;
         start();
-        hr = CheckHip(LaunchConvertBlocks(rp.direct, table.frames(), FusedFrame{nullptr, nullptr}, n, stream), "k_convert_blocks");
+        hr = CheckHip(LaunchConvertBlocks(rp.direct, frames, stream), "k_convert_blocks");
         break;
     case BatchRoute::RgbSurfaceStrip: {
         // Interleaved RGB without a convert draw (m_PSConvColorData.bEnable false, :849-853): every frame is repacked into its own slot of a
@@ -1289,7 +1279,7 @@ HRESULT CHipVideoProcessor::RunBatchRoute(BatchRoutePlan &rp, BatchRun &run)
             const int m = std::min(chunk, n - at);
             hr = CheckHip(LaunchRepackRgb(m_srcParams->repack, nullptr, m_srcBottomUp ? -m_srcPitch : m_srcPitch, (uint8_t *)m_batchTex.ptr, tp,
                                           m_srcWidth, m_srcHeight, stream, srcs + at, m, texBytes), "k_repack_rgb");
-            if (!hr) hr = CheckHip(LaunchFusedStrip(rp.strip, table.frames() + at, FusedFrame{nullptr, nullptr}, m, stream), "k_fused_strip<surface>");
+            if (!hr) hr = CheckHip(LaunchFusedStrip(rp.strip, LaunchFrames::Device(table.frames() + at, m), stream), "k_fused_strip<surface>");
         }
         break;
     }
@@ -1311,7 +1301,7 @@ HRESULT CHipVideoProcessor::RunBatchRoute(BatchRoutePlan &rp, BatchRun &run)
             if ((hr = UploadFrameTable(m, srcs + at, nullptr, (uint8_t *)m_batchPost.ptr, postStride, stream, &drawTab))) break;
             if ((hr = UploadFrameTable(m, srcs + at, dsts + at, nullptr, 0, stream, &realTab))) break;
             ResizeBatch tb; tb.n = m; tb.in_stride = postStride; tb.frames = realTab.frames();
-            if (!(hr = CheckHip(LaunchFusedStrip(rp.strip, drawTab.frames(), FusedFrame{nullptr, nullptr}, m, stream), "k_fused_strip")))
+            if (!(hr = CheckHip(LaunchFusedStrip(rp.strip, LaunchFrames::Device(drawTab.frames(), m), stream), "k_fused_strip")))
                 hr = CheckHip(LaunchHdr10ToneMap(post, m_hdrTm, w2, h2, MakeStore(dsts[at], rtPitch, m_plan.swap_fmt, true), stream, &tb), "k_hdr10_tonemap");
         }
         break;
@@ -1335,22 +1325,17 @@ HRESULT CHipVideoProcessor::RunBatchRoute(BatchRoutePlan &rp, BatchRun &run)
         if ((hr = UploadFrameTable(n, srcs, dsts, nullptr, 0, stream, &table))) break;
         rp.strip.fp.dst_aligned16 = rp.aligned8 ? 1 : 0;
         start();
-        hr = CheckHip(LaunchFusedStrip(rp.strip, table.frames(), FusedFrame{nullptr, nullptr}, n, stream), "k_fused_strip");
+        hr = CheckHip(LaunchFusedStrip(rp.strip, LaunchFrames::Device(table.frames(), n), stream), "k_fused_strip");
         break;
     case BatchRoute::FusedUp2x: {
         FusedParams fp{};
         FillFusedParams((const uint8_t *)srcs[0], nullptr, rtPitch, &fp);
         fp.dst_aligned16 = rp.aligned ? 1 : 0;
-        // up to 32 frames travel in the exact-2x kernel's arguments: no table copy on the stream in front of the launch and no slot event
+        // the frames the exact-2x kernel carries travel in its arguments: no table copy on the stream in front of the launch and no slot event
         // behind it (the fused Jinc2m kernel, which LaunchFusedUp2x may launch instead, reads an uploaded table)
-        FusedFrame tab[32];
-        if (n <= 32 && !fp.jinc_tab) {
-            for (int i = 0; i < n; i++) tab[i] = FusedFrame{(const uint8_t *)srcs[i], dsts[i]};
-            fp.frames_host = tab;
-        } else if ((hr = UploadFrameTable(n, srcs, dsts, nullptr, 0, stream, &table))) break;
+        if ((hr = BatchFrames(n, srcs, dsts, FusedUp2xByValueMax(fp), stream, rows, &table, &frames))) break;
         start();
-        // (LaunchFusedUp2x wants a table for n > 1; with frames_host set no kernel is handed this pointer)
-        hr = CheckHip(LaunchFusedUp2x(fp, fp.frames_host ? tab : table.frames(), FusedFrame{nullptr, nullptr}, n, stream), "k_fused_up2x");
+        hr = CheckHip(LaunchFusedUp2x(fp, frames, stream), "k_fused_up2x");
         break;
     }
     }
@@ -1374,7 +1359,7 @@ HRESULT CHipVideoProcessor::PrepareErrDiff(int frames)
     return hr;
 }
 
-HRESULT CHipVideoProcessor::ErrDiffPass(int n, const FusedFrame *table, FusedFrame single, int rtPitch, hipStream_t s)
+HRESULT CHipVideoProcessor::ErrDiffPass(const LaunchFrames &frames, int rtPitch, hipStream_t s)
 {
     ErrDiffParams P{};
     P.x0 = std::max((int)m_videoRect.left, 0); P.y0 = std::max((int)m_videoRect.top, 0);
@@ -1396,16 +1381,16 @@ HRESULT CHipVideoProcessor::ErrDiffPass(int n, const FusedFrame *table, FusedFra
     if (*m_edStatus) { *m_edStatus = 0; return Fail(MPCVR_E_FAIL, "error diffusion: a band of an earlier pass gave up waiting for the band above"); }
     // the hand-off rows are cleared and rewritten by every launch: launches of one context run in stream order on one buffer
     if (s != m_stream) (void)hipStreamSynchronize(m_stream);
-    const size_t need = ErrorDiffusionHandoffBytes(P, n);
+    const size_t need = ErrorDiffusionHandoffBytes(P, frames.n);
     if ((hr = CheckHip(m_edHandoff.CheckCreate(need), "error-diffusion hand-off rows"))) return hr;
     P.handoff = (uint32_t *)m_edHandoff.ptr; P.status = m_edStatus;
     // the hand-off words carry the launch's generation: rows of the same layout need no clearing from launch to launch (600 MB for a 32-frame
     // batch of 8K frames); another layout, another buffer or a wrapped count: gen = 0 = the launcher clears them and starts at 1
     // (the layout is compared field by field — round 5 hashed it into 64 bits, and two layouts whose hashes met would have shared uncleared rows)
-    const EdLayout key{P.x0, P.x1, P.y0, P.y1, n, (const void *)P.handoff};
+    const EdLayout key{P.x0, P.x1, P.y0, P.y1, frames.n, (const void *)P.handoff};
     if (!(key == m_edKey) || m_edGen >= 4095 || m_edGen <= 0 || P.test_stall) { P.gen = 0; m_edGen = 1; m_edKey = P.test_stall ? EdLayout{} : key; }
     else P.gen = ++m_edGen;
-    return CheckHip(LaunchErrorDiffusion(P, table, single, n, s), "k_error_diffusion");
+    return CheckHip(LaunchErrorDiffusion(P, frames, s), "k_error_diffusion");
 }
 
 // a validated batch of an error-diffusion plan (RunBatch): chunks of frames through the routes into the intermediates, a pass behind each
@@ -1438,7 +1423,7 @@ HRESULT CHipVideoProcessor::ProcessBatchErrDiff(BatchRun &run)
         if (hr) return hr;
         SlotLease tab;
         if ((hr = UploadFrameTable(m, (const void *const *)mids.data(), run.dsts + at, nullptr, 0, m_stream, &tab))) return hr;
-        if ((hr = ErrDiffPass(m, tab.frames(), FusedFrame{nullptr, nullptr}, run.rtPitch, m_stream))) return hr;
+        if ((hr = ErrDiffPass(LaunchFrames::Device(tab.frames(), m), run.rtPitch, m_stream))) return hr;
     }
     (void)hipEventRecord(m_evStop, m_stream);       // (the batch's process time includes the pass)
     m_timed = true;
@@ -1486,6 +1471,20 @@ HRESULT CHipVideoProcessor::UploadFrameTable(int n, const void *const *srcs, voi
     return m_tableRing.SendRows<FusedFrame>(n, stream, "frame table", lease, [&](FusedFrame *fr) {
         for (int i = 0; i < n; i++) { fr[i].src = srcs ? (const uint8_t *)srcs[i] : nullptr; fr[i].dst = dsts ? dsts[i] : (void *)(dst_base + (size_t)i * dst_stride); }
     });
+}
+
+// The frames of a whole-batch launch that takes byValueMax rows in its kernel arguments (the launcher's own answer: ConvertBlocksByValueMax,
+// FusedUp2xByValueMax): up to that many go into `rows` (the caller's, kHostTableMax of them) and nothing is queued; more go through the table ring
+HRESULT CHipVideoProcessor::BatchFrames(int n, const void *const *srcs, void *const *dsts, int byValueMax, hipStream_t stream, FusedFrame *rows, SlotLease *lease, LaunchFrames *frames)
+{
+    if (n <= byValueMax) {
+        for (int i = 0; i < n; i++) rows[i] = FusedFrame{(const uint8_t *)srcs[i], dsts[i]};
+        *frames = LaunchFrames::Host(rows, n);
+        return MPCVR_S_OK;
+    }
+    const HRESULT hr = UploadFrameTable(n, srcs, dsts, nullptr, 0, stream, lease);
+    if (!hr) *frames = LaunchFrames::Device(lease->frames(), n);
+    return hr;
 }
 
 // The exact-2x kernel's tables as it keeps them in LDS, computed once per plan instead of by every workgroup of every launch
@@ -1604,7 +1603,7 @@ HRESULT CHipVideoProcessor::ProcessBatchLaunches(const BatchRun &run, const Fuse
         conv.store.dst = m_batchConv.ptr;
         const BatchRun part = run.Slice(at, m);
         if (part.dvTab) { conv.conv.dovi = part.dvTab; conv.dovi_cm = part.dvCm; }       // (the chunk's slice of the per-frame RPU tables)
-        if ((hr = CheckHip(LaunchConvertBlocks(conv, table + at, FusedFrame{nullptr, nullptr}, m, run.on.stream, m_convBytes), "k_convert_blocks"))) return hr;
+        if ((hr = CheckHip(LaunchConvertBlocks(conv, LaunchFrames::Device(table + at, m), run.on.stream, m_convBytes), "k_convert_blocks"))) return hr;
         df.n = m;
         df.rtTab = table + at;
         if (!hdr) df.lastTab = df.rtTab;

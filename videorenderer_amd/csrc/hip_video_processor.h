@@ -424,11 +424,13 @@ private:
     int m_edPitch = 0;             // bytes per row of an intermediate (a multiple of 256)
     size_t m_edStride = 0;         // bytes per intermediate
     HRESULT PrepareErrDiff(int frames);
-    HRESULT ErrDiffPass(int n, const FusedFrame *table, FusedFrame single, int rtPitch, hipStream_t s);
+    HRESULT ErrDiffPass(const LaunchFrames &frames, int rtPitch, hipStream_t s);
     HRESULT ProcessBatchErrDiff(BatchRun &run);
     size_t PostStride() const { return (m_postBytes + 255) & ~(size_t)255; }
     // a frame table in a slot of the ring (pinned copy + device copy): frame i = {srcs ? srcs[i] : null, dsts ? dsts[i] : dst_base + i * dst_stride}
     HRESULT UploadFrameTable(int n, const void *const *srcs, void *const *dsts, uint8_t *dst_base, size_t dst_stride, hipStream_t stream, SlotLease *lease);
+    // the frames {srcs[i], dsts[i]} of a launch that takes byValueMax rows in its arguments: in `rows` (kHostTableMax of them), or uploaded (*lease)
+    HRESULT BatchFrames(int n, const void *const *srcs, void *const *dsts, int byValueMax, hipStream_t stream, FusedFrame *rows, SlotLease *lease, LaunchFrames *frames);
     DevBuffer m_batchTex;          // interleaved RGB / v210 batches: the frames' m_TexSrcVideo copies side by side (ProcessBatch)
     bool m_texSrcZeroed = false, m_batchTexZeroed = false;     // the texels the RGB copy loops never write have been cleared for the current media type
     // Jinc2m phase tables of the first / second draw (null: weights per pixel)

@@ -268,16 +268,16 @@ static int ErrDiffResidentWaves()
     return cache[dev] = per_cu * cus;
 }
 
-hipError_t LaunchErrorDiffusion(const ErrDiffParams &P_in, const FusedFrame *frames_dev, FusedFrame single, int n_frames, hipStream_t s)
+hipError_t LaunchErrorDiffusion(const ErrDiffParams &P_in, const LaunchFrames &F, hipStream_t s)
 {
-    if (n_frames <= 0 || (!frames_dev && n_frames != 1)) return hipErrorInvalidValue;
+    if (!F.Valid(0)) return hipErrorInvalidValue;
     if (P_in.x1 <= P_in.x0 || P_in.y1 <= P_in.y0 || !P_in.handoff || !P_in.status) return hipErrorInvalidValue;
     ErrDiffParams P = P_in;
     if (P.spin_limit <= 0) P.spin_limit = 1 << 21;           // polls (~1 us each) a band grants the band above before it gives up and flags the launch
     const EdSchedule S = ed_schedule(P.x0, P.x1, P.y1 - P.y0);
     // the ticket counter starts at zero; the hand-off rows are cleared only when the caller does not vouch for them (gen = 0: no word of an
     // earlier launch on this buffer may carry the generation this launch tags its words with — then it runs as generation 1 on cleared rows)
-    const size_t rows_bytes = ErrorDiffusionHandoffBytes(P, n_frames) - 16 * sizeof(uint32_t);
+    const size_t rows_bytes = ErrorDiffusionHandoffBytes(P, F.n) - 16 * sizeof(uint32_t);
     hipError_t e = hipSuccess;
     if (P.gen <= 0 || P.gen > (int)kEdGenMask) { P.gen = 1; e = hipMemsetAsync(P.handoff, 0, rows_bytes + 16 * sizeof(uint32_t), s); }
     else e = hipMemsetAsync((uint8_t *)P.handoff + rows_bytes, 0, 16 * sizeof(uint32_t), s);
@@ -285,10 +285,10 @@ hipError_t LaunchErrorDiffusion(const ErrDiffParams &P_in, const FusedFrame *fra
     // as many wavefronts as the chip keeps resident (or as there are bands); each takes bands by ticket until none is left.  MPCVR_ERRDIFF_WAVES
     // overrides the number (A/B: fewer resident wavefronts = fewer bands sharing a SIMD)
     static const int waves_env = [] { const char *v = std::getenv("MPCVR_ERRDIFF_WAVES"); return v ? std::atoi(v) : 0; }();
-    const long total = (long)n_frames * S.bands;
+    const long total = (long)F.n * S.bands;
     const long want = waves_env > 0 ? waves_env : ErrDiffResidentWaves();
     const dim3 grid((unsigned)std::max<long>(1, std::min<long>(total, want))), block(64);
-    hipLaunchKernelGGL(k_error_diffusion, grid, block, 0, s, P, frames_dev, single, n_frames);
+    hipLaunchKernelGGL(k_error_diffusion, grid, block, 0, s, P, F.dev, F.one, F.n);
     return hipGetLastError();
 }
 

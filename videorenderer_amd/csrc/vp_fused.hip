@@ -452,6 +452,19 @@ void ChromaCatmullWeights(int chroma_loc, float wx[2][4], float wy[2][4])
     }
 }
 
+// FusedArgs::exact_cv of a launch — the exact form of the convert stage (convert_block_exact): an 8-bit internal format in front of a resize — there
+// a texel one code off the reference's comes out of a negative-lobe filter up to two codes off.  10-bit internal formats keep the fast form (the same
+// effect is a quarter of an 8-bit code), and so do the tails (their own transcendentals decide the last code) and Dolby Vision.
+static int ExactConvert(const FusedParams &P, int resize_follows)
+{
+    const ConvertParams &c = P.conv;
+    static const int exact8 = EnvInt("MPCVR_EXACT8", 1);          // 0: the fast form everywhere (A/B)
+    // ... and, round 5's last finding (the fuzz tool with the tier flags, seed 208, case 600): 10-bit internal formats too where an HDR10 tone-mapping
+    // operator follows — one code of the intermediate came out of operator 5 as five ten-bit codes
+    const bool exact_fmt = c.out_fmt == SF_BGRA8 || (P.exact_wide && c.out_fmt == SF_RGB10A2);
+    return (exact8 && ((resize_follows >= 0 ? resize_follows : P.exact_convert) || P.exact_wide) && exact_fmt && c.tail == TAIL_NONE && !c.dovi) ? 1 : 0;
+}
+
 // the convert-side and store-side constants both kernels of this file take
 void FillFusedArgs(const FusedParams &P, FusedArgs &a, int resize_follows)
 {
@@ -491,14 +504,7 @@ void FillFusedArgs(const FusedParams &P, FusedArgs &a, int resize_follows)
         a.m[3 * i + 2] = c.cm[3 * i + 2] * (dv ? 1.0f : sc);
         a.c[i] = c.cm[9 + i];
     }
-    // the exact form of the convert stage (convert_block_exact): an 8-bit internal format in front of a resize — there a texel one code off
-    // the reference's comes out of a negative-lobe filter up to two codes off.  10-bit internal formats keep the fast form (the same effect
-    // is a quarter of an 8-bit code), and so do the tails (their own transcendentals decide the last code) and Dolby Vision.
-    static const int exact8 = EnvInt("MPCVR_EXACT8", 1);          // 0: the fast form everywhere (A/B)
-    // ... and, round 5's last finding (the fuzz tool with the tier flags, seed 208, case 600): 10-bit internal formats too where an HDR10 tone-mapping
-    // operator follows — one code of the intermediate came out of operator 5 as five ten-bit codes
-    const bool exact_fmt = c.out_fmt == SF_BGRA8 || (P.exact_wide && c.out_fmt == SF_RGB10A2);
-    a.exact_cv = (exact8 && ((resize_follows >= 0 ? resize_follows : P.exact_convert) || P.exact_wide) && exact_fmt && c.tail == TAIL_NONE && !dv) ? 1 : 0;
+    a.exact_cv = ExactConvert(P, resize_follows);
     for (int i = 0; i < 9; i++) a.xm[i] = c.cm[i];
     for (int i = 0; i < 3; i++) a.xc[i] = c.cm[9 + i];
     {
@@ -611,49 +617,45 @@ static int ResidentWorkgroups(const void *kern, int threads, size_t lds)
     return memo[key] = n;
 }
 
-hipError_t LaunchConvertBlocks(const FusedParams &P, const FusedFrame *frames_dev, FusedFrame single, int n_frames, hipStream_t s,
-                               size_t batch_stride, const FusedFrame *frames_host)
+// Does the streaming kernel (k_convert_stream) take the block convert with these parameters?  Bi-planar 4:2:0 / 4:2:2 samples whose rows take
+// the lane's 4- / 8-byte loads and 16-byte stores.  exact_cv: FusedArgs::exact_cv of the launch.
+static bool ConvertStreams(const FusedParams &P, bool exact_cv)
+{
+    static const int no_stream = EnvInt("MPCVR_NO_STREAM_CONVERT", 0);
+    const ConvertParams &c = P.conv;
+    const int srck = FusedSourceKind(P);
+    const int lbs = srck == SRC_P01X ? 8 : 4;
+    // (the exact form of the convert stage — an 8-bit texture in front of an UNFUSED resize — is k_convert_blocks' alone: the streaming kernel is
+    // C1's, and the second form behind a branch cost it 8 registers and 15 % with the branch never taken)
+    return !no_stream && !(c.chroma_scaling == 2 && c.fmt.subsampling == 420) && FusedDoviKind(P) == DV_NONE && !exact_cv && (srck == SRC_P01X || srck == SRC_NV12) && c.out_w >= 8 && (c.out_w & 3) == 0 && (c.rect_l & 3) == 0 &&
+           (c.pitch[0] % lbs) == 0 && (c.pitch[1] % lbs) == 0 && (P.plane_off[1] % lbs) == 0 && P.dst_aligned16 && (P.store.off_x & 3) == 0 &&
+           (P.store.dst_pitch & 15) == 0 && P.src_aligned16;
+}
+
+int ConvertBlocksByValueMax(const FusedParams &P) { return ConvertStreams(P, ExactConvert(P, -1) != 0) ? TableRows<FrameTable128>() : TableRows<FrameTable32>(); }
+
+hipError_t LaunchConvertBlocks(const FusedParams &P, const LaunchFrames &F, hipStream_t s, size_t batch_stride)
 {
     uint8_t *batch_dst = batch_stride ? (uint8_t *)P.store.dst : nullptr;
-    // up to 32 frames travel in the kernel arguments (no table upload in front of the launch)
-    FrameTable32 tab;
-    tab.n = 0;
-    if (frames_host && n_frames <= 32) {
-        tab.n = n_frames;
-        for (int i = 0; i < n_frames; i++) tab.f[i] = frames_host[i];
-        for (int i = n_frames; i < 32; i++) tab.f[i] = FusedFrame{nullptr, nullptr};
-    } else if (!frames_dev && n_frames != 1 && !(frames_host && n_frames <= kHostTableMax)) return hipErrorInvalidValue;
     FusedArgs a;
     FillFusedArgs(P, a);
+    const bool stream = ConvertStreams(P, a.exact_cv != 0);
+    if (!F.Valid(stream ? TableRows<FrameTable128>() : TableRows<FrameTable32>())) return hipErrorInvalidValue;
     const ConvertParams &c = P.conv;
     const bool fin = P.store.mode == ST_FINAL;
     const int tailk = FusedTailKind(P), srck = FusedSourceKind(P);
     const int dvk = FusedDoviKind(P);
     const bool catmull = c.chroma_scaling == 2 && c.fmt.subsampling == 420;
-    // the streaming kernel (k_convert_stream): bi-planar 4:2:0 / 4:2:2 samples whose rows take the lane's 4- / 8-byte loads and 16-byte stores
-    static const int no_stream = EnvInt("MPCVR_NO_STREAM_CONVERT", 0);
-    const int lbs = srck == SRC_P01X ? 8 : 4;
-    // (the exact form of the convert stage — an 8-bit texture in front of an UNFUSED resize — is k_convert_blocks' alone: the streaming kernel is
-    // C1's, and the second form behind a branch cost it 8 registers and 15 % with the branch never taken)
-    const bool stream = !no_stream && !catmull && dvk == DV_NONE && !a.exact_cv && (srck == SRC_P01X || srck == SRC_NV12) && c.out_w >= 8 && (c.out_w & 3) == 0 && (c.rect_l & 3) == 0 &&
-                        (c.pitch[0] % lbs) == 0 && (c.pitch[1] % lbs) == 0 && (P.plane_off[1] % lbs) == 0 && P.dst_aligned16 && (P.store.off_x & 3) == 0 &&
-                        (P.store.dst_pitch & 15) == 0 && P.src_aligned16 && (frames_dev || frames_host || n_frames == 1);
-    if (!stream && !frames_dev && n_frames != 1 && !tab.n) return hipErrorInvalidValue;     // (a host table of more than 32 frames serves the streaming kernel only)
     if (stream) {
         FrameTable128 tab128;
-        tab128.n = 0;
-        if (frames_host && n_frames <= kHostTableMax) {
-            tab128.n = n_frames;
-            for (int i = 0; i < n_frames; i++) tab128.f[i] = frames_host[i];
-            for (int i = n_frames; i < kHostTableMax; i++) tab128.f[i] = FusedFrame{nullptr, nullptr};
-        }
+        F.ByValue(&tab128);
         const bool tables = fin || tail_has_table(tailk);
         const size_t lds = (fin ? 4096 : 0) + (tail_has_table(tailk) ? LDS_T : 0);
         StreamArgs q{};
         q.n_strips = (c.out_w + 255) / 256;
         q.npairs = c.out_h / 2 + 1;
-        q.n_frames = n_frames;
-        q.total = n_frames * q.npairs;
+        q.n_frames = F.n;
+        q.total = F.n * q.npairs;
         q.batch_dst = batch_dst; q.batch_stride = batch_stride;
         // workgroups of 8 waves where tables are staged (once per workgroup), of 4 otherwise; exactly the waves the chip keeps resident
         static const int wg_env = EnvInt("MPCVR_STREAM_WG_WAVES", 0), occ_env = EnvInt("MPCVR_STREAM_WG_PER_CU", 0), min_pairs_env = EnvInt("MPCVR_STREAM_MIN_PAIRS", 0);
@@ -666,7 +668,7 @@ hipError_t LaunchConvertBlocks(const FusedParams &P, const FusedFrame *frames_de
             const int min_pairs = min_pairs_env > 0 ? min_pairs_env : 4;            // a wave's run: at least this many row pairs (a short launch spreads thinner, not shorter)
             q.n_slots = (int)std::max<long>(1, std::min<long>(n_waves / q.n_strips, std::max(1, q.total / min_pairs)));
             const dim3 grid((unsigned)(((long)q.n_slots * q.n_strips + wgw - 1) / wgw), 1, 1);
-            hipLaunchKernelGGL(kern, grid, block, lds, s, a, frames_dev, single, q, tab128);
+            hipLaunchKernelGGL(kern, grid, block, lds, s, a, F.dev, F.one, q, tab128);
             err = hipGetLastError();
         };
 #define MPCVR_ST3(TK, SK, FN) launch(k_convert_stream<TK, SK, FN>)
@@ -681,6 +683,8 @@ hipError_t LaunchConvertBlocks(const FusedParams &P, const FusedFrame *frames_de
 #undef MPCVR_ST3
         return err;
     }
+    FrameTable32 tab;
+    F.ByValue(&tab);
     const int strips = (c.out_w + 127) / 128, npairs = c.out_h / 2 + 1;
     // row pairs per wave: enough waves to fill the chip a few times over, few enough to amortise the table staging
     int pairs = 16;
@@ -690,12 +694,12 @@ hipError_t LaunchConvertBlocks(const FusedParams &P, const FusedFrame *frames_de
     // with 4 k waves per launch, 284 k with 64 k)
     const bool tables = fin || tail_has_table(tailk) || dvk != DV_NONE;
     const long want_waves = pairs_waves > 0 ? pairs_waves : tables ? 8192 : 65536;
-    while (pairs > 2 && (long)strips * ((npairs + pairs - 1) / pairs) * n_frames < want_waves) pairs >>= 1;
+    while (pairs > 2 && (long)strips * ((npairs + pairs - 1) / pairs) * F.n < want_waves) pairs >>= 1;
     const int wg_waves = dvk == DV_SDR_L2 ? 8 : 4;         // (k_convert_blocks: NTH)
-    const dim3 grid(strips, (npairs + wg_waves * pairs - 1) / (wg_waves * pairs), n_frames), block(64 * wg_waves, 1, 1);
+    const dim3 grid(strips, (npairs + wg_waves * pairs - 1) / (wg_waves * pairs), F.n), block(64 * wg_waves, 1, 1);
     const size_t lds = (fin ? 4096 : 0) + (dvk != DV_NONE ? LDS_E + LDS_V + (dvk == DV_SDR_L2 ? LDS_T + LDS_PE : 0) : tail_has_table(tailk) ? LDS_T : 0);
     if (dvk != DV_NONE) {       // Dolby Vision: 16-bit bi-planar (P010 / P016) or whatever the generic source variant reads
-#define MPCVR_CBD(SK, FN, DK) hipLaunchKernelGGL((k_convert_blocks<TAILK_ALU, SK, FN, DK>), grid, block, lds, s, a, frames_dev, single, pairs, batch_dst, batch_stride, tab)
+#define MPCVR_CBD(SK, FN, DK) hipLaunchKernelGGL((k_convert_blocks<TAILK_ALU, SK, FN, DK>), grid, block, lds, s, a, F.dev, F.one, pairs, batch_dst, batch_stride, tab)
 #define MPCVR_CBD2(SK, FN) do { if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)k_convert_blocks<TAILK_ALU, SK, FN, DV_SDR_L2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
                                 if (dvk == DV_SDR) MPCVR_CBD(SK, FN, DV_SDR); else if (dvk == DV_SDR_L2) MPCVR_CBD(SK, FN, DV_SDR_L2); else MPCVR_CBD(SK, FN, DV_GENERAL); } while (0)
         if (srck == SRC_P01X) { if (fin) MPCVR_CBD2(SRC_P01X, true); else MPCVR_CBD2(SRC_P01X, false); }
@@ -704,8 +708,8 @@ hipError_t LaunchConvertBlocks(const FusedParams &P, const FusedFrame *frames_de
 #undef MPCVR_CBD
         return hipGetLastError();
     }
-#define MPCVR_CB3(TK, SK, FN) do { if (catmull) hipLaunchKernelGGL((convert_blocks_kernel<TK, SK, FN, 1>(a.exact_cv != 0)), grid, block, lds, s, a, frames_dev, single, pairs, batch_dst, batch_stride, tab); \
-                                   else hipLaunchKernelGGL((convert_blocks_kernel<TK, SK, FN, 0>(a.exact_cv != 0)), grid, block, lds, s, a, frames_dev, single, pairs, batch_dst, batch_stride, tab); } while (0)
+#define MPCVR_CB3(TK, SK, FN) do { if (catmull) hipLaunchKernelGGL((convert_blocks_kernel<TK, SK, FN, 1>(a.exact_cv != 0)), grid, block, lds, s, a, F.dev, F.one, pairs, batch_dst, batch_stride, tab); \
+                                   else hipLaunchKernelGGL((convert_blocks_kernel<TK, SK, FN, 0>(a.exact_cv != 0)), grid, block, lds, s, a, F.dev, F.one, pairs, batch_dst, batch_stride, tab); } while (0)
 #define MPCVR_CB2(TK, SK) do { if (fin) MPCVR_CB3(TK, SK, true); else MPCVR_CB3(TK, SK, false); } while (0)
 #define MPCVR_CB(TK) do { if (srck == SRC_P01X) MPCVR_CB2(TK, SRC_P01X); else if (srck == SRC_PLANAR16) MPCVR_CB2(TK, SRC_PLANAR16); else MPCVR_CB2(TK, SRC_GENERIC); } while (0)
     if (tailk == TAILK_NONE) {          // (the 8-bit loaders exist without a tail only: FusedSourceKind)
@@ -723,14 +727,14 @@ hipError_t LaunchConvertBlocks(const FusedParams &P, const FusedFrame *frames_de
 #ifndef MPCVR_UP2X_WAVES_HOST
 #define MPCVR_UP2X_WAVES_HOST 3     // = MPCVR_UP2X_WAVES of vp_fused_up2x.h: waves per SIMD the fused 2x kernel is allocated for
 #endif
-hipError_t LaunchFusedUp2x(const FusedParams &P, const FusedFrame *frames_dev, FusedFrame single, int n_frames, hipStream_t s)
+hipError_t LaunchFusedUp2x(const FusedParams &P, const LaunchFrames &F, hipStream_t s)
 {
     static const int seg_env = EnvInt("MPCVR_FUSED_SEG", 0);
-    if (!frames_dev && n_frames != 1) return hipErrorInvalidValue;
+    if (!F.Valid(FusedUp2xByValueMax(P))) return hipErrorInvalidValue;
     const ConvertParams &c = P.conv;
     FusedArgs a;
     FillFusedArgs(P, a, 1);
-    if (P.jinc_tab) return LaunchFusedJinc2x(P, a, P.jinc_tab, frames_dev, single, n_frames, s);
+    if (P.jinc_tab) return LaunchFusedJinc2x(P, a, P.jinc_tab, F, s);
     const int nt = P.wx.ntaps;
     for (int t = 0; t < 6; t++) { a.we[t] = P.wx.w_even[t]; a.wo[t] = P.wx.w_odd[t]; }
     int knt = nt;
@@ -749,12 +753,12 @@ hipError_t LaunchFusedUp2x(const FusedParams &P, const FusedFrame *frames_dev, F
         seg = 72;
         // frames that run side by side (a batch, or single frames on the context's lanes) share the chip: a batch aims at >= 4 rounds of
         // the ~3072 resident waves, overlapping single frames at a round and a quarter between them — the fewest, longest segments that still fill it
-        const long side = (long)n_frames * (P.inflight > 1 ? P.inflight : 1);
+        const long side = (long)F.n * (P.inflight > 1 ? P.inflight : 1);
         // (single frames on four lanes, one box: 72-row segments 19.9 k frames/s, 60: 19.7 k, 90: 19.2 k, 120: 17.8 k, 180: 14.2 k — 3,840 waves)
-        const long want = n_frames > 1 ? 12288 : 3840;
+        const long want = F.n > 1 ? 12288 : 3840;
         for (int cand : {180, 144, 120, 108, 90, 72, 60, 48, 36, 24})
             if ((long)strips * ((c.out_h + cand - 1) / cand) * side >= want || cand == 24) { seg = cand; break; }
-        if (n_frames > 1) {
+        if (F.n > 1) {
             // A batch starts together and runs in rounds of the resident waves (3 per SIMD): a half-empty last round costs a whole one, and every
             // segment walks 6 rows of run-in.  Cost of a candidate = rounds x (rows + 6); the longest segment among the cheapest.  32 frames of
             // 1080p: 180 rows = 3,072 items = ONE round, 96.2 k frames/s (C2) where the rule above took 36 rows (5 rounds, 17 % run-in): 87.9 k.
@@ -776,9 +780,9 @@ hipError_t LaunchFusedUp2x(const FusedParams &P, const FusedFrame *frames_dev, F
     // than the packed-fp32 chains on this part (profiles/r03/mfma_overlap_ubench.txt: the matrix pipe does not overlap v_pk_fma_f32), 16
     // instantiations and half a CPU-minute of build; its source is kept under profiles/r06/experiments/matrix_core_taps/.  The flag is accepted
     // and ignored.)
-    if (knt == 4) return LaunchFusedUp2xNT<4>(P, a, strips, seg, frames_dev, single, n_frames, s);
-    if (knt == 5) return LaunchFusedUp2xNT<5>(P, a, strips, seg, frames_dev, single, n_frames, s);
-    return LaunchFusedUp2xNT<6>(P, a, strips, seg, frames_dev, single, n_frames, s);
+    if (knt == 4) return LaunchFusedUp2xNT<4>(P, a, strips, seg, F, s);
+    if (knt == 5) return LaunchFusedUp2xNT<5>(P, a, strips, seg, F, s);
+    return LaunchFusedUp2xNT<6>(P, a, strips, seg, F, s);
 }
 
 }  // namespace mpcvr

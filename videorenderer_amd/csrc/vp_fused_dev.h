@@ -1140,14 +1140,14 @@ int FusedDoviKind(const FusedParams &P);          // DV_* for the launch
 hipError_t AllowLargeLds(const void *kern, size_t lds);
 int DeviceCuCount();        // vp_fused.hip: compute units of the current device (256)
 // vp_fused_jinc.hip: the fused 2x launch with the 2-D Jinc2m filter in the place of the two separable draws (`a` complete but for seg_rows)
-hipError_t LaunchFusedJinc2x(const FusedParams &P, const FusedArgs &a, const float *jtab_dev, const FusedFrame *frames_dev, FusedFrame single, int n_frames, hipStream_t s);
+hipError_t LaunchFusedJinc2x(const FusedParams &P, const FusedArgs &a, const float *jtab_dev, const LaunchFrames &F, hipStream_t s);
 // LDS a workgroup of the current device may claim with that attribute (gfx950: 160 KiB): queried once per device, so a part or
 // partition with less makes the planners fall back at plan time instead of failing at launch; 160 KiB where no device answers
 size_t DeviceLdsLimit();
 // vp_fused_period.hip: the periodic-phase kernel for this strip launch, or hipErrorNotSupported (LaunchFusedStrip then runs k_fused_strip)
-hipError_t LaunchFusedPeriod(const FusedStripParams &S, const FusedArgs &a, const FusedFrame *frames_dev, FusedFrame single, int n_frames, hipStream_t s);
+hipError_t LaunchFusedPeriod(const FusedStripParams &S, const FusedArgs &a, const LaunchFrames &F, hipStream_t s);
 // vp_fused_up2x.h, instantiated by vp_fused_up2x_nt{4,5,6}.hip: the packed-fp32 kernel for one tap count
 template <int NT>
-hipError_t LaunchFusedUp2xNT(const FusedParams &P, const FusedArgs &a, int strips, int seg, const FusedFrame *frames_dev, FusedFrame single, int n_frames, hipStream_t s);
+hipError_t LaunchFusedUp2xNT(const FusedParams &P, const FusedArgs &a, int strips, int seg, const LaunchFrames &F, hipStream_t s);
 
 }  // namespace mpcvr

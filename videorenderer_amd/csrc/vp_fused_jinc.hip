@@ -365,7 +365,7 @@ void BuildFusedJincTable(const void *phases, float *out)
 }
 
 // `a` is complete but for seg_rows; jtab_dev: FusedJincTableBytes() on the device
-hipError_t LaunchFusedJinc2x(const FusedParams &P, const FusedArgs &a_in, const float *jtab_dev, const FusedFrame *frames_dev, FusedFrame single, int n_frames, hipStream_t s)
+hipError_t LaunchFusedJinc2x(const FusedParams &P, const FusedArgs &a_in, const float *jtab_dev, const LaunchFrames &F, hipStream_t s)
 {
     static const int seg_env = EnvInt("MPCVR_JINC_SEG", 0);
     const ConvertParams &c = P.conv;
@@ -377,7 +377,7 @@ hipError_t LaunchFusedJinc2x(const FusedParams &P, const FusedArgs &a_in, const 
         // One workgroup per CU (LDS), so a launch runs in rounds of CUs x 12 waves and a last round that is half empty costs a whole one
         // (32 frames of 1080p: 90-row segments = 6,144 items = 2 rounds: 45.7 k frames/s; 120 rows = 1.5 rounds: 35.7 k; 72 rows = 2.5: 39.0 k).
         // Cost of a candidate = rounds x rows an item walks (its segment + 7 rows of run-in); the longest segment among the cheapest.
-        const long side = (long)n_frames * (P.inflight > 1 ? P.inflight : 1);
+        const long side = (long)F.n * (P.inflight > 1 ? P.inflight : 1);
         const long resident = (long)DeviceCuCount() * jw;
         long best = -1;
         for (int cand : {180, 144, 120, 108, 90, 72, 60, 48, 36, 24}) {
@@ -389,7 +389,7 @@ hipError_t LaunchFusedJinc2x(const FusedParams &P, const FusedArgs &a_in, const 
     seg = (seg + 1) & ~1;
     if (seg > c.out_h) seg = c.out_h;
     a.seg_rows = seg;
-    const dim3 grid((strips * ((c.out_h + seg - 1) / seg) + jw - 1) / jw, 1, n_frames), block(64 * jw, 1, 1);
+    const dim3 grid((strips * ((c.out_h + seg - 1) / seg) + jw - 1) / jw, 1, F.n), block(64 * jw, 1, 1);
     const size_t lds = FusedJincLdsBytes(P);
     if (lds > DeviceLdsLimit()) return hipErrorInvalidValue;            // (UpdatePlan does not pick this route then)
     const bool aligned = P.dst_aligned16 && (a.off_x & 3) == 0 && (a.dst_pitch & 15) == 0;
@@ -403,7 +403,7 @@ hipError_t LaunchFusedJinc2x(const FusedParams &P, const FusedArgs &a_in, const 
 #define MPCVR_JL3(TK, SK, EK) do { \
         auto kern = fused_jinc2x_kernel<TK, SK, EK>(a.exact_cv != 0); \
         if (lds > 48 * 1024) { const hipError_t ea = AllowLargeLds((const void *)kern, lds); if (ea != hipSuccess) return ea; } \
-        hipLaunchKernelGGL(kern, grid, block, lds, s, a, jtab_dev, frames_dev, single); } while (0)
+        hipLaunchKernelGGL(kern, grid, block, lds, s, a, jtab_dev, F.dev, F.one); } while (0)
 #define MPCVR_JL(TK) do { \
         if (srck == SRC_P01X && epik == EPI_DITHER8) MPCVR_JL3(TK, SRC_P01X, EPI_DITHER8); \
         else if (srck == SRC_P01X) MPCVR_JL3(TK, SRC_P01X, EPI_GENERIC); \

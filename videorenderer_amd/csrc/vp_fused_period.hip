@@ -58,7 +58,7 @@ bool FusedPeriodTakes(const FusedStripParams &S)
 }
 
 // the same launch contract as LaunchFusedStrip (which calls this first); hipErrorNotSupported = not this kernel's case
-hipError_t LaunchFusedPeriod(const FusedStripParams &S, const FusedArgs &a_in, const FusedFrame *frames_dev, FusedFrame single, int n_frames, hipStream_t s)
+hipError_t LaunchFusedPeriod(const FusedStripParams &S, const FusedArgs &a_in, const LaunchFrames &F, hipStream_t s)
 {
     if (!FusedPeriodTakes(S)) return hipErrorNotSupported;
     const FusedParams &P = S.fp;
@@ -80,7 +80,7 @@ hipError_t LaunchFusedPeriod(const FusedStripParams &S, const FusedArgs &a_in, c
     q.n_strips = (S.out_w + q.strip_w - 1) / q.strip_w;
     q.acols = S.per_acols;
     if (S.surface_mode) {
-        q.surf = n_frames > 1 || !single.src ? (const uint8_t *)S.surf.ptr : nullptr;      // a batch reads surf + z * stride; one frame: single.src
+        q.surf = F.n > 1 || !F.one.src ? (const uint8_t *)S.surf.ptr : nullptr;      // a batch reads surf + z * stride; one frame: F.one.src
         q.surf_fmt = S.surf.fmt; q.surf_pitch = S.surf.pitch; q.surf_w = S.surf.w; q.surf_stride = S.surf_stride; q.other = S.other;
     }
     // segment height (a multiple of the body's PB output rows): long segments recompute less (the taps' span each), short ones fill the chip
@@ -88,10 +88,10 @@ hipError_t LaunchFusedPeriod(const FusedStripParams &S, const FusedArgs &a_in, c
     int seg = seg_env;
     if (seg <= 0) {
         seg = 2 * PB;
-        const long side = (long)n_frames * (P.inflight > 1 ? P.inflight : 1);       // frames sharing the chip: a batch, or single frames on the context's lanes
+        const long side = (long)F.n * (P.inflight > 1 ? P.inflight : 1);       // frames sharing the chip: a batch, or single frames on the context's lanes
         // two rounds of the 4096 resident waves are enough: longer segments recompute less than a third round balances (round 4, same box:
         // 1080p -> 1440p 93.3 k frames/s at 64 rows (14,720 waves), 99.2 k at 96 (9,600), 85.3 k at 192 (5,120); 4K -> 1440p flat from 48 to 192)
-        const long want = n_frames > 1 ? 8192 : 4096;
+        const long want = F.n > 1 ? 8192 : 4096;
         for (int cand : {24, 16, 12, 8, 6, 4, 3, 2})
             if ((long)q.n_strips * ((S.out_h + cand * PB - 1) / (cand * PB)) * side >= want || cand == 2) { seg = cand * PB; break; }
     }
@@ -115,15 +115,15 @@ hipError_t LaunchFusedPeriod(const FusedStripParams &S, const FusedArgs &a_in, c
         }
     }
     while (waves > 1 && PeriodLds(S, fastepi, lut, waves) > DeviceLdsLimit()) waves--;
-    const long items = (long)q.n_strips * n_segs * n_frames;
+    const long items = (long)q.n_strips * n_segs * F.n;
     if (items < 512L * waves) waves = (int)std::max<long>(1, std::min<long>(waves, items / 512));
     const size_t lds = PeriodLds(S, fastepi, lut, waves);
-    const dim3 grid((q.n_strips * n_segs + waves - 1) / waves, 1, n_frames), block(64 * waves, 1, 1);
-    if (S.per_P == 4 && S.per_Q == 3) return LaunchFusedPeriodPQ<4, 3>(a, q, S.per_nt, tailk, srck, epik, grid, block, lds, frames_dev, single, s);
-    if (S.per_P == 3 && S.per_Q == 2) return LaunchFusedPeriodPQ<3, 2>(a, q, S.per_nt, tailk, srck, epik, grid, block, lds, frames_dev, single, s);
-    if (S.per_P == 2 && S.per_Q == 3) return LaunchFusedPeriodPQ<2, 3>(a, q, S.per_nt, tailk, srck, epik, grid, block, lds, frames_dev, single, s);
-    if (S.per_P == 1 && S.per_Q == 2) return LaunchFusedPeriodPQ<1, 2>(a, q, S.per_nt, tailk, srck, epik, grid, block, lds, frames_dev, single, s);
-    if (S.per_P == 3 && S.per_Q == 1) return LaunchFusedPeriodPQ<3, 1>(a, q, S.per_nt, tailk, srck, epik, grid, block, lds, frames_dev, single, s);
+    const dim3 grid((q.n_strips * n_segs + waves - 1) / waves, 1, F.n), block(64 * waves, 1, 1);
+    if (S.per_P == 4 && S.per_Q == 3) return LaunchFusedPeriodPQ<4, 3>(a, q, S.per_nt, tailk, srck, epik, grid, block, lds, F.dev, F.one, s);
+    if (S.per_P == 3 && S.per_Q == 2) return LaunchFusedPeriodPQ<3, 2>(a, q, S.per_nt, tailk, srck, epik, grid, block, lds, F.dev, F.one, s);
+    if (S.per_P == 2 && S.per_Q == 3) return LaunchFusedPeriodPQ<2, 3>(a, q, S.per_nt, tailk, srck, epik, grid, block, lds, F.dev, F.one, s);
+    if (S.per_P == 1 && S.per_Q == 2) return LaunchFusedPeriodPQ<1, 2>(a, q, S.per_nt, tailk, srck, epik, grid, block, lds, F.dev, F.one, s);
+    if (S.per_P == 3 && S.per_Q == 1) return LaunchFusedPeriodPQ<3, 1>(a, q, S.per_nt, tailk, srck, epik, grid, block, lds, F.dev, F.one, s);
     return hipErrorNotSupported;
 }
 

@@ -105,9 +105,9 @@ hipError_t AllowLargeLds(const void *kern, size_t lds)
     return e;
 }
 
-hipError_t LaunchFusedStrip(const FusedStripParams &S, const FusedFrame *frames_dev, FusedFrame single, int n_frames, hipStream_t s)
+hipError_t LaunchFusedStrip(const FusedStripParams &S, const LaunchFrames &F, hipStream_t s)
 {
-    if (!frames_dev && n_frames != 1) return hipErrorInvalidValue;
+    if (!F.Valid(0)) return hipErrorInvalidValue;
     const FusedParams &P = S.fp;
     FusedArgs a;
     if (S.surface_mode) {       // store-side constants only: there is no convert stage
@@ -124,7 +124,7 @@ hipError_t LaunchFusedStrip(const FusedStripParams &S, const FusedFrame *frames_
         a.H = S.mid_h; a.W = S.surf.w;
     } else FillFusedArgs(P, a, 1);
     if (S.per_P) {       // a periodic vertical ratio: the register-window kernel when the launch meets its preconditions
-        const hipError_t ep = LaunchFusedPeriod(S, a, frames_dev, single, n_frames, s);
+        const hipError_t ep = LaunchFusedPeriod(S, a, F, s);
         if (ep != hipErrorNotSupported) { if (S.ran_period) *S.ran_period = 1; return ep; }
     }
     if (S.ran_period) *S.ran_period = 0;
@@ -138,7 +138,7 @@ hipError_t LaunchFusedStrip(const FusedStripParams &S, const FusedFrame *frames_
     q.acols = S.acols;
     q.a_scale = 16777216.0f / a.maxv;
     if (S.surface_mode) {
-        q.surf = n_frames > 1 || !single.src ? (const uint8_t *)S.surf.ptr : nullptr;      // a batch reads surf + z * stride; one frame: single.src
+        q.surf = F.n > 1 || !F.one.src ? (const uint8_t *)S.surf.ptr : nullptr;      // a batch reads surf + z * stride; one frame: F.one.src
         q.other = S.other; q.surf_fmt = S.surf.fmt; q.surf_pitch = S.surf.pitch; q.surf_w = S.surf.w; q.surf_stride = S.surf_stride;
         q.a_scale = S.surf.fmt == SF_RGBA16F ? 1.0f : 16777216.0f / (S.surf.fmt == SF_RGB10A2 ? 1023.0f : 255.0f);
     }
@@ -147,8 +147,8 @@ hipError_t LaunchFusedStrip(const FusedStripParams &S, const FusedFrame *frames_
     int seg = seg_env;
     if (seg <= 0) {
         seg = 16;
-        const long side = (long)n_frames * (P.inflight > 1 ? P.inflight : 1);       // frames sharing the chip: a batch, or single frames on the context's lanes
-        const long want = n_frames > 1 ? 12288 : 4096;
+        const long side = (long)F.n * (P.inflight > 1 ? P.inflight : 1);       // frames sharing the chip: a batch, or single frames on the context's lanes
+        const long want = F.n > 1 ? 12288 : 4096;
         for (int cand : {192, 128, 96, 64, 48, 32, 24, 16})
             if ((long)q.n_strips * ((S.out_h + cand - 1) / cand) * side >= want || cand == 16) { seg = cand; break; }
     }
@@ -165,16 +165,16 @@ hipError_t LaunchFusedStrip(const FusedStripParams &S, const FusedFrame *frames_
     // waves per workgroup: as many as LDS allows for a launch that fills the chip several times over; a small launch (one frame) is
     // spread over all CUs instead — 1,800 work items in 16-wave workgroups occupy 113 of 256 CUs, four waves deep
     int waves = StripWaves(S, fastepi, tail_has_table(tailk));
-    const long items = (long)q.n_strips * n_segs * n_frames;
+    const long items = (long)q.n_strips * n_segs * F.n;
     if (items < 512L * waves) waves = (int)std::max<long>(1, std::min<long>(waves, items / 512));
     const size_t lds = StripLds(S, fastepi, tail_has_table(tailk), waves);
-    const dim3 grid((q.n_strips * n_segs + waves - 1) / waves, 1, n_frames), block(64 * waves, 1, 1);
+    const dim3 grid((q.n_strips * n_segs + waves - 1) / waves, 1, F.n), block(64 * waves, 1, 1);
     const int epi = fastepi ? STRIP_EPI_FAST : direct ? STRIP_EPI_DIRECT : STRIP_EPI_GENERIC;
     switch (S.nt) {
-    case 4: return LaunchFusedStripNT<4>(a, q, st, S.pxl, tailk, srck, epi, S.surface_mode != 0, grid, block, lds, frames_dev, single, s);
-    case 6: return LaunchFusedStripNT<6>(a, q, st, S.pxl, tailk, srck, epi, S.surface_mode != 0, grid, block, lds, frames_dev, single, s);
-    case 8: return LaunchFusedStripNT<8>(a, q, st, S.pxl, tailk, srck, epi, S.surface_mode != 0, grid, block, lds, frames_dev, single, s);
-    case 16: return LaunchFusedStripNT<16>(a, q, st, S.pxl, tailk, srck, epi, S.surface_mode != 0, grid, block, lds, frames_dev, single, s);
+    case 4: return LaunchFusedStripNT<4>(a, q, st, S.pxl, tailk, srck, epi, S.surface_mode != 0, grid, block, lds, F.dev, F.one, s);
+    case 6: return LaunchFusedStripNT<6>(a, q, st, S.pxl, tailk, srck, epi, S.surface_mode != 0, grid, block, lds, F.dev, F.one, s);
+    case 8: return LaunchFusedStripNT<8>(a, q, st, S.pxl, tailk, srck, epi, S.surface_mode != 0, grid, block, lds, F.dev, F.one, s);
+    case 16: return LaunchFusedStripNT<16>(a, q, st, S.pxl, tailk, srck, epi, S.surface_mode != 0, grid, block, lds, F.dev, F.one, s);
     }
     return hipErrorNotSupported;
 }

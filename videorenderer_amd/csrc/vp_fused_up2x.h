@@ -374,10 +374,10 @@ inline auto fused_up2x_kernel(bool exact) -> decltype(&k_fused_up2x<NT, TAIL, SR
 
 // grid / LDS / (source, epilogue, tail) dispatch of one tap count; `a` is complete (FillFusedArgs + weights + seg_rows)
 template <int NT>
-hipError_t LaunchFusedUp2xNT(const FusedParams &P, const FusedArgs &a_in, int strips, int seg, const FusedFrame *frames_dev, FusedFrame single, int n_frames, hipStream_t s)
+hipError_t LaunchFusedUp2xNT(const FusedParams &P, const FusedArgs &a_in, int strips, int seg, const LaunchFrames &F, hipStream_t s)
 {
     const ConvertParams &c = P.conv;
-    const dim3 grid((strips + WAVES - 1) / WAVES, (c.out_h + seg - 1) / seg, n_frames);
+    const dim3 grid((strips + WAVES - 1) / WAVES, (c.out_h + seg - 1) / seg, F.n);
     const dim3 block(256, 1, 1);
     const int tailk = FusedTailKind(P);
     static const int lds_pad = EnvInt("MPCVR_FUSED_LDS_PAD", 0);   // experiments: lower the occupancy by claiming more LDS
@@ -387,14 +387,10 @@ hipError_t LaunchFusedUp2xNT(const FusedParams &P, const FusedArgs &a_in, int st
     // the table image is staged instead of the tables' sources when it was baked from this launch's tone-map table (or the kernel reads none)
     const unsigned char *baked = (P.baked && (((uintptr_t)P.baked) & 15) == 0 && (!tail_has_table(tailk) || (P.baked_lut && P.baked_lut == a.lut)))
                                      ? (const unsigned char *)P.baked : nullptr;
-    // up to 32 frames by value: a host table, or the single frame as entry 0; the kernel reads frames_dev only where it is handed one
+    // (F is valid: LaunchFusedUp2x)  By value: host rows, or the single frame as entry 0; the kernel reads F.dev only where it is handed one
     FrameTable32 tab{};
-    if (n_frames <= 32 && (P.frames_host || !frames_dev)) {
-        if (!P.frames_host && n_frames != 1) return hipErrorInvalidValue;
-        tab.n = n_frames;
-        for (int i = 0; i < n_frames; i++) tab.f[i] = P.frames_host ? P.frames_host[i] : single;
-        frames_dev = nullptr;
-    } else if (!frames_dev) return hipErrorInvalidValue;
+    if (F.host) F.ByValue(&tab);
+    else if (!F.dev) { tab.n = 1; tab.f[0] = F.one; }
     // the specialised epilogues use 16-byte stores / dither reads: off_x % 4 == 0 and 16-byte aligned rows; the integer
     // final pass additionally needs k*M + (j << 14) < 2^32 and M < 2^24 (true for 10-bit internal -> 8-bit target)
     const bool aligned = P.dst_aligned16 && (a.off_x & 3) == 0 && (a.dst_pitch & 15) == 0;
@@ -403,7 +399,7 @@ hipError_t LaunchFusedUp2xNT(const FusedParams &P, const FusedArgs &a_in, int st
                    : (!a.final_pass && P.store.dst_fmt == SF_BGRA8 && P.store.quant == 255) ? EPI_DIRECT8
                    : (!a.final_pass && P.store.dst_fmt == SF_RGB10A2 && P.store.quant == 1023) ? EPI_DIRECT8 : EPI_GENERIC;
     // instantiated (source, epilogue) pairs: each source with the epilogue it normally meets + the generic one
-#define MPCVR_LAUNCH3(NTK, TK, SK, EK) hipLaunchKernelGGL((fused_up2x_kernel<NTK, TK, SK, EK>(a.exact_cv != 0)), grid, block, lds, s, a, frames_dev, baked, tab)
+#define MPCVR_LAUNCH3(NTK, TK, SK, EK) hipLaunchKernelGGL((fused_up2x_kernel<NTK, TK, SK, EK>(a.exact_cv != 0)), grid, block, lds, s, a, F.dev, baked, tab)
 #define MPCVR_LAUNCH(NT, TK) do { \
         if (srck == SRC_P01X && epik == EPI_DITHER8) MPCVR_LAUNCH3(NT, TK, SRC_P01X, EPI_DITHER8); \
         else if (srck == SRC_P01X && epik == EPI_DIRECT8) MPCVR_LAUNCH3(NT, TK, SRC_P01X, EPI_DIRECT8); \

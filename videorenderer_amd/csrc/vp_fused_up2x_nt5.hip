@@ -2,5 +2,5 @@
 #include "vp_fused_up2x.h"
 
 namespace mpcvr {
-template hipError_t LaunchFusedUp2xNT<5>(const FusedParams &, const FusedArgs &, int, int, const FusedFrame *, FusedFrame, int, hipStream_t);
+template hipError_t LaunchFusedUp2xNT<5>(const FusedParams &, const FusedArgs &, int, int, const LaunchFrames &, hipStream_t);
 }

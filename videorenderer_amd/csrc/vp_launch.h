@@ -57,6 +57,28 @@ struct FusedFrame {
     const uint8_t *src;   // sample base (planes back to back)
     void *dst;            // render target base
 };
+template <class Table> constexpr int TableRows() { return (int)(sizeof(Table::f) / sizeof(FusedFrame)); }      // rows of a by-value table (FrameTable32 / FrameTable128)
+// The frames a launch draws: frame z's {src, dst}, in one of three forms (the factories below build nothing else).  Every fused launcher takes
+// one and checks it once (Valid) against the rows its kernel carries in its arguments; the kernels find the form they were handed on their own.
+struct LaunchFrames {
+    int n = 1;
+    FusedFrame one{nullptr, nullptr};   // the single frame of a launch without a table
+    const FusedFrame *host = nullptr;   // n rows in host memory: they travel by value in the kernel arguments (no copy on the stream)
+    const FusedFrame *dev = nullptr;    // n rows in device memory
+    static LaunchFrames One(const uint8_t *src, void *dst) { LaunchFrames f; f.one = FusedFrame{src, dst}; return f; }
+    static LaunchFrames Host(const FusedFrame *rows, int n) { LaunchFrames f; f.n = n; f.host = rows; return f; }
+    static LaunchFrames Device(const FusedFrame *rows, int n) { LaunchFrames f; f.n = n; f.dev = rows; return f; }
+    // by_value_max: host rows the launcher's kernel takes in its arguments (0: One or Device only).  Host rows past it are the caller's
+    // programming error (hipErrorInvalidValue) — the caller asks ConvertBlocksByValueMax / FusedUp2xByValueMax first
+    bool Valid(int by_value_max) const { return n >= 1 && (host ? !dev && !one.src && n <= by_value_max : dev ? !one.src : n == 1); }
+    // the host rows as a kernel's by-value table (FrameTable32 / FrameTable128); n = 0: the kernel reads `dev` or `one`
+    template <class Table> void ByValue(Table *t) const
+    {
+        t->n = host ? n : 0;
+        if (!host) return;
+        for (int i = 0; i < TableRows<Table>(); i++) t->f[i] = i < n ? host[i] : FusedFrame{nullptr, nullptr};
+    }
+};
 struct FusedParams {
     ConvertParams conv;       // plane pointers are ignored; derived per frame from FusedFrame::src
     size_t plane_off[3];      // byte offsets of the planes inside a sample
@@ -86,8 +108,6 @@ struct FusedParams {
                               // 16-byte loads; null => the kernel derives the tables from store.dither and the tone-map table, as the other fused kernels do
     const float *baked_lut;   // the device table the image's tone-map part was baked from (pq_lut, hlg_lut or null): an image baked from another
                               // table than the launch's is not used
-    const FusedFrame *frames_host;   // host, n_frames entries, n_frames <= 32: the frame table travels by value in the kernel arguments and
-                              // frames_dev is not handed to the kernel (LaunchFusedUp2x still wants it non-null for n_frames > 1)
 };
 // The LDS image of the fused kernels' read-only tables, byte for byte what their prologue computes (vp_fused_dev.h: LDS_D | LDS_DB | LDS_T):
 //   D[1024]  uint16   the dither table's fp16 bits
@@ -111,7 +131,7 @@ struct ErrDiffParams {
     int *status;               // host memory the device can write: set to 1 when a band gave up waiting for the band above (never, unless a launch is broken)
 };
 size_t ErrorDiffusionHandoffBytes(const ErrDiffParams &P, int n_frames);
-hipError_t LaunchErrorDiffusion(const ErrDiffParams &P, const FusedFrame *frames_dev, FusedFrame single, int n_frames, hipStream_t s);
+hipError_t LaunchErrorDiffusion(const ErrDiffParams &P, const LaunchFrames &F, hipStream_t s);       // F: One or Device
 bool FusedUp2xSupported(const FusedParams &P);
 // vp_fused_jinc.hip: the weight table of the fused Jinc2m kernel, from BuildJincPhases' table of a 2x draw
 hipError_t LaunchEvalDoviTail(const float *rgb_dev, float *out_dev, size_t n, const float lms[9], const float k[5], const float gamut[9], int l2, float lum_scale, int stage, hipStream_t s);
@@ -124,16 +144,19 @@ bool BlockConvertLayout(const FusedParams &P, bool catmull_420);       // source
 // the final pass into a B8G8R8A8 render target (store.mode == ST_FINAL).  out_w / out_h / wx / wy of P are not used.
 bool ConvertBlocksSupported(const FusedParams &P, bool to_rt);
 // batch_stride != 0: frame z is stored at P.store.dst + z * batch_stride (a batched intermediate) instead of frames[z].dst
-// frames_host != nullptr and n_frames <= 32 (<= kHostTableMax where the streaming kernel takes the launch; hipErrorInvalidValue otherwise: the
-// caller then uploads the table): the frame table travels by value in the kernel arguments (frames_dev is not read)
+// The kernels' by-value frame tables (LaunchFrames::host): 32 rows for k_convert_blocks and the exact-2x kernel ...
 struct FrameTable32 { FusedFrame f[32]; int n; };
-// k_convert_stream: up to 128 frames (a step of 1080p frames is 128 of them: no table upload in front of an 80-300 us launch)
+// ... k_convert_stream: up to 128 frames (a step of 1080p frames is 128 of them: no table upload in front of an 80-300 us launch)
 struct FrameTable128 { FusedFrame f[128]; int n; };
 enum { kHostTableMax = 128 };
-hipError_t LaunchConvertBlocks(const FusedParams &P, const FusedFrame *frames_dev, FusedFrame single, int n_frames, hipStream_t s,
-                               size_t batch_stride = 0, const FusedFrame *frames_host = nullptr);
-// frames_dev == nullptr: n_frames must be 1 and `single` is used (no device-side table needed)
-hipError_t LaunchFusedUp2x(const FusedParams &P, const FusedFrame *frames_dev, FusedFrame single, int n_frames, hipStream_t s);
+static_assert(TableRows<FrameTable128>() == kHostTableMax, "the callers' row arrays (kHostTableMax) hold the largest by-value table");
+// How many host rows the launch with these parameters takes by value — the launchers' own rule, for the caller that has to choose between
+// LaunchFrames::Host and an uploaded table: 128 where the streaming kernel takes the convert and 32 otherwise; 32 for the exact-2x kernel
+// and 0 with jinc_tab set (the fused Jinc2m kernel reads an uploaded table).  The strip, periodic and error-diffusion launchers take none.
+int ConvertBlocksByValueMax(const FusedParams &P);
+inline int FusedUp2xByValueMax(const FusedParams &P) { return P.jinc_tab ? 0 : TableRows<FrameTable32>(); }
+hipError_t LaunchConvertBlocks(const FusedParams &P, const LaunchFrames &F, hipStream_t s, size_t batch_stride = 0);
+hipError_t LaunchFusedUp2x(const FusedParams &P, const LaunchFrames &F, hipStream_t s);
 
 // arbitrary-ratio fused path (vp_fused_strip.hip): block convert + both draws of an unrotated two-pass resize + final pass in one
 // kernel, driven by the tap tables of BuildAxisTaps; wave-autonomous strips like the 2x kernel, the vertical window in LDS.
@@ -163,7 +186,7 @@ struct FusedStripParams {
     const void *per_xi_t, *per_xw_t, *per_yw, *per_xstrip;
 };
 bool FusedStripSupported(const FusedStripParams &S);
-hipError_t LaunchFusedStrip(const FusedStripParams &S, const FusedFrame *frames_dev, FusedFrame single, int n_frames, hipStream_t s);
+hipError_t LaunchFusedStrip(const FusedStripParams &S, const LaunchFrames &F, hipStream_t s);       // F: One or Device
 size_t FusedStripLdsBytes(const FusedStripParams &S);
 size_t DeviceLdsLimit();       // LDS bytes one workgroup may claim on the current device (queried, not assumed)
 // true when LaunchFusedStrip would run the periodic-phase kernel for this launch (GetVPInfo reports it)
