@@ -515,6 +515,55 @@ int32_t mpcvr_deint_pass(const void *prev, const void *cur, const void *next, in
  * the previous sample stays current. */
 int32_t mpcvr_copy_sample_fields(mpcvr_ctx *ctx, const void *prev, const void *cur, const void *next, int32_t field_order, int32_t field, int32_t mode);
 
+/* EXTENSION — a 3D colour LUT applied to a rendered frame: the colour decision a broadcast or grading pipeline carries as a .cube file
+ * (an HLG -> SDR or PQ -> SDR conversion, a camera log to Rec.709, a show look, a display or encoder calibration), tetrahedral
+ * interpolation in integers.  The reference has no LUT; there is no reference line to cite.  The definition is the integer text below,
+ * modelled bit for bit by tests/lut3d_model.py (arithmetic: csrc/vp_lut3d_core.h, which the kernel and mpcvr_plan_lut3d_value both compile).
+ *   Surfaces: src is a DEVICE surface of w x h 32-bit texels, w and h in 1 .. 32768, src_fmt = MPCVR_OUT_BGRA8 (maxin = 255) or
+ *     MPCVR_OUT_RGB10A2 (maxin = 1023); the A / X bits of src are ignored.  dst is w x h 32-bit texels, dst_fmt chosen independently of
+ *     src_fmt from the same two formats, its largest code maxout; the A / X bits of dst are written as all ones.  Pointers and pitches are
+ *     multiples of 4 and pitches >= 4 w (the render-target rule of mpcvr_process); 16-byte loads and stores are taken where pointers and
+ *     pitches allow them.
+ *   The table: lut is in DEVICE memory, 8-byte aligned: n^3 entries of four uint16_t {R, G, B, pad}, n in 2 .. 65.  The entry of node
+ *     (r, g, b) sits at index (b n + g) n + r — R runs fastest, the order of a .cube file.  pad is ignored.  An entry component E in
+ *     0 .. 65535 stands for E / 65535 of the destination's range.
+ *   Per texel, everything in 32-bit unsigned integers.  For each source code c of (R, G, B):
+ *       t = c (n - 1),   i = min(t / maxin, n - 2),   f = t - i maxin     (f lies in 0 .. maxin).
+ *     Order the three channels so that f(1) >= f(2) >= f(3).  A tie needs no rule: it gives the vertex the two orders disagree about the
+ *     weight zero, so either order gives the same answer (tests/test_lut3d.py evaluates tied inputs under every admissible order).
+ *       V0 = lut[iR, iG, iB],   V1 = V0 stepped by +1 along the axis of f(1),   V2 = V1 stepped by +1 along the axis of f(2),
+ *       V3 = lut[iR + 1, iG + 1, iB + 1];
+ *       w0 = maxin - f(1),   w1 = f(1) - f(2),   w2 = f(2) - f(3),   w3 = f(3)     (they sum to maxin).
+ *     For each output channel k:
+ *       acc = sum over j of w_j V_j[k]     (at most 1023 * 65535 = 67,042,305),
+ *       v = (acc + (maxin >> 1)) / maxin,   out = (v maxout + 32767) / 65535.
+ *     Both divisions are by compile-time constants.  No dithering: an RGB10A2 source written as BGRA8 is rounded, as in mpcvr_encode_pass.
+ *   With the identity table E[i] = (2 i 65535 + (n - 1)) / (2 (n - 1)) per axis, out == c whenever maxin == maxout, and across depths
+ *     out == (2 c maxout + maxin) / (2 maxin), for every code and every n (tests/test_lut3d.py).
+ *   In place: dst == src with dst_pitch == src_pitch is allowed; every texel is read before it is written, by the same lane.
+ * Refusals, with nothing launched and nothing written: MPCVR_E_POINTER for a NULL src, lut_dev or dst; MPCVR_E_INVALIDARG for another
+ * src_fmt or dst_fmt, n, w or h out of range, a pointer or pitch that breaks the rules above, any other overlap of dst with src, and any
+ * overlap of the table with dst (a surface counts as the bytes from its first pixel to the last pixel of its last row).  No byte outside
+ * dst's pixels is ever written: not the pitch padding, nothing in front of or behind the surface. */
+/* Host, no GPU: n^3 float triplets in .cube order (R fastest) -> the 8-byte entries: each component rint(clamp(x, 0, 1) * 65535)
+ * evaluated in double (ties to even), NaN -> 0, pad = 0.  MPCVR_E_POINTER for a NULL pointer, MPCVR_E_INVALIDARG for n outside 2 .. 65. */
+int32_t mpcvr_plan_lut3d_entries(const float *rgb, int32_t n, uint16_t *entries);
+/* Host, no GPU: *out = the destination texel of one source texel through a table in HOST memory, bit for bit what the kernel writes.
+ * MPCVR_E_POINTER for a NULL pointer, MPCVR_E_INVALIDARG for another format or n. */
+int32_t mpcvr_plan_lut3d_value(int32_t src_fmt, int32_t dst_fmt, const uint16_t *entries_host, int32_t n, uint32_t texel, uint32_t *out);
+/* One standalone pass over one device surface, like mpcvr_encode_pass; stream = a hipStream_t or NULL.  One kernel launch (k_lut3d,
+ * csrc/vp_lut3d.hip).  The table is read from LDS or from where it lies, by its size; the bytes are the same. */
+int32_t mpcvr_lut3d_pass(const void *src, int32_t src_pitch, int32_t src_fmt, int32_t w, int32_t h, const void *lut_dev, int32_t n,
+                         void *dst, int32_t dst_pitch, int32_t dst_fmt, void *stream);
+/* mpcvr_render, then the pass from the back buffer over the whole window into dst, ordered exactly as mpcvr_render_tensor: Process into
+ * the context-owned back buffer with the letterbox cleared to black, on the context stream (not on a frame lane; the pixels are the
+ * same), the pass queued behind it, and everything queued later, lanes included, behind the pass.  dst is complete after
+ * mpcvr_synchronize; the back buffer is only read: mpcvr_get_backbuffer and mpcvr_get_displayed_image afterwards see the RGB frame a plain
+ * mpcvr_render leaves.  The source format is the context's output_format — MPCVR_OUT_RGB10A2 lets the table see 10-bit codes, with
+ * dst_fmt free.  Everything mpcvr_lut3d_pass refuses about the table and dst is answered before anything is drawn.  S_FALSE, with nothing
+ * drawn or written, when there is no sample (as mpcvr_render). */
+int32_t mpcvr_render_lut3d(mpcvr_ctx *ctx, int32_t field, const void *lut_dev, int32_t n, void *dst, int32_t dst_pitch, int32_t dst_fmt);
+
 /* Configure — DX11VideoProcessor.cpp:3800-4050: diff each field, rebuild only what changed. */
 int32_t mpcvr_configure(mpcvr_ctx *ctx, const mpcvr_settings *settings);
 
@@ -747,6 +796,27 @@ int32_t mpcvr_plan_batch_deint(int32_t pitch, int32_t lines, int32_t n_out, size
 int32_t mpcvr_process_batch_deint(mpcvr_ctx *ctx, int32_t n, const void *const *frames /* n + 2 device samples */, int32_t field_order,
                                   int32_t fields_per_frame /* 1 or 2 */, int32_t mode, void *const *dsts /* n * fields_per_frame targets */,
                                   int32_t dst_pitch);
+/* EXTENSION — a batch through a 3D LUT (the pass itself: mpcvr_lut3d_pass above).  dsts[i] is the render target of frame i, all n of
+ * dst_pitch and dst_fmt.  Target i holds, byte for byte, what
+ *     mpcvr_process_batch(srcs -> n window-sized RGB targets of the context's output_format, black outside the video rect), then
+ *     mpcvr_lut3d_pass(target i, output_format, window_w, window_h, lut_dev, lut_n, dsts[i], dst_pitch, dst_fmt), n times
+ * leave, with ONE k_lut3d launch per chunk of frames (its frame dimension) where the composition takes n, and no intermediate targets of
+ * the caller's.  The machinery is that of mpcvr_process_batch_tensor: the RGB frames live in the same context-owned surfaces (one per batch
+ * lane used), laid out by mpcvr_plan_batch_lut3d — the formulas of mpcvr_plan_batch_tensor — under the budget of
+ * mpcvr_set_batch_yuv_budget.  Chunks, routes, the letterbox and the order are as described for mpcvr_process_batch_yuv; every target
+ * counts as bytes the chunk writes: single frames, batches and further calls that write memory a target in flight covers stay behind it
+ * in queue order.  The intended use is a context whose output_format is MPCVR_OUT_RGB10A2, so that the table sees 10-bit codes, with
+ * dst_fmt free.  The targets are complete after mpcvr_synchronize.
+ * Refusals, answered before anything is drawn, allocated or written: MPCVR_E_NOT_VALID_STATE before mpcvr_set_input; MPCVR_E_POINTER for
+ * a NULL array, entry or table; MPCVR_E_INVALIDARG for n <= 0, whatever mpcvr_lut3d_pass refuses about the table, dst_pitch, dst_fmt and
+ * a dsts[i] (a target that overlaps the table included), and any two targets that overlap each other.
+ * mpcvr_get_last_batch_info afterwards: "launches" counts one pass per chunk, and ";lut3d_chunks=<k>;lut3d_lanes=<lane,lane,...>"
+ * follow (the lane of each chunk, -1 = the context stream; the first 64 chunks), then ";lut3d_table=lds" or ";lut3d_table=global":
+ * where the pass read the table from. */
+int32_t mpcvr_plan_batch_lut3d(int32_t window_w, int32_t window_h, int32_t n, size_t budget_bytes,
+                               int32_t *surface_pitch, size_t *frame_stride, int32_t *frames_per_chunk, int32_t *chunks);
+int32_t mpcvr_process_batch_lut3d(mpcvr_ctx *ctx, int32_t n, const void *const *srcs, const void *lut_dev, int32_t lut_n,
+                                  void *const *dsts, int32_t dst_pitch, int32_t dst_fmt);
 
 /* Multi-GPU: the parameter blob (colour matrix, luminance scale, gamut matrix, resize phase weights,
  * dither table) a rank-0 context computes and every other rank adopts after an RCCL broadcast.

@@ -207,6 +207,7 @@ EXPORTS = [
     "mpcvr_plan_tensor_value", "mpcvr_tensor_pass", "mpcvr_render_tensor", "mpcvr_plan_batch_tensor", "mpcvr_process_batch_tensor",
     "mpcvr_plan_sample_code", "mpcvr_sample_pass", "mpcvr_copy_sample_tensor", "mpcvr_plan_batch_from_tensors", "mpcvr_process_batch_from_tensors",
     "mpcvr_plan_deint_planes", "mpcvr_deint_plane_host", "mpcvr_deint_pass", "mpcvr_copy_sample_fields", "mpcvr_plan_batch_deint", "mpcvr_process_batch_deint",
+    "mpcvr_plan_lut3d_entries", "mpcvr_plan_lut3d_value", "mpcvr_lut3d_pass", "mpcvr_render_lut3d", "mpcvr_plan_batch_lut3d", "mpcvr_process_batch_lut3d",
 ]
 
 _lib = None
@@ -329,6 +330,12 @@ def load_library():
         "mpcvr_copy_sample_fields": [vp, vp, vp, vp, i32, i32, i32],
         "mpcvr_plan_batch_deint": [i32, i32, i32, C.c_size_t, P(C.c_size_t), P(i32), P(i32)],
         "mpcvr_process_batch_deint": [vp, i32, P(vp), i32, i32, i32, P(vp), i32],
+        "mpcvr_plan_lut3d_entries": [vp, i32, vp],
+        "mpcvr_plan_lut3d_value": [i32, i32, vp, i32, u32, P(u32)],
+        "mpcvr_lut3d_pass": [vp, i32, i32, i32, i32, vp, i32, vp, i32, i32, vp],
+        "mpcvr_render_lut3d": [vp, i32, vp, i32, vp, i32, i32],
+        "mpcvr_plan_batch_lut3d": [i32, i32, i32, C.c_size_t, P(i32), P(C.c_size_t), P(i32), P(i32)],
+        "mpcvr_process_batch_lut3d": [vp, i32, P(vp), vp, i32, P(vp), i32, i32],
     }
     for name, args in sig.items():
         if lib_path != LIB_PATH and not hasattr(L, name):
@@ -515,6 +522,108 @@ def plan_batch_tensor(window_w, window_h, n, budget_bytes=0):
     if hr:
         raise MpcvrError(hr, "mpcvr_plan_batch_tensor")
     return dict(surface_pitch=pitch.value, frame_stride=stride.value, frames_per_chunk=fpc.value, chunks=chunks.value)
+
+
+def plan_lut3d_entries(rgb, n):
+    """(extension) The table of the 3D LUT pass from n^3 float triplets in .cube order, R fastest (include/mpcvr.h:
+    mpcvr_plan_lut3d_entries): a numpy uint16 array of (n^3, 4) {R, G, B, pad = 0}, each component rint(clamp(x, 0, 1) * 65535) in double,
+    NaN -> 0.  Host only, no GPU.  Upload it as it is (8 bytes per entry) for lut3d_pass."""
+    import numpy as np
+    n = int(n)
+    rgb = np.ascontiguousarray(rgb, dtype=np.float32).reshape(-1, 3)
+    if rgb.shape[0] != n ** 3:
+        raise ValueError("a table of size %d takes %d triplets, not %d" % (n, n ** 3, rgb.shape[0]))
+    out = np.empty((rgb.shape[0], 4), dtype=np.uint16)
+    hr = load_library().mpcvr_plan_lut3d_entries(C.c_void_p(rgb.ctypes.data), n, C.c_void_p(out.ctypes.data))
+    if hr != S_OK:
+        raise MpcvrError(hr, "mpcvr_plan_lut3d_entries")
+    return out
+
+
+def plan_lut3d_value(src_fmt, dst_fmt, entries, n, texel):
+    """(extension) One texel of the 3D LUT pass on the host (include/mpcvr.h: mpcvr_plan_lut3d_value): `entries` the (n^3, 4) uint16
+    table in host memory, `texel` a 32-bit source texel or an array of them; the destination texel(s), bit for bit what the kernel writes."""
+    import numpy as np
+    entries = np.ascontiguousarray(entries, dtype=np.uint16)
+    if entries.size != 4 * int(n) ** 3:
+        raise ValueError("a table of size %d takes %d uint16 words, not %d" % (n, 4 * int(n) ** 3, entries.size))
+    f = load_library().mpcvr_plan_lut3d_value
+    ep, out = C.c_void_p(entries.ctypes.data), C.c_uint32()
+    scalar = np.ndim(texel) == 0
+    res = []
+    for t in np.atleast_1d(np.asarray(texel, dtype=np.uint32)).ravel().tolist():
+        hr = f(int(src_fmt), int(dst_fmt), ep, int(n), t, C.byref(out))
+        if hr != S_OK:
+            raise MpcvrError(hr, "mpcvr_plan_lut3d_value")
+        res.append(out.value)
+    return res[0] if scalar else np.array(res, dtype=np.uint32).reshape(np.shape(texel))
+
+
+def lut3d_pass(src, src_pitch, src_fmt, w, h, lut, n, dst, dst_pitch, dst_fmt, stream=None):
+    """(extension) One device surface of 32-bit RGB texels (0 = BGRA8, 1 = RGB10A2) through the 3D LUT at `lut` (device tensor or address:
+    n^3 entries of 8 bytes, plan_lut3d_entries) into the surface at `dst`, of either format; dst may be src with the same pitch
+    (include/mpcvr.h: mpcvr_lut3d_pass).  Complete in stream order."""
+    hr = load_library().mpcvr_lut3d_pass(C.c_void_p(_ptr(src)), int(src_pitch), int(src_fmt), int(w), int(h), C.c_void_p(_ptr(lut)), int(n),
+                                         C.c_void_p(_ptr(dst)), int(dst_pitch), int(dst_fmt), C.c_void_p(stream or 0))
+    if hr != S_OK:
+        raise MpcvrError(hr, "mpcvr_lut3d_pass")
+    return hr
+
+
+def plan_batch_lut3d(window_w, window_h, n, budget_bytes=0):
+    """(extension) The layout integers of mpcvr_process_batch_lut3d (include/mpcvr.h: mpcvr_plan_batch_lut3d): plan_batch_tensor's formulas.
+    dict(surface_pitch, frame_stride, frames_per_chunk, chunks).  Host only, no GPU."""
+    pitch, stride, fpc, chunks = C.c_int32(), C.c_size_t(), C.c_int32(), C.c_int32()
+    hr = load_library().mpcvr_plan_batch_lut3d(int(window_w), int(window_h), int(n), int(budget_bytes), C.byref(pitch), C.byref(stride), C.byref(fpc), C.byref(chunks))
+    if hr != S_OK:
+        raise MpcvrError(hr, "mpcvr_plan_batch_lut3d")
+    return dict(surface_pitch=pitch.value, frame_stride=stride.value, frames_per_chunk=fpc.value, chunks=chunks.value)
+
+
+def read_cube(path):
+    """(extension) A .cube file with a 3D table: (n, float32 array of (n^3, 3)) in the file's order, R fastest, which is the order
+    plan_lut3d_entries takes.  LUT_3D_SIZE, TITLE and # comments are understood; DOMAIN_MIN / DOMAIN_MAX are folded in linearly (a value
+    v of channel k becomes (v - min[k]) / (max[k] - min[k])).  A LUT_1D_SIZE file, another keyword, or an entry count that is not n^3 raises
+    ValueError."""
+    import numpy as np
+    n, lo, hi, rows = None, [0.0, 0.0, 0.0], [1.0, 1.0, 1.0], []
+    with open(path, "r", encoding="utf-8", errors="replace") as fh:
+        for ln, raw in enumerate(fh, 1):
+            line = raw.split("#", 1)[0].strip()
+            if not line:
+                continue
+            tok = line.split()
+            key = tok[0].upper()
+            if key == "TITLE":
+                continue
+            if key == "LUT_1D_SIZE":
+                raise ValueError("%s:%d: a 1D table (LUT_1D_SIZE); the pass takes a 3D table" % (path, ln))
+            if key == "LUT_3D_SIZE":
+                if len(tok) != 2 or n is not None:
+                    raise ValueError("%s:%d: LUT_3D_SIZE takes one integer, once" % (path, ln))
+                n = int(tok[1])
+                if not 2 <= n <= 65:
+                    raise ValueError("%s:%d: a table size of %d is outside 2 .. 65" % (path, ln, n))
+                continue
+            if key in ("DOMAIN_MIN", "DOMAIN_MAX"):
+                if len(tok) != 4:
+                    raise ValueError("%s:%d: %s takes three numbers" % (path, ln, key))
+                (lo if key == "DOMAIN_MIN" else hi)[:] = [float(x) for x in tok[1:]]
+                continue
+            if key[0].isalpha() and key not in ("NAN", "INF", "INFINITY"):
+                raise ValueError("%s:%d: unknown keyword %s" % (path, ln, tok[0]))
+            if len(tok) != 3:
+                raise ValueError("%s:%d: a table line takes three numbers" % (path, ln))
+            rows.append([float(x) for x in tok])
+    if n is None:
+        raise ValueError("%s: no LUT_3D_SIZE" % path)
+    if len(rows) != n ** 3:
+        raise ValueError("%s: %d entries, LUT_3D_SIZE %d takes %d" % (path, len(rows), n, n ** 3))
+    if any(not h > l for l, h in zip(lo, hi)):
+        raise ValueError("%s: DOMAIN_MAX must lie above DOMAIN_MIN" % path)
+    v = np.array(rows, dtype=np.float64)
+    v = (v - np.array(lo)) / (np.array(hi) - np.array(lo))
+    return n, v.astype(np.float32)
 
 
 def _tensor_dtype(dt):
@@ -956,6 +1065,39 @@ class VideoProcessor:
         self._keep = keep
         return self._check(self._L.mpcvr_process_batch_tensor(self._ctx, n, keep[0], C.byref(d), keep[1]))
 
+    def RenderLut3d(self, lut, n, dst_fmt=None, out=None, out_pitch=None, field=1):
+        """(extension) Render, then the back buffer through the 3D LUT at `lut` (device tensor or address: n^3 entries of 8 bytes,
+        plan_lut3d_entries) into a target of dst_fmt (OUT_BGRA8 / OUT_RGB10A2; None: the context's output_format) (mpcvr_render_lut3d).
+        `out`: a device tensor or address of window_h rows of out_pitch bytes (None: 4 * window_w); else a (H, W, 4) uint8 tensor is
+        allocated.  Returns the target, complete after Synchronize; None when there is no sample (S_FALSE).  The back buffer stays the
+        plain frame."""
+        import torch
+        ww, wh = self._window_size()
+        if dst_fmt is None:
+            dst_fmt = self.settings.output_format
+        if out is None:
+            out = torch.empty((wh, ww, 4), dtype=torch.uint8, device="cuda")
+            out_pitch = ww * 4
+        elif out_pitch is None:
+            out_pitch = ww * 4
+        self._keep = (lut, out)
+        hr = self._check(self._L.mpcvr_render_lut3d(self._ctx, field, C.c_void_p(_ptr(lut)), int(n), C.c_void_p(_ptr(out)), int(out_pitch), int(dst_fmt)))
+        return out if hr == S_OK else None
+
+    def ProcessBatchLut3d(self, srcs, lut, n, dsts, dst_pitch, dst_fmt=None):
+        """(extension) ProcessBatch with every frame taken through the 3D LUT at `lut` on its way to its render target
+        (mpcvr_process_batch_lut3d): dsts[i] are device tensors or addresses of window_h rows of dst_pitch bytes, of dst_fmt (None: the
+        context's output_format).  One k_lut3d launch per chunk; complete after Synchronize.  GetLastBatchInfo adds lut3d_chunks /
+        lut3d_lanes / lut3d_table."""
+        m = len(srcs)
+        assert m == len(dsts) and m > 0
+        if dst_fmt is None:
+            dst_fmt = self.settings.output_format
+        arr = C.c_void_p * m
+        keep = (arr(*[_ptr(s) for s in srcs]), arr(*[_ptr(d) for d in dsts]), (srcs, dsts, lut))
+        self._keep = keep
+        return self._check(self._L.mpcvr_process_batch_lut3d(self._ctx, m, keep[0], C.c_void_p(_ptr(lut)), int(n), keep[1], int(dst_pitch), int(dst_fmt)))
+
     def MeasureBackBuffer(self, hist=None):
         """(extension) The histogram of max(R, G, B) of the frame the last Render / RenderYuv left, over video rect ∩ window
         (mpcvr_measure_backbuffer): a device tensor of 1024 int32 words holding the uint32 counts (allocated when `hist` is None), complete
@@ -1132,7 +1274,7 @@ class VideoProcessor:
         return buf.value.decode()
 
     def GetLastBatchInfo(self):
-        """'frames=<n>;launches=<kernel launches>;lane=<0 | 1: the batch ran on that lane beside its predecessor, -1: on the context stream>;waits=<frames / batches still in flight on other lanes, into memory this batch's targets overlap, that it was ordered behind>[;dovi_runs=...]' of the last ProcessBatch / ProcessBatchDovi / ProcessBatchYuv call, as a dict; behind a ProcessBatchYuv also yuv_chunks and yuv_lanes (the lane of each chunk), behind a ProcessBatchTensor tensor_chunks and tensor_lanes, behind a ProcessBatchFromTensors sample_chunks."""
+        """'frames=<n>;launches=<kernel launches>;lane=<0 | 1: the batch ran on that lane beside its predecessor, -1: on the context stream>;waits=<frames / batches still in flight on other lanes, into memory this batch's targets overlap, that it was ordered behind>[;dovi_runs=...]' of the last ProcessBatch / ProcessBatchDovi / ProcessBatchYuv call, as a dict; behind a ProcessBatchYuv also yuv_chunks and yuv_lanes (the lane of each chunk), behind a ProcessBatchTensor tensor_chunks and tensor_lanes, behind a ProcessBatchFromTensors sample_chunks, behind a ProcessBatchLut3d lut3d_chunks, lut3d_lanes and lut3d_table."""
         buf = C.create_string_buffer(512)
         self._check(self._L.mpcvr_get_last_batch_info(self._ctx, buf, 512))
         d = dict(kv.split("=", 1) for kv in buf.value.decode().split(";"))
@@ -1145,6 +1287,8 @@ class VideoProcessor:
             out.update(sample_chunks=int(d["sample_chunks"]))
         if "deint_chunks" in d:      # (only behind a ProcessBatchDeint)
             out.update(deint_chunks=int(d["deint_chunks"]))
+        if "lut3d_chunks" in d:      # (only behind a ProcessBatchLut3d: the lane of each chunk, and where the pass read the table from)
+            out.update(lut3d_chunks=int(d["lut3d_chunks"]), lut3d_lanes=[int(x) for x in d["lut3d_lanes"].split(",") if x], lut3d_table=d.get("lut3d_table", ""))
         return out
 
     def GetLastProcessMs(self):

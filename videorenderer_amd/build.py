@@ -50,6 +50,7 @@ SOURCES = [
     ("vp_tensor.hip", []),
     ("vp_tensor_in.hip", []),
     ("vp_deint.hip", []),
+    ("vp_lut3d.hip", []),
     ("vp_probe.hip", []),
 ]
 

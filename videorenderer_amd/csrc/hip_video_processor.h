@@ -16,6 +16,7 @@
 #include "vp_tensor.h"
 #include "vp_tensor_in.h"
 #include "vp_deint.h"
+#include "vp_lut3d.h"
 #include "vp_launch.h"
 #include "vp_params.h"
 #include "vp_plan.h"
@@ -72,6 +73,12 @@ HRESULT SampleSurface(const void *tensor, const mpcvr_tensor_desc *desc, int w, 
 HRESULT DeintSurface(const void *prev, const void *cur, const void *next, int cformat, int w, int h, int pitch, int keep, int first, int mode,
                      void *dst, int dstPitch, hipStream_t stream, bool checkOnly, const char **why = nullptr, int *launches = nullptr);
 
+// EXTENSION (mpcvr_lut3d_pass, include/mpcvr.h): checks every argument, then — unless checkOnly — launches k_lut3d on `stream`.
+// MPCVR_E_POINTER / MPCVR_E_INVALIDARG with nothing launched or written.  checkOnly takes src = nullptr for a source that is still to be
+// allocated (it cannot overlap the destination or the table)
+HRESULT Lut3dSurface(const void *src, int srcPitch, int srcFmt, int w, int h, const void *lutDev, int n, void *dst, int dstPitch, int dstFmt,
+                     hipStream_t stream, bool checkOnly, const char **why = nullptr);
+
 class CHipVideoProcessor {
 public:
     CHipVideoProcessor();
@@ -126,6 +133,10 @@ public:
     // sample surface, the pass (its frame dimension) in front of each chunk's batch, everything on the context stream
     HRESULT CopySampleFields(const void *prev, const void *cur, const void *next, int fieldOrder, int field, int mode);
     HRESULT ProcessBatchDeint(int n, const void *const *frames, int fieldOrder, int fieldsPerFrame, int mode, void *const *dsts, int rtPitch);
+    // EXTENSION (mpcvr_render_lut3d / mpcvr_process_batch_lut3d): Render / the batch, then k_lut3d (vp_lut3d.h) behind it in stream order into the
+    // caller's targets; the batch shares ProcessBatchYuv's surfaces, budget and chunk loop
+    HRESULT RenderLut3d(int field, const void *lutDev, int n, void *dst, int dstPitch, int dstFmt);
+    HRESULT ProcessBatchLut3d(int n, const void *const *srcs, const void *lutDev, int lutN, void *const *dsts, int dstPitch, int dstFmt);
     HRESULT SetBatchYuvBudget(size_t bytes) { m_yuvBudget = bytes; return MPCVR_S_OK; }
     std::string GetLastBatchInfo() const;
     HRESULT ProcessBatchDovi(int n, const void *const *srcs, void *const *dsts, int rtPitch, const mpcvr_dovi_metadata *rpus);
@@ -478,7 +489,7 @@ private:
     };
     YuvSurface m_yuvSurf[FrameLanes::kFrameLanes];
     size_t m_yuvBudget = 0;            // SetBatchYuvBudget; 0: kBatchYuvDefaultBudget
-    std::string m_yuvLastInfo;         // ";yuv_chunks=..;yuv_lanes=.." (";tensor_chunks=..;tensor_lanes=..") of the last batch call, if it was a ProcessBatchYuv (ProcessBatchTensor)
+    std::string m_yuvLastInfo;         // ";yuv_chunks=..;yuv_lanes=.." (";tensor_chunks=..;tensor_lanes=..", ";lut3d_chunks=..;lut3d_lanes=..;lut3d_table=..") of the last batch call, if it was a ProcessBatchYuv (ProcessBatchTensor, ProcessBatchLut3d)
     DevBuffer m_sampleSurf;            // ProcessBatchFromTensors / ProcessBatchDeint: the samples of one chunk side by side (PlanBatchSamples), written and read in stream order on the context stream
     // the chunk loop of ProcessBatchYuv / ProcessBatchTensor: surfaces, lanes and order; writesOf(at, m): what the chunk writes for the caller, pass(run, at): its pass
     template <class WritesOf, class Pass>

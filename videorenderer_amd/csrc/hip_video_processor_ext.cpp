@@ -1,6 +1,6 @@
 // hip_video_processor_ext.cpp — the EXTENSIONS of CHipVideoProcessor (no reference line anywhere in this file): frames as NV12 / P010, their
-// histograms, frames as float tensors, float tensors as samples, deinterlacing at field rate.  Each is a free function that checks and launches
-// one pass (EncodeSurface, MeasureSurface, TensorSurface, SampleSurface, DeintSurface), a per-sample call and a batch call; the batch calls share
+// histograms, frames as float tensors, float tensors as samples, deinterlacing at field rate, frames through a 3D LUT.  Each is a free function that checks and launches
+// one pass (EncodeSurface, MeasureSurface, TensorSurface, SampleSurface, DeintSurface, Lut3dSurface), a per-sample call and a batch call; the batch calls share
 // two chunk loops (RunSurfaceChunks, RunSampleChunks), the per-sample calls CopySample's upload slots (AcquireUploadSlot / PublishUploadSlot).
 #include "hip_video_processor.h"
 
@@ -738,6 +738,116 @@ HRESULT CHipVideoProcessor::ProcessBatchDeint(int n, const void *const *frames, 
         }
         return hr;
     });
+}
+
+// ------------------------------------------------------------------------------------------------
+// EXTENSION — a 3D colour LUT over rendered frames (include/mpcvr.h: mpcvr_lut3d_pass, mpcvr_render_lut3d, mpcvr_process_batch_lut3d;
+// kernel: vp_lut3d.hip).  No reference line: the reference has no LUT.
+// ------------------------------------------------------------------------------------------------
+// What a k_lut3d launch is given, but for its surfaces: src / dst or the frame table are the caller's, who takes src16 / dst16 back where a
+// pointer of the launch is off 16 bytes (here they say what the pitches allow), as in TensorLaunchParams
+static Lut3dParams Lut3dLaunchParams(int w, int h, int srcPitch, int dstPitch, const void *lutDev, int n)
+{
+    Lut3dParams p{};
+    p.src_pitch = srcPitch; p.dst_pitch = dstPitch; p.w = w; p.h = h;
+    p.lut = (const Lut3dEntry *)lutDev; p.n = n;
+    p.src16 = (srcPitch & 15) == 0;
+    p.dst16 = (dstPitch & 15) == 0;
+    return p;
+}
+
+HRESULT Lut3dSurface(const void *src, int srcPitch, int srcFmt, int w, int h, const void *lutDev, int n, void *dst, int dstPitch, int dstFmt,
+                     hipStream_t stream, bool checkOnly, const char **why)
+{
+    const char *dummy;
+    if (!why) why = &dummy;
+    if ((!src && !checkOnly) || !lutDev || !dst) { *why = "null surface, table or destination"; return MPCVR_E_POINTER; }      // (checkOnly: a source still to be allocated)
+    if ((srcFmt != MPCVR_OUT_BGRA8 && srcFmt != MPCVR_OUT_RGB10A2) || (dstFmt != MPCVR_OUT_BGRA8 && dstFmt != MPCVR_OUT_RGB10A2)) {
+        *why = "source and destination BGRA8 or RGB10A2"; return MPCVR_E_INVALIDARG;
+    }
+    if (w < 1 || h < 1 || w > 32768 || h > 32768) { *why = "width and height must be 1 .. 32768"; return MPCVR_E_INVALIDARG; }
+    if (n < kLut3dMinN || n > kLut3dMaxN) { *why = "the table's size must be 2 .. 65"; return MPCVR_E_INVALIDARG; }
+    if (srcPitch < 4 * w || dstPitch < 4 * w) { *why = "pitch smaller than a row"; return MPCVR_E_INVALIDARG; }
+    if (((uintptr_t)src | (uintptr_t)srcPitch | (uintptr_t)dst | (uintptr_t)dstPitch) & 3) { *why = "surfaces and pitches must be multiples of 4"; return MPCVR_E_INVALIDARG; }
+    if ((uintptr_t)lutDev & 7) { *why = "the table must be 8-byte aligned"; return MPCVR_E_INVALIDARG; }
+    const RtSpan s = RowsSpan(src, (size_t)srcPitch, h, (size_t)4 * w), d = RowsSpan(dst, (size_t)dstPitch, h, (size_t)4 * w);
+    const RtSpan t{(uintptr_t)lutDev, (uintptr_t)lutDev + Lut3dTableBytes(n)};
+    // in place — the same first pixel and the same pitch — is the one overlap of the two surfaces a lane's read-then-write order covers
+    if (src && d.Overlaps(s) && !(dst == src && dstPitch == srcPitch)) { *why = "the destination overlaps the source without being the source"; return MPCVR_E_INVALIDARG; }
+    if (t.Overlaps(d)) { *why = "the table overlaps the destination"; return MPCVR_E_INVALIDARG; }
+    if (checkOnly) return MPCVR_S_OK;
+    Lut3dParams p = Lut3dLaunchParams(w, h, srcPitch, dstPitch, lutDev, n);
+    p.src = (const uint8_t *)src; p.dst = (uint8_t *)dst;
+    p.src16 &= (s.lo & 15) == 0;
+    p.dst16 &= (d.lo & 15) == 0;
+    if (LaunchLut3d(p, srcFmt == MPCVR_OUT_RGB10A2, dstFmt == MPCVR_OUT_RGB10A2, stream) != hipSuccess) { *why = "k_lut3d launch failed"; return MPCVR_E_FAIL; }
+    return MPCVR_S_OK;
+}
+
+// Render, then the pass from the back buffer over the whole window into the caller's target, ordered as RenderYuv (the comment there): on
+// the context stream, the lanes' next work behind the pass.  The back buffer is only read: it stays the frame a plain Render leaves.
+HRESULT CHipVideoProcessor::RenderLut3d(int /*field*/, const void *lutDev, int n, void *dst, int dstPitch, int dstFmt)
+{
+    if (!m_bInit || !m_srcParams) return Fail(MPCVR_E_NOT_VALID_STATE, "InitMediaType has not been called");
+    (void)hipSetDevice(m_device);
+    const int w = m_windowRect.Width(), h = m_windowRect.Height();
+    // everything about the table and the target is answered before anything is drawn (a back buffer Render has yet to allocate cannot overlap them)
+    const bool have = m_BackBuffer.ptr && m_BackBuffer.size >= (size_t)w * 4 * h;
+    HRESULT hr;
+    const char *why = "";
+    if ((hr = Lut3dSurface(have ? m_BackBuffer.ptr : nullptr, w * 4, m_cfg.output_format, w, h, lutDev, n, dst, dstPitch, dstFmt, nullptr, true, &why))) return Fail(hr, why);
+    if (!m_curSample) return MPCVR_S_FALSE;          // nothing to draw, as Render
+    if ((hr = RenderBackBuffer(true)) != MPCVR_S_OK) return hr;
+    hr = Lut3dSurface(m_BackBuffer.ptr, w * 4, m_cfg.output_format, w, h, lutDev, n, dst, dstPitch, dstFmt, m_stream, false, &why);
+    m_launches++;
+    m_lanes.NoteStreamWork();
+    return hr ? Fail(hr, why) : MPCVR_S_OK;
+}
+
+// A batch through the table (include/mpcvr.h: mpcvr_process_batch_lut3d): ProcessBatchTensor with k_lut3d as the chunk's pass and the
+// caller's render targets as what it writes.  Everything about the arguments is answered first; the chunks, their surfaces, lanes and order
+// are RunSurfaceChunks'.
+HRESULT CHipVideoProcessor::ProcessBatchLut3d(int n, const void *const *srcs, const void *lutDev, int lutN, void *const *dsts, int dstPitch, int dstFmt)
+{
+    const BatchRecord record(*this, n > 0 ? n : 0);
+    if (!m_bInit || !m_srcParams) return Fail(MPCVR_E_NOT_VALID_STATE, "InitMediaType has not been called");
+    if (n <= 0) return Fail(MPCVR_E_INVALIDARG, "empty batch");
+    if (!srcs || !dsts || !lutDev) return Fail(MPCVR_E_POINTER, "null array of frames or targets, or null table");
+    for (int i = 0; i < n; i++)
+        if (!srcs[i] || !dsts[i]) return Fail(MPCVR_E_POINTER, "null frame or target in batch");
+    const int w = m_windowRect.Width(), h = m_windowRect.Height();
+    BatchYuvLayout lay;
+    if (!PlanBatchTensor(w, h, n, m_yuvBudget, &lay)) return Fail(MPCVR_E_INVALIDARG, "the pass needs a window width and height of 1 .. 32768");
+    // what the pass refuses, per frame, the table against the target included (the surface is still to be allocated: it cannot overlap either) ...
+    const char *why = "";
+    for (int i = 0; i < n; i++)
+        if (HRESULT bad = Lut3dSurface(nullptr, lay.surfacePitch, m_cfg.output_format, w, h, lutDev, lutN, dsts[i], dstPitch, dstFmt, nullptr, true, &why)) return Fail(bad, why);
+    // ... and the targets against each other
+    std::vector<RtSpan> targets((size_t)n);
+    for (int i = 0; i < n; i++) targets[i] = RowsSpan(dsts[i], (size_t)dstPitch, h, (size_t)4 * w);
+    if (AnyTwoSpansOverlap(targets)) return Fail(MPCVR_E_INVALIDARG, "two targets of the batch overlap");
+
+    (void)hipSetDevice(m_device);
+    if (HRESULT bad = m_planDirty ? UpdatePlan() : MPCVR_S_OK) return bad;
+    const Lut3dParams lp = Lut3dLaunchParams(w, h, lay.surfacePitch, dstPitch, lutDev, lutN);      // (src16 holds for every chunk: every frame of a surface starts on 256 bytes)
+    const bool in10 = m_cfg.output_format == MPCVR_OUT_RGB10A2, out10 = dstFmt == MPCVR_OUT_RGB10A2;
+    const HRESULT hr = RunSurfaceChunks(n, srcs, lay, "lut3d",
+        [&](int at, int m) { return std::vector<RtSpan>(targets.begin() + (size_t)at, targets.begin() + (size_t)(at + m)); },
+        [&](BatchRun &run, int at) {
+            // the targets' table through the frame tables' ring; the lease ends behind the pass
+            SlotLease table;
+            Lut3dParams p = lp;
+            if (HRESULT bad = m_tableRing.SendRows<Lut3dFrame>(run.n, run.on.stream, "lut3d frame table", &table, [&](Lut3dFrame *fr) {
+                    for (int i = 0; i < run.n; i++) {
+                        fr[i] = Lut3dFrame{(const uint8_t *)run.dsts[i], (uint8_t *)dsts[at + i]};
+                        p.dst16 &= ((uintptr_t)dsts[at + i] & 15) == 0;      // the 16-byte stores only if every target of the launch allows them
+                    }
+                })) return bad;
+            p.frames = (const Lut3dFrame *)table.dev;
+            return CheckHip(LaunchLut3d(p, in10, out10, run.on.stream, run.n), "k_lut3d");
+        });
+    m_yuvLastInfo += std::string(";lut3d_table=") + Lut3dPlaceName(Lut3dPlaceFor(lutN));
+    return hr;
 }
 
 }  // namespace mpcvr

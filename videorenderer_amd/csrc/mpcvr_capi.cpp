@@ -169,7 +169,7 @@ int32_t mpcvr_process_batch_dovi(mpcvr_ctx *ctx, int32_t n, const void *const *s
 
 // EXTENSION: a batch as NV12 / P010 (include/mpcvr.h; PlanBatchYuv vp_plan.cpp, CHipVideoProcessor::ProcessBatchYuv)
 static_assert(MPCVR_BATCH_YUV_DEFAULT_BUDGET == mpcvr::kBatchYuvDefaultBudget, "the header and vp_plan.h name one default budget");
-// what the four mpcvr_plan_batch_* functions hand back of a planned layout (each pointer optional)
+// what the mpcvr_plan_batch_* functions hand back of a planned layout (each pointer optional)
 static int32_t ChunkLayoutOut(bool planned, const mpcvr::ChunkLayout &lay, size_t *frame_stride, int32_t *frames_per_chunk, int32_t *chunks)
 {
     if (!planned) return MPCVR_E_INVALIDARG;
@@ -353,6 +353,51 @@ int32_t mpcvr_process_batch_deint(mpcvr_ctx *ctx, int32_t n, const void *const *
 {
     CTX_OR_FAIL();
     return ctx->vp.ProcessBatchDeint(n, frames, field_order, fields_per_frame, mode, dsts, dst_pitch);
+}
+
+// EXTENSION: a 3D colour LUT over rendered frames (include/mpcvr.h; k_lut3d vp_lut3d.hip, the arithmetic vp_lut3d_core.h, Lut3dSurface and
+// CHipVideoProcessor::RenderLut3d / ProcessBatchLut3d hip_video_processor_ext.cpp, PlanLut3dEntries / PlanLut3dValue vp_plan.cpp)
+int32_t mpcvr_plan_lut3d_entries(const float *rgb, int32_t n, uint16_t *entries)
+{
+    if (!rgb || !entries) return MPCVR_E_POINTER;
+    if (n < mpcvr::kLut3dMinN || n > mpcvr::kLut3dMaxN) return MPCVR_E_INVALIDARG;
+    mpcvr::PlanLut3dEntries(rgb, n, entries);
+    return MPCVR_S_OK;
+}
+
+int32_t mpcvr_plan_lut3d_value(int32_t src_fmt, int32_t dst_fmt, const uint16_t *entries_host, int32_t n, uint32_t texel, uint32_t *out)
+{
+    if (!entries_host || !out) return MPCVR_E_POINTER;
+    return mpcvr::PlanLut3dValue(src_fmt, dst_fmt, entries_host, n, texel, out) ? MPCVR_S_OK : MPCVR_E_INVALIDARG;
+}
+
+int32_t mpcvr_lut3d_pass(const void *src, int32_t src_pitch, int32_t src_fmt, int32_t w, int32_t h, const void *lut_dev, int32_t n, void *dst,
+                         int32_t dst_pitch, int32_t dst_fmt, void *stream)
+{
+    return mpcvr::Lut3dSurface(src, src_pitch, src_fmt, w, h, lut_dev, n, dst, dst_pitch, dst_fmt, (hipStream_t)stream, false);
+}
+
+int32_t mpcvr_render_lut3d(mpcvr_ctx *ctx, int32_t field, const void *lut_dev, int32_t n, void *dst, int32_t dst_pitch, int32_t dst_fmt)
+{
+    CTX_OR_FAIL();
+    if (!lut_dev || !dst) return MPCVR_E_POINTER;
+    return ctx->vp.RenderLut3d(field, lut_dev, n, dst, dst_pitch, dst_fmt);
+}
+
+int32_t mpcvr_plan_batch_lut3d(int32_t window_w, int32_t window_h, int32_t n, size_t budget_bytes,
+                               int32_t *surface_pitch, size_t *frame_stride, int32_t *frames_per_chunk, int32_t *chunks)
+{
+    mpcvr::BatchYuvLayout lay;
+    const bool planned = mpcvr::PlanBatchTensor(window_w, window_h, n, budget_bytes, &lay);      // (the same surface of 32-bit texels)
+    if (planned && surface_pitch) *surface_pitch = lay.surfacePitch;
+    return ChunkLayoutOut(planned, lay, frame_stride, frames_per_chunk, chunks);
+}
+
+int32_t mpcvr_process_batch_lut3d(mpcvr_ctx *ctx, int32_t n, const void *const *srcs, const void *lut_dev, int32_t lut_n, void *const *dsts,
+                                  int32_t dst_pitch, int32_t dst_fmt)
+{
+    CTX_OR_FAIL();
+    return ctx->vp.ProcessBatchLut3d(n, srcs, lut_dev, lut_n, dsts, dst_pitch, dst_fmt);
 }
 
 int32_t mpcvr_get_param_blob(mpcvr_ctx *ctx, void *buf, size_t *size) { CTX_OR_FAIL(); return ctx->vp.GetParamBlob(buf, size); }

@@ -11,6 +11,7 @@
 #include "vp_measure.h"
 #include "vp_tensor.h"
 #include "vp_tensor_in.h"
+#include "vp_lut3d.h"
 #include "vp_deint.h"
 #include "vp_crmath.h"      // the shaders' sin / cos as defined functions (the weights the resize shaders compute per pixel are computed here, once)
 
@@ -330,6 +331,39 @@ bool PlanSampleCode(int dtype, int cformat, uint32_t element_bits, float scale, 
 bool PlanBatchSamples(int pitch, int h, int n, size_t budget, ChunkLayout *out)
 {
     return pitch >= 1 && h >= 1 && h <= 32768 && PlanChunks(n, (size_t)3 * (size_t)pitch * (size_t)h, budget, out);
+}
+
+// ------------------------------------------------------------------------------------------------
+// EXTENSION — the 3D LUT pass on the host (include/mpcvr.h: mpcvr_plan_lut3d_entries, mpcvr_plan_lut3d_value): the table's entries from
+// the floats of a .cube file, and one texel through the function of vp_lut3d_core.h the kernel compiles.  No reference line: the reference
+// has no LUT.
+// ------------------------------------------------------------------------------------------------
+void PlanLut3dEntries(const float *rgb, int n, uint16_t *entries)
+{
+    const size_t count = (size_t)n * (size_t)n * (size_t)n;
+    for (size_t i = 0; i < count; i++) {
+        for (int k = 0; k < 3; k++) {
+            const double x = (double)rgb[3 * i + k];
+            // (NaN fails both comparisons' complement: it lands on 0)
+            const double c = x >= 1.0 ? 1.0 : x > 0.0 ? x : 0.0;
+            entries[4 * i + k] = (uint16_t)std::rint(c * 65535.0);
+        }
+        entries[4 * i + 3] = 0;
+    }
+}
+
+bool PlanLut3dValue(int src_fmt, int dst_fmt, const uint16_t *entries, int n, uint32_t texel, uint32_t *out)
+{
+    if ((src_fmt != MPCVR_OUT_BGRA8 && src_fmt != MPCVR_OUT_RGB10A2) || (dst_fmt != MPCVR_OUT_BGRA8 && dst_fmt != MPCVR_OUT_RGB10A2)) return false;
+    if (n < kLut3dMinN || n > kLut3dMaxN) return false;
+    const auto fetch = [entries](uint32_t at) {
+        const uint16_t *e = entries + 4 * (size_t)at;
+        return Lut3dEntry{(uint32_t)e[0] | (uint32_t)e[1] << 16, (uint32_t)e[2] | (uint32_t)e[3] << 16};
+    };
+    const bool in10 = src_fmt == MPCVR_OUT_RGB10A2, out10 = dst_fmt == MPCVR_OUT_RGB10A2;
+    *out = in10 ? (out10 ? Lut3dTexel<true, true>(texel, (uint32_t)n, fetch) : Lut3dTexel<true, false>(texel, (uint32_t)n, fetch))
+                : (out10 ? Lut3dTexel<false, true>(texel, (uint32_t)n, fetch) : Lut3dTexel<false, false>(texel, (uint32_t)n, fetch));
+    return true;
 }
 
 // ------------------------------------------------------------------------------------------------
