@@ -564,6 +564,72 @@ int32_t mpcvr_lut3d_pass(const void *src, int32_t src_pitch, int32_t src_fmt, in
  * drawn or written, when there is no sample (as mpcvr_render). */
 int32_t mpcvr_render_lut3d(mpcvr_ctx *ctx, int32_t field, const void *lut_dev, int32_t n, void *dst, int32_t dst_pitch, int32_t dst_fmt);
 
+/* EXTENSION — debanding of a rendered frame: hashed four-tap smoothing in integers, the step madVR and mpv users know as "deband".  An
+ * 8-bit source with a sky or a fade upscaled 2x, or a PQ -> SDR tone map that stretches the shadows, leaves plateaus a few codes high and
+ * tens of pixels wide, which the ordered dither and the error-diffusion pass quantise faithfully.  The pass replaces a texel by the mean of
+ * four texels around it where that mean is close to it, and quantises last: render MPCVR_OUT_RGB10A2 with the dither off, deband, and let
+ * the pass write 8 bits with its own dither.  The reference has no deband; there is no reference line to cite.  The definition is the
+ * integer text below, modelled bit for bit by tests/deband_model.py (arithmetic: csrc/vp_deband_core.h, which the kernel and
+ * mpcvr_deband_host both compile).
+ *   Surfaces: src and dst are w x h 32-bit texels, w and h in 1 .. 32768, each MPCVR_OUT_BGRA8 (largest code 255) or MPCVR_OUT_RGB10A2
+ *     (1023), chosen independently: maxin and maxout.  The A / X bits of src are ignored, those of dst written as all ones.  Pointers and
+ *     pitches are multiples of 4 and pitches >= 4 w (the rules of mpcvr_lut3d_pass); 16-byte loads and stores are taken where pointers and
+ *     pitches allow them.  NOT in place: the pass reads neighbours, so any overlap of dst with src is refused.
+ *   Parameters (mpcvr_deband_params): range 1 .. 64, iterations 1 .. 4, range * iterations <= 64 — that product is the halo R, the farthest
+ *     a tap lies from its texel in x and in y; threshold 0 .. 4 maxin in QUARTER codes of the source; dither 0 or 1.  A uint32_t seed is
+ *     passed beside the struct.  mpcvr_deband_params_default: range 16, iterations 2, threshold 16 for RGB10A2 and 4 for BGRA8 (one 8-bit
+ *     code either way), dither 1.
+ *   The hash, in 32-bit unsigned wrap-around arithmetic:
+ *       H(x, y, k, seed):  h = x + y 0x9E3779B1 + k 0x85EBCA77 + seed 0xC2B2AE3D;
+ *                          h ^= h >> 16;  h *= 0x7feb352d;  h ^= h >> 15;  h *= 0x846ca68b;  h ^= h >> 16.
+ *   Per texel (x, y), the same for the three channels unless said:
+ *     1. cur = 4 c, c the channel's source code.
+ *     2. For k = 1 .. iterations:  r = range k,  h = H(x, y, k, seed),
+ *          dx = (((h & 0xffff) (2 r + 1)) >> 16) - r,   dy = (((h >> 16) (2 r + 1)) >> 16) - r      (each in -r .. r);
+ *        the four taps are the SOURCE codes at (x + dx, y + dy), (x - dy, y + dx), (x - dx, y - dy), (x + dy, y - dx), each coordinate
+ *        clamped to the surface; s = their sum, per channel; per channel: if |s - cur| k <= threshold then cur = s.
+ *     3. den = 4 maxin;  d = den / 2 with dither 0,  d = ((H(x, y, 0, seed) >> 8) den) >> 24 with dither 1 (one value for the texel's three
+ *        channels, 0 .. den - 1; this one product needs 34 bits and is NOT wrapped: it is the high word of (H & 0xffffff00) den);
+ *        out = (cur maxout + d) / den, which never exceeds maxout; the division is by a compile-time constant.
+ *   Consequences (tests/test_deband.py asserts them):
+ *     - threshold == 0 and dither 0: out == c at equal depths, out == (2 c maxout + maxin) / (2 maxin) across depths — an iteration can
+ *       only replace cur by an equal s;
+ *     - a flat surface is returned unchanged for every threshold (s == cur everywhere), at equal depths with dither 0;
+ *     - a surface of two levels A, B per channel with |A - B| > threshold is returned unchanged at equal depths with dither 0: a tap set
+ *       that crosses the edge m times (m of its four taps lie on the other side) gives |s - cur| = m |A - B| (s and cur are both sums of
+ *       four codes), so m = 0 leaves cur as it is and m >= 1 is refused for every k.
+ * Refusals, with nothing launched and nothing written: MPCVR_E_POINTER for a NULL src, params or dst; MPCVR_E_INVALIDARG for another
+ * src_fmt or dst_fmt, w or h out of range, a parameter outside the rules above, a pointer or pitch that breaks them, and any overlap of
+ * dst with src (a surface counts as the bytes from its first pixel to the last pixel of its last row).  No byte outside dst's pixels is ever
+ * written: not the pitch padding, nothing in front of or behind the surface. */
+typedef struct mpcvr_deband_params {
+    int32_t range;          /* 1 .. 64: iteration k takes its taps up to range * k texels away */
+    int32_t iterations;     /* 1 .. 4, range * iterations <= 64 */
+    int32_t threshold;      /* 0 .. 4 * maxin, quarter codes of the source */
+    int32_t dither;         /* 0: round to nearest, 1: hashed dither on the output quantisation */
+} mpcvr_deband_params;
+/* Host, no GPU: the defaults for a source of src_fmt.  MPCVR_E_POINTER for NULL, MPCVR_E_INVALIDARG for another format. */
+int32_t mpcvr_deband_params_default(int32_t src_fmt, mpcvr_deband_params *params);
+/* Host, no GPU: the whole pass over surfaces in HOST memory, bit for bit what the kernel writes (the core needs neighbours, so it takes a
+ * surface where mpcvr_plan_lut3d_value takes a texel).  The refusals of mpcvr_deband_pass. */
+int32_t mpcvr_deband_host(const void *src_host, int64_t src_pitch, int32_t src_fmt, int32_t w, int32_t h, const mpcvr_deband_params *params,
+                          uint32_t seed, void *dst_host, int64_t dst_pitch, int32_t dst_fmt);
+/* Host, no GPU: *halo = R = range * iterations and *placement = where a launch over a w x h surface reads its taps from: 1 = a tile plus
+ * halo staged in LDS, 0 = 4-byte loads from the surface (the environment variable MPCVR_DEBAND_TAPS = lds | global,
+ * read per launch, overrides the rule where the placement is possible, and this call answers with it).  Each pointer optional.
+ * MPCVR_E_POINTER for NULL params, MPCVR_E_INVALIDARG for what mpcvr_deband_pass refuses about the format, the parameters and the extent. */
+int32_t mpcvr_plan_deband(int32_t src_fmt, const mpcvr_deband_params *params, int32_t w, int32_t h, int32_t *halo, int32_t *placement);
+/* One standalone pass over one device surface, like mpcvr_lut3d_pass; stream = a hipStream_t or NULL.  One kernel launch (k_deband,
+ * csrc/vp_deband.hip); the bytes do not depend on the placement. */
+int32_t mpcvr_deband_pass(const void *src, int32_t src_pitch, int32_t src_fmt, int32_t w, int32_t h, const mpcvr_deband_params *params,
+                          uint32_t seed, void *dst, int32_t dst_pitch, int32_t dst_fmt, void *stream);
+/* mpcvr_render, then the pass from the back buffer over the whole window into dst, ordered exactly as mpcvr_render_lut3d: Process into the
+ * context-owned back buffer with the letterbox cleared to black, on the context stream, the pass queued behind it, and everything queued
+ * later, lanes included, behind the pass.  dst is complete after mpcvr_synchronize; the back buffer is only read.  The source format is the
+ * context's output_format.  Everything mpcvr_deband_pass refuses is answered before anything is drawn.  S_FALSE, with nothing drawn or
+ * written, when there is no sample (as mpcvr_render). */
+int32_t mpcvr_render_deband(mpcvr_ctx *ctx, int32_t field, const mpcvr_deband_params *params, uint32_t seed, void *dst, int32_t dst_pitch, int32_t dst_fmt);
+
 /* Configure — DX11VideoProcessor.cpp:3800-4050: diff each field, rebuild only what changed. */
 int32_t mpcvr_configure(mpcvr_ctx *ctx, const mpcvr_settings *settings);
 
@@ -817,6 +883,24 @@ int32_t mpcvr_plan_batch_lut3d(int32_t window_w, int32_t window_h, int32_t n, si
                                int32_t *surface_pitch, size_t *frame_stride, int32_t *frames_per_chunk, int32_t *chunks);
 int32_t mpcvr_process_batch_lut3d(mpcvr_ctx *ctx, int32_t n, const void *const *srcs, const void *lut_dev, int32_t lut_n,
                                   void *const *dsts, int32_t dst_pitch, int32_t dst_fmt);
+/* EXTENSION — a batch through the deband pass (the pass itself: mpcvr_deband_pass above).  dsts[i] is the render target of frame i, all n
+ * of dst_pitch and dst_fmt.  Target i holds, byte for byte, what
+ *     mpcvr_process_batch(srcs -> n window-sized RGB targets of the context's output_format, black outside the video rect), then
+ *     mpcvr_deband_pass(target i, output_format, window_w, window_h, params, seed + i (mod 2^32), dsts[i], dst_pitch, dst_fmt), n times
+ * leave, with ONE k_deband launch per chunk of frames (its frame dimension) where the composition takes n, and no intermediate targets of
+ * the caller's.  The machinery is that of mpcvr_process_batch_lut3d: the RGB frames live in the context-owned surfaces laid out by
+ * mpcvr_plan_batch_deband — the formulas of mpcvr_plan_batch_tensor — under the budget of mpcvr_set_batch_yuv_budget; chunks, routes, the
+ * letterbox and the order are as described for mpcvr_process_batch_yuv.  The targets are complete after mpcvr_synchronize.
+ * Refusals, answered before anything is drawn, allocated or written: MPCVR_E_NOT_VALID_STATE before mpcvr_set_input; MPCVR_E_POINTER for
+ * a NULL array, entry or params; MPCVR_E_INVALIDARG for n <= 0, whatever mpcvr_deband_pass refuses about the parameters, dst_pitch,
+ * dst_fmt and a dsts[i], and any two targets that overlap each other.
+ * mpcvr_get_last_batch_info afterwards: "launches" counts one pass per chunk, and ";deband_chunks=<k>;deband_lanes=<lane,lane,...>"
+ * follow (the lane of each chunk, -1 = the context stream; the first 64 chunks), then ";deband_taps=lds" or ";deband_taps=global":
+ * where the pass read its taps from. */
+int32_t mpcvr_plan_batch_deband(int32_t window_w, int32_t window_h, int32_t n, size_t budget_bytes,
+                                int32_t *surface_pitch, size_t *frame_stride, int32_t *frames_per_chunk, int32_t *chunks);
+int32_t mpcvr_process_batch_deband(mpcvr_ctx *ctx, int32_t n, const void *const *srcs, const mpcvr_deband_params *params, uint32_t seed,
+                                   void *const *dsts, int32_t dst_pitch, int32_t dst_fmt);
 
 /* Multi-GPU: the parameter blob (colour matrix, luminance scale, gamut matrix, resize phase weights,
  * dither table) a rank-0 context computes and every other rank adopts after an RCCL broadcast.

@@ -180,6 +180,10 @@ class DeintPlane(C.Structure):
                 ("cs", C.c_int32), ("mask", C.c_int32)]
 
 
+class DebandParams(C.Structure):       # mpcvr_deband_params
+    _fields_ = [("range", C.c_int32), ("iterations", C.c_int32), ("threshold", C.c_int32), ("dither", C.c_int32)]
+
+
 class MpcvrError(RuntimeError):
     def __init__(self, hr, msg):
         super().__init__(f"HRESULT 0x{hr & 0xffffffff:08X}: {msg}")
@@ -208,6 +212,7 @@ EXPORTS = [
     "mpcvr_plan_sample_code", "mpcvr_sample_pass", "mpcvr_copy_sample_tensor", "mpcvr_plan_batch_from_tensors", "mpcvr_process_batch_from_tensors",
     "mpcvr_plan_deint_planes", "mpcvr_deint_plane_host", "mpcvr_deint_pass", "mpcvr_copy_sample_fields", "mpcvr_plan_batch_deint", "mpcvr_process_batch_deint",
     "mpcvr_plan_lut3d_entries", "mpcvr_plan_lut3d_value", "mpcvr_lut3d_pass", "mpcvr_render_lut3d", "mpcvr_plan_batch_lut3d", "mpcvr_process_batch_lut3d",
+    "mpcvr_deband_params_default", "mpcvr_deband_host", "mpcvr_plan_deband", "mpcvr_deband_pass", "mpcvr_render_deband", "mpcvr_plan_batch_deband", "mpcvr_process_batch_deband",
 ]
 
 _lib = None
@@ -336,6 +341,13 @@ def load_library():
         "mpcvr_render_lut3d": [vp, i32, vp, i32, vp, i32, i32],
         "mpcvr_plan_batch_lut3d": [i32, i32, i32, C.c_size_t, P(i32), P(C.c_size_t), P(i32), P(i32)],
         "mpcvr_process_batch_lut3d": [vp, i32, P(vp), vp, i32, P(vp), i32, i32],
+        "mpcvr_deband_params_default": [i32, P(DebandParams)],
+        "mpcvr_deband_host": [vp, C.c_int64, i32, i32, i32, P(DebandParams), u32, vp, C.c_int64, i32],
+        "mpcvr_plan_deband": [i32, P(DebandParams), i32, i32, P(i32), P(i32)],
+        "mpcvr_deband_pass": [vp, i32, i32, i32, i32, P(DebandParams), u32, vp, i32, i32, vp],
+        "mpcvr_render_deband": [vp, i32, P(DebandParams), u32, vp, i32, i32],
+        "mpcvr_plan_batch_deband": [i32, i32, i32, C.c_size_t, P(i32), P(C.c_size_t), P(i32), P(i32)],
+        "mpcvr_process_batch_deband": [vp, i32, P(vp), P(DebandParams), u32, P(vp), i32, i32],
     }
     for name, args in sig.items():
         if lib_path != LIB_PATH and not hasattr(L, name):
@@ -577,6 +589,79 @@ def plan_batch_lut3d(window_w, window_h, n, budget_bytes=0):
     hr = load_library().mpcvr_plan_batch_lut3d(int(window_w), int(window_h), int(n), int(budget_bytes), C.byref(pitch), C.byref(stride), C.byref(fpc), C.byref(chunks))
     if hr != S_OK:
         raise MpcvrError(hr, "mpcvr_plan_batch_lut3d")
+    return dict(surface_pitch=pitch.value, frame_stride=stride.value, frames_per_chunk=fpc.value, chunks=chunks.value)
+
+
+def _deband_params(params):
+    """a DebandParams from one, from a dict of its fields, or from a (range, iterations, threshold, dither) sequence"""
+    if isinstance(params, DebandParams):
+        return params
+    if isinstance(params, dict):
+        return DebandParams(**{k: int(v) for k, v in params.items()})
+    return DebandParams(*[int(v) for v in params])
+
+
+def deband_params_default(src_fmt):
+    """(extension) The default parameters of the deband pass for a source of src_fmt (0 = BGRA8, 1 = RGB10A2) as a DebandParams
+    (include/mpcvr.h: mpcvr_deband_params_default): range 16, iterations 2, threshold one 8-bit code, dither on.  Host only."""
+    p = DebandParams()
+    hr = load_library().mpcvr_deband_params_default(int(src_fmt), C.byref(p))
+    if hr != S_OK:
+        raise MpcvrError(hr, "mpcvr_deband_params_default")
+    return p
+
+
+def deband_host(src, src_fmt, params, seed, dst_fmt, src_pitch=None, dst=None, dst_pitch=None, w=None):
+    """(extension) The deband pass over a surface in HOST memory, bit for bit what the kernel writes (include/mpcvr.h: mpcvr_deband_host).
+    `src`: a (h, w) uint32 numpy array, or with src_pitch and w a uint8 array of h rows of src_pitch bytes.  Returns a (h, w) uint32 array,
+    or fills `dst` (uint8, h rows of dst_pitch bytes) and returns it.  No GPU."""
+    import numpy as np
+    if src_pitch is None:
+        src = np.ascontiguousarray(src, dtype=np.uint32)
+        h, w = src.shape
+        src_pitch = 4 * w
+    else:
+        h = (src.size + src_pitch - 4 * w) // src_pitch
+    out = dst
+    if out is None:
+        out, dst_pitch = np.empty((h, w), dtype=np.uint32), 4 * w
+    p = _deband_params(params)
+    hr = load_library().mpcvr_deband_host(C.c_void_p(src.ctypes.data), int(src_pitch), int(src_fmt), int(w), int(h), C.byref(p), int(seed) & 0xffffffff,
+                                          C.c_void_p(out.ctypes.data), int(dst_pitch), int(dst_fmt))
+    if hr != S_OK:
+        raise MpcvrError(hr, "mpcvr_deband_host")
+    return out
+
+
+def plan_deband(src_fmt, params, w, h):
+    """(extension) (halo R = range * iterations, 'lds' | 'global': where a launch over a w x h surface reads its taps from)
+    (include/mpcvr.h: mpcvr_plan_deband; MPCVR_DEBAND_TAPS overrides the rule where possible).  Host only, no GPU."""
+    halo, place = C.c_int32(), C.c_int32()
+    p = _deband_params(params)
+    hr = load_library().mpcvr_plan_deband(int(src_fmt), C.byref(p), int(w), int(h), C.byref(halo), C.byref(place))
+    if hr != S_OK:
+        raise MpcvrError(hr, "mpcvr_plan_deband")
+    return halo.value, "lds" if place.value == 1 else "global"
+
+
+def deband_pass(src, src_pitch, src_fmt, w, h, params, seed, dst, dst_pitch, dst_fmt, stream=None):
+    """(extension) One device surface of 32-bit RGB texels (0 = BGRA8, 1 = RGB10A2) through the deband pass into the surface at `dst`, of
+    either format; dst must not overlap src (include/mpcvr.h: mpcvr_deband_pass).  Complete in stream order."""
+    p = _deband_params(params)
+    hr = load_library().mpcvr_deband_pass(C.c_void_p(_ptr(src)), int(src_pitch), int(src_fmt), int(w), int(h), C.byref(p), int(seed) & 0xffffffff,
+                                          C.c_void_p(_ptr(dst)), int(dst_pitch), int(dst_fmt), C.c_void_p(stream or 0))
+    if hr != S_OK:
+        raise MpcvrError(hr, "mpcvr_deband_pass")
+    return hr
+
+
+def plan_batch_deband(window_w, window_h, n, budget_bytes=0):
+    """(extension) The layout integers of mpcvr_process_batch_deband (include/mpcvr.h: mpcvr_plan_batch_deband): plan_batch_tensor's formulas.
+    dict(surface_pitch, frame_stride, frames_per_chunk, chunks).  Host only, no GPU."""
+    pitch, stride, fpc, chunks = C.c_int32(), C.c_size_t(), C.c_int32(), C.c_int32()
+    hr = load_library().mpcvr_plan_batch_deband(int(window_w), int(window_h), int(n), int(budget_bytes), C.byref(pitch), C.byref(stride), C.byref(fpc), C.byref(chunks))
+    if hr != S_OK:
+        raise MpcvrError(hr, "mpcvr_plan_batch_deband")
     return dict(surface_pitch=pitch.value, frame_stride=stride.value, frames_per_chunk=fpc.value, chunks=chunks.value)
 
 
@@ -1098,6 +1183,41 @@ class VideoProcessor:
         self._keep = keep
         return self._check(self._L.mpcvr_process_batch_lut3d(self._ctx, m, keep[0], C.c_void_p(_ptr(lut)), int(n), keep[1], int(dst_pitch), int(dst_fmt)))
 
+    def RenderDeband(self, params=None, seed=0, dst_fmt=None, out=None, out_pitch=None, field=1):
+        """(extension) Render, then the back buffer through the deband pass (params: a DebandParams, a dict of its fields or None for
+        deband_params_default of the context's output_format) into a target of dst_fmt (OUT_BGRA8 / OUT_RGB10A2; None: the context's
+        output_format) (mpcvr_render_deband).  `out`: a device tensor or address of window_h rows of out_pitch bytes (None: 4 * window_w);
+        else a (H, W, 4) uint8 tensor is allocated.  Returns the target, complete after Synchronize; None when there is no sample
+        (S_FALSE).  The back buffer stays the plain frame."""
+        import torch
+        ww, wh = self._window_size()
+        if dst_fmt is None:
+            dst_fmt = self.settings.output_format
+        p = deband_params_default(self.settings.output_format) if params is None else _deband_params(params)
+        if out is None:
+            out = torch.empty((wh, ww, 4), dtype=torch.uint8, device="cuda")
+            out_pitch = ww * 4
+        elif out_pitch is None:
+            out_pitch = ww * 4
+        self._keep = (out,)
+        hr = self._check(self._L.mpcvr_render_deband(self._ctx, field, C.byref(p), int(seed) & 0xffffffff, C.c_void_p(_ptr(out)), int(out_pitch), int(dst_fmt)))
+        return out if hr == S_OK else None
+
+    def ProcessBatchDeband(self, srcs, params, seed, dsts, dst_pitch, dst_fmt=None):
+        """(extension) ProcessBatch with every frame taken through the deband pass on its way to its render target, frame i with seed + i
+        (mpcvr_process_batch_deband): dsts[i] are device tensors or addresses of window_h rows of dst_pitch bytes, of dst_fmt (None: the
+        context's output_format).  One k_deband launch per chunk; complete after Synchronize.  GetLastBatchInfo adds deband_chunks /
+        deband_lanes / deband_taps."""
+        m = len(srcs)
+        assert m == len(dsts) and m > 0
+        if dst_fmt is None:
+            dst_fmt = self.settings.output_format
+        p = deband_params_default(self.settings.output_format) if params is None else _deband_params(params)
+        arr = C.c_void_p * m
+        keep = (arr(*[_ptr(s) for s in srcs]), arr(*[_ptr(d) for d in dsts]), (srcs, dsts))
+        self._keep = keep
+        return self._check(self._L.mpcvr_process_batch_deband(self._ctx, m, keep[0], C.byref(p), int(seed) & 0xffffffff, keep[1], int(dst_pitch), int(dst_fmt)))
+
     def MeasureBackBuffer(self, hist=None):
         """(extension) The histogram of max(R, G, B) of the frame the last Render / RenderYuv left, over video rect ∩ window
         (mpcvr_measure_backbuffer): a device tensor of 1024 int32 words holding the uint32 counts (allocated when `hist` is None), complete
@@ -1274,7 +1394,7 @@ class VideoProcessor:
         return buf.value.decode()
 
     def GetLastBatchInfo(self):
-        """'frames=<n>;launches=<kernel launches>;lane=<0 | 1: the batch ran on that lane beside its predecessor, -1: on the context stream>;waits=<frames / batches still in flight on other lanes, into memory this batch's targets overlap, that it was ordered behind>[;dovi_runs=...]' of the last ProcessBatch / ProcessBatchDovi / ProcessBatchYuv call, as a dict; behind a ProcessBatchYuv also yuv_chunks and yuv_lanes (the lane of each chunk), behind a ProcessBatchTensor tensor_chunks and tensor_lanes, behind a ProcessBatchFromTensors sample_chunks, behind a ProcessBatchLut3d lut3d_chunks, lut3d_lanes and lut3d_table."""
+        """'frames=<n>;launches=<kernel launches>;lane=<0 | 1: the batch ran on that lane beside its predecessor, -1: on the context stream>;waits=<frames / batches still in flight on other lanes, into memory this batch's targets overlap, that it was ordered behind>[;dovi_runs=...]' of the last ProcessBatch / ProcessBatchDovi / ProcessBatchYuv call, as a dict; behind a ProcessBatchYuv also yuv_chunks and yuv_lanes (the lane of each chunk), behind a ProcessBatchTensor tensor_chunks and tensor_lanes, behind a ProcessBatchFromTensors sample_chunks, behind a ProcessBatchLut3d lut3d_chunks, lut3d_lanes and lut3d_table, behind a ProcessBatchDeband deband_chunks, deband_lanes and deband_taps."""
         buf = C.create_string_buffer(512)
         self._check(self._L.mpcvr_get_last_batch_info(self._ctx, buf, 512))
         d = dict(kv.split("=", 1) for kv in buf.value.decode().split(";"))
@@ -1289,6 +1409,8 @@ class VideoProcessor:
             out.update(deint_chunks=int(d["deint_chunks"]))
         if "lut3d_chunks" in d:      # (only behind a ProcessBatchLut3d: the lane of each chunk, and where the pass read the table from)
             out.update(lut3d_chunks=int(d["lut3d_chunks"]), lut3d_lanes=[int(x) for x in d["lut3d_lanes"].split(",") if x], lut3d_table=d.get("lut3d_table", ""))
+        if "deband_chunks" in d:     # (only behind a ProcessBatchDeband: the lane of each chunk, and where the pass read its taps from)
+            out.update(deband_chunks=int(d["deband_chunks"]), deband_lanes=[int(x) for x in d["deband_lanes"].split(",") if x], deband_taps=d.get("deband_taps", ""))
         return out
 
     def GetLastProcessMs(self):

@@ -51,6 +51,7 @@ SOURCES = [
     ("vp_tensor_in.hip", []),
     ("vp_deint.hip", []),
     ("vp_lut3d.hip", []),
+    ("vp_deband.hip", []),
     ("vp_probe.hip", []),
 ]
 

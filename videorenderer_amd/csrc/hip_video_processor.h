@@ -17,6 +17,7 @@
 #include "vp_tensor_in.h"
 #include "vp_deint.h"
 #include "vp_lut3d.h"
+#include "vp_deband.h"
 #include "vp_launch.h"
 #include "vp_params.h"
 #include "vp_plan.h"
@@ -79,6 +80,12 @@ HRESULT DeintSurface(const void *prev, const void *cur, const void *next, int cf
 HRESULT Lut3dSurface(const void *src, int srcPitch, int srcFmt, int w, int h, const void *lutDev, int n, void *dst, int dstPitch, int dstFmt,
                      hipStream_t stream, bool checkOnly, const char **why = nullptr);
 
+// EXTENSION (mpcvr_deband_pass, include/mpcvr.h): checks every argument, then — unless checkOnly — launches k_deband on `stream`.
+// MPCVR_E_POINTER / MPCVR_E_INVALIDARG with nothing launched or written.  checkOnly takes src = nullptr for a source that is still to be
+// allocated (it cannot overlap the destination)
+HRESULT DebandSurface(const void *src, int srcPitch, int srcFmt, int w, int h, const mpcvr_deband_params *params, uint32_t seed, void *dst, int dstPitch,
+                      int dstFmt, hipStream_t stream, bool checkOnly, const char **why = nullptr);
+
 class CHipVideoProcessor {
 public:
     CHipVideoProcessor();
@@ -137,6 +144,10 @@ public:
     // caller's targets; the batch shares ProcessBatchYuv's surfaces, budget and chunk loop
     HRESULT RenderLut3d(int field, const void *lutDev, int n, void *dst, int dstPitch, int dstFmt);
     HRESULT ProcessBatchLut3d(int n, const void *const *srcs, const void *lutDev, int lutN, void *const *dsts, int dstPitch, int dstFmt);
+    // EXTENSION (mpcvr_render_deband / mpcvr_process_batch_deband): Render / the batch, then k_deband (vp_deband.h) behind it in stream order into
+    // the caller's targets; frame i of a batch takes seed + i; the batch shares ProcessBatchYuv's surfaces, budget and chunk loop
+    HRESULT RenderDeband(int field, const mpcvr_deband_params *params, uint32_t seed, void *dst, int dstPitch, int dstFmt);
+    HRESULT ProcessBatchDeband(int n, const void *const *srcs, const mpcvr_deband_params *params, uint32_t seed, void *const *dsts, int dstPitch, int dstFmt);
     HRESULT SetBatchYuvBudget(size_t bytes) { m_yuvBudget = bytes; return MPCVR_S_OK; }
     std::string GetLastBatchInfo() const;
     HRESULT ProcessBatchDovi(int n, const void *const *srcs, void *const *dsts, int rtPitch, const mpcvr_dovi_metadata *rpus);
@@ -489,7 +500,7 @@ private:
     };
     YuvSurface m_yuvSurf[FrameLanes::kFrameLanes];
     size_t m_yuvBudget = 0;            // SetBatchYuvBudget; 0: kBatchYuvDefaultBudget
-    std::string m_yuvLastInfo;         // ";yuv_chunks=..;yuv_lanes=.." (";tensor_chunks=..;tensor_lanes=..", ";lut3d_chunks=..;lut3d_lanes=..;lut3d_table=..") of the last batch call, if it was a ProcessBatchYuv (ProcessBatchTensor, ProcessBatchLut3d)
+    std::string m_yuvLastInfo;         // ";yuv_chunks=..;yuv_lanes=.." (";tensor_chunks=..;tensor_lanes=..", ";lut3d_chunks=..;lut3d_lanes=..;lut3d_table=..", ";deband_chunks=..;deband_lanes=..;deband_taps=..") of the last batch call, if it was a ProcessBatchYuv (ProcessBatchTensor, ProcessBatchLut3d, ProcessBatchDeband)
     DevBuffer m_sampleSurf;            // ProcessBatchFromTensors / ProcessBatchDeint: the samples of one chunk side by side (PlanBatchSamples), written and read in stream order on the context stream
     // the chunk loop of ProcessBatchYuv / ProcessBatchTensor: surfaces, lanes and order; writesOf(at, m): what the chunk writes for the caller, pass(run, at): its pass
     template <class WritesOf, class Pass>

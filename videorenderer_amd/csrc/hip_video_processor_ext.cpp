@@ -850,4 +850,109 @@ HRESULT CHipVideoProcessor::ProcessBatchLut3d(int n, const void *const *srcs, co
     return hr;
 }
 
+// ------------------------------------------------------------------------------------------------
+// EXTENSION — debanding of rendered frames (include/mpcvr.h: mpcvr_deband_pass, mpcvr_render_deband, mpcvr_process_batch_deband;
+// kernel: vp_deband.hip).  No reference line: the reference has no deband.
+// ------------------------------------------------------------------------------------------------
+// What a k_deband launch is given, but for its surfaces and seed(s), as Lut3dLaunchParams
+static DebandParams DebandLaunchParams(int w, int h, int srcPitch, int dstPitch, const mpcvr_deband_params &params)
+{
+    DebandParams p{};
+    p.src_pitch = srcPitch; p.dst_pitch = dstPitch; p.w = w; p.h = h;
+    p.a = DebandArgs{params.range, params.iterations, params.threshold, params.dither};
+    p.src16 = (srcPitch & 15) == 0;
+    p.dst16 = (dstPitch & 15) == 0;
+    return p;
+}
+
+HRESULT DebandSurface(const void *src, int srcPitch, int srcFmt, int w, int h, const mpcvr_deband_params *params, uint32_t seed, void *dst, int dstPitch,
+                      int dstFmt, hipStream_t stream, bool checkOnly, const char **why)
+{
+    const char *dummy;
+    if (!why) why = &dummy;
+    if ((!src && !checkOnly) || !params || !dst) { *why = "null surface, parameters or destination"; return MPCVR_E_POINTER; }      // (checkOnly: a source still to be allocated)
+    if ((srcFmt != MPCVR_OUT_BGRA8 && srcFmt != MPCVR_OUT_RGB10A2) || (dstFmt != MPCVR_OUT_BGRA8 && dstFmt != MPCVR_OUT_RGB10A2)) {
+        *why = "source and destination BGRA8 or RGB10A2"; return MPCVR_E_INVALIDARG;
+    }
+    if (w < 1 || h < 1 || w > 32768 || h > 32768) { *why = "width and height must be 1 .. 32768"; return MPCVR_E_INVALIDARG; }
+    const DebandArgs a{params->range, params->iterations, params->threshold, params->dither};
+    if (!DebandArgsValid(a, srcFmt == MPCVR_OUT_RGB10A2)) { *why = "range 1 .. 64, iterations 1 .. 4, range * iterations <= 64, threshold 0 .. 4 maxin, dither 0 / 1"; return MPCVR_E_INVALIDARG; }
+    if (srcPitch < 4 * w || dstPitch < 4 * w) { *why = "pitch smaller than a row"; return MPCVR_E_INVALIDARG; }
+    if (((uintptr_t)src | (uintptr_t)srcPitch | (uintptr_t)dst | (uintptr_t)dstPitch) & 3) { *why = "surfaces and pitches must be multiples of 4"; return MPCVR_E_INVALIDARG; }
+    const RtSpan s = RowsSpan(src, (size_t)srcPitch, h, (size_t)4 * w), d = RowsSpan(dst, (size_t)dstPitch, h, (size_t)4 * w);
+    // the pass reads neighbours: no overlap at all, in place included
+    if (src && d.Overlaps(s)) { *why = "the destination overlaps the source"; return MPCVR_E_INVALIDARG; }
+    if (checkOnly) return MPCVR_S_OK;
+    DebandParams p = DebandLaunchParams(w, h, srcPitch, dstPitch, *params);
+    p.src = (const uint8_t *)src; p.dst = (uint8_t *)dst; p.seed = seed;
+    p.src16 &= (s.lo & 15) == 0;
+    p.dst16 &= (d.lo & 15) == 0;
+    if (LaunchDeband(p, srcFmt == MPCVR_OUT_RGB10A2, dstFmt == MPCVR_OUT_RGB10A2, stream) != hipSuccess) { *why = "k_deband launch failed"; return MPCVR_E_FAIL; }
+    return MPCVR_S_OK;
+}
+
+// Render, then the pass from the back buffer over the whole window into the caller's target, ordered as RenderLut3d
+HRESULT CHipVideoProcessor::RenderDeband(int /*field*/, const mpcvr_deband_params *params, uint32_t seed, void *dst, int dstPitch, int dstFmt)
+{
+    if (!m_bInit || !m_srcParams) return Fail(MPCVR_E_NOT_VALID_STATE, "InitMediaType has not been called");
+    (void)hipSetDevice(m_device);
+    const int w = m_windowRect.Width(), h = m_windowRect.Height();
+    // everything about the parameters and the target is answered before anything is drawn (a back buffer Render has yet to allocate cannot overlap it)
+    const bool have = m_BackBuffer.ptr && m_BackBuffer.size >= (size_t)w * 4 * h;
+    HRESULT hr;
+    const char *why = "";
+    if ((hr = DebandSurface(have ? m_BackBuffer.ptr : nullptr, w * 4, m_cfg.output_format, w, h, params, seed, dst, dstPitch, dstFmt, nullptr, true, &why))) return Fail(hr, why);
+    if (!m_curSample) return MPCVR_S_FALSE;          // nothing to draw, as Render
+    if ((hr = RenderBackBuffer(true)) != MPCVR_S_OK) return hr;
+    hr = DebandSurface(m_BackBuffer.ptr, w * 4, m_cfg.output_format, w, h, params, seed, dst, dstPitch, dstFmt, m_stream, false, &why);
+    m_launches++;
+    m_lanes.NoteStreamWork();
+    return hr ? Fail(hr, why) : MPCVR_S_OK;
+}
+
+// A batch through the pass (include/mpcvr.h: mpcvr_process_batch_deband): ProcessBatchLut3d with k_deband as the chunk's pass and a seed
+// per frame.  Everything about the arguments is answered first; the chunks, their surfaces, lanes and order are RunSurfaceChunks'.
+HRESULT CHipVideoProcessor::ProcessBatchDeband(int n, const void *const *srcs, const mpcvr_deband_params *params, uint32_t seed, void *const *dsts, int dstPitch, int dstFmt)
+{
+    const BatchRecord record(*this, n > 0 ? n : 0);
+    if (!m_bInit || !m_srcParams) return Fail(MPCVR_E_NOT_VALID_STATE, "InitMediaType has not been called");
+    if (n <= 0) return Fail(MPCVR_E_INVALIDARG, "empty batch");
+    if (!srcs || !dsts || !params) return Fail(MPCVR_E_POINTER, "null array of frames or targets, or null parameters");
+    for (int i = 0; i < n; i++)
+        if (!srcs[i] || !dsts[i]) return Fail(MPCVR_E_POINTER, "null frame or target in batch");
+    const int w = m_windowRect.Width(), h = m_windowRect.Height();
+    BatchYuvLayout lay;
+    if (!PlanBatchTensor(w, h, n, m_yuvBudget, &lay)) return Fail(MPCVR_E_INVALIDARG, "the pass needs a window width and height of 1 .. 32768");
+    // what the pass refuses, per frame (the surface is still to be allocated: it cannot overlap a target) ...
+    const char *why = "";
+    for (int i = 0; i < n; i++)
+        if (HRESULT bad = DebandSurface(nullptr, lay.surfacePitch, m_cfg.output_format, w, h, params, seed, dsts[i], dstPitch, dstFmt, nullptr, true, &why)) return Fail(bad, why);
+    // ... and the targets against each other
+    std::vector<RtSpan> targets((size_t)n);
+    for (int i = 0; i < n; i++) targets[i] = RowsSpan(dsts[i], (size_t)dstPitch, h, (size_t)4 * w);
+    if (AnyTwoSpansOverlap(targets)) return Fail(MPCVR_E_INVALIDARG, "two targets of the batch overlap");
+
+    (void)hipSetDevice(m_device);
+    if (HRESULT bad = m_planDirty ? UpdatePlan() : MPCVR_S_OK) return bad;
+    const DebandParams lp = DebandLaunchParams(w, h, lay.surfacePitch, dstPitch, *params);      // (src16 holds for every chunk: every frame of a surface starts on 256 bytes)
+    const bool in10 = m_cfg.output_format == MPCVR_OUT_RGB10A2, out10 = dstFmt == MPCVR_OUT_RGB10A2;
+    const HRESULT hr = RunSurfaceChunks(n, srcs, lay, "deband",
+        [&](int at, int m) { return std::vector<RtSpan>(targets.begin() + (size_t)at, targets.begin() + (size_t)(at + m)); },
+        [&](BatchRun &run, int at) {
+            // the targets' and seeds' table through the frame tables' ring; the lease ends behind the pass
+            SlotLease table;
+            DebandParams p = lp;
+            if (HRESULT bad = m_tableRing.SendRows<DebandFrame>(run.n, run.on.stream, "deband frame table", &table, [&](DebandFrame *fr) {
+                    for (int i = 0; i < run.n; i++) {
+                        fr[i] = DebandFrame{(const uint8_t *)run.dsts[i], (uint8_t *)dsts[at + i], seed + (uint32_t)(at + i), 0u};
+                        p.dst16 &= ((uintptr_t)dsts[at + i] & 15) == 0;      // the 16-byte stores only if every target of the launch allows them
+                    }
+                })) return bad;
+            p.frames = (const DebandFrame *)table.dev;
+            return CheckHip(LaunchDeband(p, in10, out10, run.on.stream, run.n), "k_deband");
+        });
+    m_yuvLastInfo += std::string(";deband_taps=") + DebandPlaceName(DebandPlaceFor(params->range * params->iterations, w, h));
+    return hr;
+}
+
 }  // namespace mpcvr

@@ -400,6 +400,66 @@ int32_t mpcvr_process_batch_lut3d(mpcvr_ctx *ctx, int32_t n, const void *const *
     return ctx->vp.ProcessBatchLut3d(n, srcs, lut_dev, lut_n, dsts, dst_pitch, dst_fmt);
 }
 
+// EXTENSION: debanding of rendered frames (include/mpcvr.h; k_deband vp_deband.hip, the arithmetic vp_deband_core.h, DebandSurface and
+// CHipVideoProcessor::RenderDeband / ProcessBatchDeband hip_video_processor_ext.cpp, PlanDebandDefaults / PlanDebandHost vp_plan.cpp)
+int32_t mpcvr_deband_params_default(int32_t src_fmt, mpcvr_deband_params *params)
+{
+    if (!params) return MPCVR_E_POINTER;
+    mpcvr::DebandArgs a;
+    if (!mpcvr::PlanDebandDefaults(src_fmt, &a)) return MPCVR_E_INVALIDARG;
+    *params = mpcvr_deband_params{a.range, a.iterations, a.threshold, a.dither};
+    return MPCVR_S_OK;
+}
+
+int32_t mpcvr_deband_host(const void *src_host, int64_t src_pitch, int32_t src_fmt, int32_t w, int32_t h, const mpcvr_deband_params *params,
+                          uint32_t seed, void *dst_host, int64_t dst_pitch, int32_t dst_fmt)
+{
+    if (!src_host || !params || !dst_host) return MPCVR_E_POINTER;
+    const mpcvr::DebandArgs a{params->range, params->iterations, params->threshold, params->dither};
+    return mpcvr::PlanDebandHost(src_host, src_pitch, src_fmt, w, h, a, seed, dst_host, dst_pitch, dst_fmt) ? MPCVR_S_OK : MPCVR_E_INVALIDARG;
+}
+
+int32_t mpcvr_plan_deband(int32_t src_fmt, const mpcvr_deband_params *params, int32_t w, int32_t h, int32_t *halo, int32_t *placement)
+{
+    if (!params) return MPCVR_E_POINTER;
+    if ((src_fmt != MPCVR_OUT_BGRA8 && src_fmt != MPCVR_OUT_RGB10A2) || w < 1 || h < 1 || w > 32768 || h > 32768 ||
+        !mpcvr::DebandArgsValid(mpcvr::DebandArgs{params->range, params->iterations, params->threshold, params->dither}, src_fmt == MPCVR_OUT_RGB10A2))
+        return MPCVR_E_INVALIDARG;
+    const int R = params->range * params->iterations;
+    if (halo) *halo = R;
+    if (placement) *placement = mpcvr::DebandPlaceFor(R, w, h);
+    return MPCVR_S_OK;
+}
+
+int32_t mpcvr_deband_pass(const void *src, int32_t src_pitch, int32_t src_fmt, int32_t w, int32_t h, const mpcvr_deband_params *params,
+                          uint32_t seed, void *dst, int32_t dst_pitch, int32_t dst_fmt, void *stream)
+{
+    return mpcvr::DebandSurface(src, src_pitch, src_fmt, w, h, params, seed, dst, dst_pitch, dst_fmt, (hipStream_t)stream, false);
+}
+
+int32_t mpcvr_render_deband(mpcvr_ctx *ctx, int32_t field, const mpcvr_deband_params *params, uint32_t seed, void *dst, int32_t dst_pitch, int32_t dst_fmt)
+{
+    CTX_OR_FAIL();
+    if (!params || !dst) return MPCVR_E_POINTER;
+    return ctx->vp.RenderDeband(field, params, seed, dst, dst_pitch, dst_fmt);
+}
+
+int32_t mpcvr_plan_batch_deband(int32_t window_w, int32_t window_h, int32_t n, size_t budget_bytes,
+                                int32_t *surface_pitch, size_t *frame_stride, int32_t *frames_per_chunk, int32_t *chunks)
+{
+    mpcvr::BatchYuvLayout lay;
+    const bool planned = mpcvr::PlanBatchTensor(window_w, window_h, n, budget_bytes, &lay);      // (the same surface of 32-bit texels)
+    if (planned && surface_pitch) *surface_pitch = lay.surfacePitch;
+    return ChunkLayoutOut(planned, lay, frame_stride, frames_per_chunk, chunks);
+}
+
+int32_t mpcvr_process_batch_deband(mpcvr_ctx *ctx, int32_t n, const void *const *srcs, const mpcvr_deband_params *params, uint32_t seed,
+                                   void *const *dsts, int32_t dst_pitch, int32_t dst_fmt)
+{
+    CTX_OR_FAIL();
+    return ctx->vp.ProcessBatchDeband(n, srcs, params, seed, dsts, dst_pitch, dst_fmt);
+}
+
 int32_t mpcvr_get_param_blob(mpcvr_ctx *ctx, void *buf, size_t *size) { CTX_OR_FAIL(); return ctx->vp.GetParamBlob(buf, size); }
 int32_t mpcvr_get_fused_tables(mpcvr_ctx *ctx, void *buf, size_t *size) { CTX_OR_FAIL(); return ctx->vp.GetFusedTables(buf, size); }
 int32_t mpcvr_set_param_blob(mpcvr_ctx *ctx, const void *buf, size_t size) { CTX_OR_FAIL(); return ctx->vp.SetParamBlob(buf, size); }

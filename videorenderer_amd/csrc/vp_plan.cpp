@@ -12,6 +12,7 @@
 #include "vp_tensor.h"
 #include "vp_tensor_in.h"
 #include "vp_lut3d.h"
+#include "vp_deband.h"
 #include "vp_deint.h"
 #include "vp_crmath.h"      // the shaders' sin / cos as defined functions (the weights the resize shaders compute per pixel are computed here, once)
 
@@ -363,6 +364,31 @@ bool PlanLut3dValue(int src_fmt, int dst_fmt, const uint16_t *entries, int n, ui
     const bool in10 = src_fmt == MPCVR_OUT_RGB10A2, out10 = dst_fmt == MPCVR_OUT_RGB10A2;
     *out = in10 ? (out10 ? Lut3dTexel<true, true>(texel, (uint32_t)n, fetch) : Lut3dTexel<true, false>(texel, (uint32_t)n, fetch))
                 : (out10 ? Lut3dTexel<false, true>(texel, (uint32_t)n, fetch) : Lut3dTexel<false, false>(texel, (uint32_t)n, fetch));
+    return true;
+}
+
+// ------------------------------------------------------------------------------------------------
+// EXTENSION — the deband pass on the host (include/mpcvr.h: mpcvr_deband_params_default, mpcvr_deband_host): the defaults, and a whole
+// surface through the function of vp_deband_core.h the kernel compiles.  No reference line: the reference has no deband.
+// ------------------------------------------------------------------------------------------------
+bool PlanDebandDefaults(int src_fmt, DebandArgs *a)
+{
+    if (src_fmt != MPCVR_OUT_BGRA8 && src_fmt != MPCVR_OUT_RGB10A2) return false;
+    *a = DebandArgs{16, 2, src_fmt == MPCVR_OUT_RGB10A2 ? 16 : 4, 1};      // (the threshold: one 8-bit code in quarter codes of the source)
+    return true;
+}
+
+bool PlanDebandHost(const void *src, int64_t src_pitch, int src_fmt, int w, int h, const DebandArgs &a, uint32_t seed, void *dst, int64_t dst_pitch, int dst_fmt)
+{
+    if ((src_fmt != MPCVR_OUT_BGRA8 && src_fmt != MPCVR_OUT_RGB10A2) || (dst_fmt != MPCVR_OUT_BGRA8 && dst_fmt != MPCVR_OUT_RGB10A2)) return false;
+    if (w < 1 || h < 1 || w > 32768 || h > 32768 || !DebandArgsValid(a, src_fmt == MPCVR_OUT_RGB10A2)) return false;
+    if (src_pitch < (int64_t)4 * w || dst_pitch < (int64_t)4 * w) return false;
+    if (((uintptr_t)src | (uintptr_t)src_pitch | (uintptr_t)dst | (uintptr_t)dst_pitch) & 3) return false;
+    // a surface: the bytes from its first pixel to the last pixel of its last row
+    const uintptr_t s0 = (uintptr_t)src, s1 = s0 + (size_t)(h - 1) * (size_t)src_pitch + (size_t)4 * w;
+    const uintptr_t d0 = (uintptr_t)dst, d1 = d0 + (size_t)(h - 1) * (size_t)dst_pitch + (size_t)4 * w;
+    if (s0 < d1 && d0 < s1) return false;
+    DebandSurfaceHost((const uint8_t *)src, src_pitch, src_fmt == MPCVR_OUT_RGB10A2, w, h, a, seed, (uint8_t *)dst, dst_pitch, dst_fmt == MPCVR_OUT_RGB10A2);
     return true;
 }
 
