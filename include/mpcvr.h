@@ -119,6 +119,7 @@ typedef struct mpcvr_settings {
     int32_t  bDeintBlend;         /* blend-deinterlace 4:2:0 samples flagged interlaced (mpcvr_set_sample_format) */
     int32_t  bConvertToSdr;       /*                           default 1         */
     int32_t  iSDRDisplayNits;     /* 25..400                   default 125       */
+                                  /* (24 and 401 are MPCVR_E_INVALIDARG from mpcvr_create and mpcvr_configure, which then changes nothing) */
     int32_t  output_format;       /* MPCVR_OUT_*               default BGRA8     */
     uint32_t flags;
 } mpcvr_settings;
@@ -194,7 +195,11 @@ int32_t mpcvr_set_sample_format(mpcvr_ctx *ctx, int32_t frame_format);
  * m_iHdrLocalToneMappingType (0 off, 1 ACES, 2 Reinhard, 3 Habel, 4 Moebius, 5 BT.2390, 6 ST 2094-10), display_max_nits =
  * m_iHdrDisplayMaxNits: ps_hdr10_tonemap.hlsl then runs as a post-scale step once mpcvr_set_hdr_metadata was called. */
 int32_t mpcvr_set_hdr_output(mpcvr_ctx *ctx, int32_t enable, int32_t tone_map_type, float display_max_nits);
-/* the values Render() passes to SetHDR10ShaderParams (:907-917, :2716-2727), sanitised the same way */
+/* the values Render() passes to SetHDR10ShaderParams (:907-917, :2716-2727), sanitised the same way: min <= 0 is 0, a mastering peak <= 10 is
+ * 1000, MaxCLL <= 10 is the mastering peak, MaxFALL <= 1 is MaxCLL, and a display peak outside 100 .. 10000 is drawn as 1000
+ * (mpcvr_plan_hdr10_params returns the sanitised values without a GPU).  There is no upper clamp, as in the reference: keep the peaks within
+ * what HDR10's 16-bit fields carry (<= 65535 nits).  The values travel with each launch: changing them, or the display peak, between two
+ * mpcvr_process calls needs no mpcvr_synchronize. */
 int32_t mpcvr_set_hdr_metadata(mpcvr_ctx *ctx, float min_mastering_nits, float max_mastering_nits, float max_cll, float max_fall);
 
 /* Dolby Vision RPU of the next sample(s): the fields of MediaSideDataDOVIMetadata (Include/IMediaSideData.h:154-330) the

@@ -145,14 +145,17 @@ CORR = {1: "fix_bt2020", 2: "fix_ycgco", 3: "fixconvert_pq_to_sdr", 4: "fixconve
 @pytest.mark.parametrize("kind", sorted(CORR))
 @pytest.mark.parametrize("fmts", [(8, 8), (10, 10), (10, 8)])
 def test_correction_shaders_against_live_reference_hlsl(oracle, kind, fmts):
-    """m_pPSCorrection shaders (ps_fix_*.hlsl, ps_fixconvert_*.hlsl, ps_convert_*.hlsl) vs orc_correction_pass."""
+    """m_pPSCorrection shaders (ps_fix_*.hlsl, ps_fixconvert_*.hlsl, ps_convert_*.hlsl) vs orc_correction_pass.  Kinds 3, 4 and 5 read
+    LuminanceScale = 10000 / nits: they run at every value of tests/tone_params.py's SDR_NITS (both ends of 25 .. 400, their neighbours, the
+    default 125 and values in between); kinds 1, 2 and 6 do not read it and keep their single run."""
     _live()
     import ref_hlsl as R
+    from tests.tone_params import SDR_NITS
+    assert 125 in SDR_NITS
     src_fmt, dst_fmt = fmts
     rng = np.random.default_rng(100 * kind + src_fmt + dst_fmt)
     h, w = 24, 64
     src = rng.integers(0, 2 ** 32, size=(h, w), dtype=np.uint32)
-    got = oracle.correction_pass(kind, src, src_fmt, dst_fmt)
     tex = np.zeros((h, w, 4), np.float32)
     if src_fmt == 10:
         for k in range(3):
@@ -161,18 +164,23 @@ def test_correction_shaders_against_live_reference_hlsl(oracle, kind, fmts):
     else:
         for k, sh_ in enumerate((16, 8, 0, 24)):
             tex[..., k] = ((src >> sh_) & 255).astype(np.float32) / np.float32(255)
-    rt = np.zeros((h, w, 4), np.float32)
     fn = R.find_shader("ps_" + CORR[kind])
-    lum = R.words(np.float32(10000.0) / np.float32(125), np.float32(0))
-    R.draw(fn, [tex], rt, dst_fmt, (0, 0, w, h), ((0.0, 0.0), (1.0, 0.0), (0.0, 1.0)), samplers=[(0, 0)], cbs=[lum])
-    if dst_fmt == 10:
-        ref = np.stack([np.floor(rt[..., k] * np.float32(1023) + np.float32(0.5)) for k in range(3)], -1).astype(np.int32)
-        gch = np.stack([(got >> (10 * k)) & 1023 for k in range(3)], -1).astype(np.int32)
-    else:
-        ref = np.stack([np.floor(rt[..., k] * np.float32(255) + np.float32(0.5)) for k in range(3)], -1).astype(np.int32)
-        gch = np.stack([(got >> sh_) & 255 for sh_ in (16, 8, 0)], -1).astype(np.int32)
-    d = np.abs(ref - gch)
-    assert d.max() == 0, (int(d.max()), float((d > 0).mean()))
+    seen = set()
+    for nits in (SDR_NITS if kind in (3, 4, 5) else (125,)):
+        got = oracle.correction_pass(kind, src, src_fmt, dst_fmt, sdr_nits=nits)
+        rt = np.zeros((h, w, 4), np.float32)
+        lum = R.words(np.float32(10000.0) / np.float32(nits), np.float32(0))
+        R.draw(fn, [tex], rt, dst_fmt, (0, 0, w, h), ((0.0, 0.0), (1.0, 0.0), (0.0, 1.0)), samplers=[(0, 0)], cbs=[lum])
+        if dst_fmt == 10:
+            ref = np.stack([np.floor(rt[..., k] * np.float32(1023) + np.float32(0.5)) for k in range(3)], -1).astype(np.int32)
+            gch = np.stack([(got >> (10 * k)) & 1023 for k in range(3)], -1).astype(np.int32)
+        else:
+            ref = np.stack([np.floor(rt[..., k] * np.float32(255) + np.float32(0.5)) for k in range(3)], -1).astype(np.int32)
+            gch = np.stack([(got >> sh_) & 255 for sh_ in (16, 8, 0)], -1).astype(np.int32)
+        d = np.abs(ref - gch)
+        assert d.max() == 0, (nits, int(d.max()), float((d > 0).mean()))
+        seen.add(ref.tobytes())
+    assert len(seen) == (len(SDR_NITS) if kind in (3, 4, 5) else 1)        # the nits reach the shader: nine different surfaces
 
 
 # ---- the rewrite itself (host logic; no reference needed) ----
