@@ -939,6 +939,13 @@ int32_t mpcvr_get_path_info(mpcvr_ctx *ctx, char *buf, size_t buf_size); /* e.g.
  * per-frame tables or went frame by frame.  After mpcvr_process_batch_yuv ";yuv_chunks=<k>;yuv_lanes=<lane,lane,...>" follow and the launches
  * include one pass per chunk; after every other batch call the string is as above. */
 int32_t mpcvr_get_last_batch_info(mpcvr_ctx *ctx, char *buf, size_t buf_size);
+/* Once the context has launched the exact-2x fused kernel, ";up2x=bp" or ";up2x=generic" follows these fields (in front of the fields of
+ * the extension calls): the form of the context's last such launch since the last batch call began, single frames included (bp: the bi-planar twin, which loads and converts every chroma texel once; generic: the kernel
+ * every launch may take; MPCVR_UP2X_NO_BP=1 in the environment keeps to it).  A batch call that launches none reports neither.
+ * Host, no GPU: 1 when the twin's carried chroma row is the row the generic kernel would load in every iteration of a launch over
+ * source rows rect_t .. rect_t + h - 1 of a sample with ch chroma rows, for the siting coefficients (vk1, vk2, vk3) of
+ * 4 v'(sy) = vk1 sy + vk2 (sy & ~1) + vk3; 0 otherwise (the launch then runs the generic kernel). */
+int32_t mpcvr_plan_up2x_row_carry(int32_t vk1, int32_t vk2, int32_t vk3, int32_t rect_t, int32_t h, int32_t ch);
 const char *mpcvr_last_error(mpcvr_ctx *ctx);
 const char *mpcvr_version(void);
 

@@ -198,7 +198,7 @@ EXPORTS = [
     "mpcvr_get_backbuffer", "mpcvr_get_current_image", "mpcvr_get_displayed_image", "mpcvr_flush", "mpcvr_reset", "mpcvr_process_batch", "mpcvr_process_batch_dovi",
     "mpcvr_get_param_blob", "mpcvr_set_param_blob", "mpcvr_broadcast_param_blob_begin", "mpcvr_broadcast_param_blob_end",
     "mpcvr_broadcast_param_blob", "mpcvr_get_color_matrix", "mpcvr_get_extfmt",
-    "mpcvr_get_frame_bytes", "mpcvr_get_fused_tables", "mpcvr_get_path_info", "mpcvr_get_last_batch_info", "mpcvr_last_error", "mpcvr_version",
+    "mpcvr_get_frame_bytes", "mpcvr_get_fused_tables", "mpcvr_get_path_info", "mpcvr_get_last_batch_info", "mpcvr_plan_up2x_row_carry", "mpcvr_last_error", "mpcvr_version",
     "mpcvr_get_last_process_ms", "mpcvr_get_last_timings",
     "mpcvr_plan_frame_layout", "mpcvr_plan_color_matrix", "mpcvr_plan_gamut_2020_to_709", "mpcvr_plan_pq_lut",
     "mpcvr_plan_upscale_weights", "mpcvr_plan_axis_taps", "mpcvr_plan_describe", "mpcvr_plan_final_pass_multiplier",
@@ -287,6 +287,7 @@ def load_library():
         "mpcvr_get_fused_tables": [vp, vp, P(C.c_size_t)],
         "mpcvr_get_path_info": [vp, C.c_char_p, C.c_size_t],
         "mpcvr_get_last_batch_info": [vp, C.c_char_p, C.c_size_t],
+        "mpcvr_plan_up2x_row_carry": [i32, i32, i32, i32, i32, i32],
         "mpcvr_get_last_process_ms": [vp, P(f)],
         "mpcvr_get_last_timings": [vp, P(f), P(f), P(f), P(f)],
         "mpcvr_plan_frame_layout": [i32, i32, i32, P(i32), P(C.c_size_t)],
@@ -378,6 +379,12 @@ def plan_frame_layout(cformat, width, height):
     if hr < 0:
         raise MpcvrError(hr, "mpcvr_plan_frame_layout")
     return nbytes.value, pitch.value
+
+
+def plan_up2x_row_carry(vk1, vk2, vk3, rect_t, h, ch):
+    """True when the exact-2x kernel's bi-planar twin may carry a chroma row from one iteration to the next over source rows
+    rect_t .. rect_t + h - 1 of a sample with ch chroma rows (include/mpcvr.h: mpcvr_plan_up2x_row_carry)."""
+    return bool(load_library().mpcvr_plan_up2x_row_carry(vk1, vk2, vk3, rect_t, h, ch))
 
 
 def plan_color_matrix(cformat, rect_w, rect_h, extfmt=0, brightness=0.0, contrast=1.0, hue=0.0, saturation=1.0):
@@ -1412,6 +1419,13 @@ class VideoProcessor:
         if "deband_chunks" in d:     # (only behind a ProcessBatchDeband: the lane of each chunk, and where the pass read its taps from)
             out.update(deband_chunks=int(d["deband_chunks"]), deband_lanes=[int(x) for x in d["deband_lanes"].split(",") if x], deband_taps=d.get("deband_taps", ""))
         return out
+
+    def GetUp2xForm(self):
+        """'bp' / 'generic': the form of the context's last exact-2x fused launch since its last batch call began (";up2x=" of
+        mpcvr_get_last_batch_info: the bi-planar twin k_fused_up2x_bp, or k_fused_up2x); None when it has launched none."""
+        buf = C.create_string_buffer(512)
+        self._check(self._L.mpcvr_get_last_batch_info(self._ctx, buf, 512))
+        return dict(kv.split("=", 1) for kv in buf.value.decode().split(";")).get("up2x")
 
     def GetLastProcessMs(self):
         ms = C.c_float()

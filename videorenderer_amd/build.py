@@ -31,6 +31,10 @@ SOURCES = [
     ("vp_fused_up2x_nt4.hip", []),
     ("vp_fused_up2x_nt5.hip", []),
     ("vp_fused_up2x_nt6.hip", []),
+    ("vp_fused_up2x_bp.hip", []),
+    ("vp_fused_up2x_bp_nt4.hip", []),
+    ("vp_fused_up2x_bp_nt5.hip", []),
+    ("vp_fused_up2x_bp_nt6.hip", []),
     ("vp_fused_strip.hip", []),
     ("vp_fused_strip_nt4.hip", []),
     ("vp_fused_strip_nt6.hip", []),

@@ -1005,7 +1005,12 @@ HRESULT CHipVideoProcessor::ProcessOne(const uint8_t *sample, void *rt, int rtPi
         // UpdatePlan asked FusedUp2xSupported without a target (pitch 0): what depends on THIS call's target is asked here, as the strip and
         // same-size routes below ask it — rows that span 4 GiB go to the convert kernel and the resize draws, which store through size_t
         if (StoreRowsFit32(fp.store, fp.out_h))       // (a single frame travels by value in the kernel arguments)
-            return CheckHip(LaunchFusedUp2x(fp, LaunchFrames::One(sample, rt), on.stream), "k_fused_up2x");
+        {
+            FusedUp2xLastForm() = -1;
+            const hipError_t e = LaunchFusedUp2x(fp, LaunchFrames::One(sample, rt), on.stream);
+            if (FusedUp2xLastForm() >= 0) m_up2xForm = FusedUp2xLastForm();      // (GetLastBatchInfo: ";up2x=")
+            return CheckHip(e, "k_fused_up2x");
+        }
         m_fusedAside = true;
     }
     if (m_strip) {
@@ -1335,7 +1340,9 @@ HRESULT CHipVideoProcessor::RunBatchRoute(BatchRoutePlan &rp, BatchRun &run)
         // behind it (the fused Jinc2m kernel, which LaunchFusedUp2x may launch instead, reads an uploaded table)
         if ((hr = BatchFrames(n, srcs, dsts, FusedUp2xByValueMax(fp), stream, rows, &table, &frames))) break;
         start();
+        FusedUp2xLastForm() = -1;
         hr = CheckHip(LaunchFusedUp2x(fp, frames, stream), "k_fused_up2x");
+        if (FusedUp2xLastForm() >= 0) m_up2xForm = FusedUp2xLastForm();
         break;
     }
     }
@@ -1705,6 +1712,7 @@ std::string CHipVideoProcessor::GetLastBatchInfo() const
     std::string s = "frames=" + std::to_string(m_lastBatchFrames) + ";launches=" + std::to_string(m_lastBatchLaunches) + ";lane=" + std::to_string(m_lastBatchLane) + ";waits=" + std::to_string(m_lastBatchWaits) +
                     ";uploads=" + std::to_string(m_lastBatchUploads);
     if (!m_dvLastInfo.empty()) s += ";dovi_runs=" + m_dvLastInfo;
+    if (m_up2xForm >= 0) s += m_up2xForm == 1 ? ";up2x=bp" : ";up2x=generic";      // the exact-2x kernel's form (vp_fused_up2x_bp.h)
     s += m_yuvLastInfo;            // (";yuv_chunks=..;yuv_lanes=.." behind a ProcessBatchYuv, ";tensor_chunks=..;tensor_lanes=.." behind a ProcessBatchTensor, empty otherwise)
     return s;
 }

@@ -324,6 +324,7 @@ private:
     int m_lastBatchLane = -1;                                // the lane the last batch ran on (-1: the context stream)
     int m_lastBatchUploads = 0;                              // frame / plane tables the last batch call sent (a table of up to 32 frames travels in the exact-2x kernel's arguments: 0)
     int m_lastBatchFrames = 0, m_lastBatchLaunches = 0;      // ... and what the last batch call used
+    int m_up2xForm = -1;                                     // the form of the last exact-2x launch since the last batch call began (FusedUp2xLastForm; -1: none)
     HRESULT CheckTargetLayout(int n, void *const *dsts, int rtPitch);
     // The record of a batch call (GetLastBatchInfo), open for as long as the call runs: every batch entry point starts with one, so a refused call reports an empty record
     struct BatchRecord {
@@ -331,7 +332,7 @@ private:
         BatchRecord(CHipVideoProcessor &v, int frames) : vp(v), launches(v.m_launches), uploads(v.m_tableRing.Sent())
         {
             vp.m_lastBatchFrames = frames; vp.m_lastBatchLaunches = vp.m_lastBatchUploads = 0; vp.m_lastBatchLane = -1; vp.m_lastBatchWaits = 0;
-            vp.m_dvLastInfo.clear(); vp.m_yuvLastInfo.clear();
+            vp.m_dvLastInfo.clear(); vp.m_yuvLastInfo.clear(); vp.m_up2xForm = -1;
         }
         ~BatchRecord() { vp.m_lastBatchLaunches = (int)(vp.m_launches - launches); vp.m_lastBatchUploads = (int)(vp.m_tableRing.Sent() - uploads); }     // (what the call launched and sent up to its return)
     };

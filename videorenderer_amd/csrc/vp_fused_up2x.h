@@ -28,9 +28,15 @@
 // This header holds the kernel template and its per-tap-count launcher; vp_fused_up2x_nt{4,5,6}.hip instantiate one tap count
 // each (36 kernels per translation unit, compiled side by side), vp_fused.hip keeps the block-convert kernels and the dispatch.
 // -DMPCVR_UP2X_HEADLINE_ONLY (tools/isa_headline.sh): only the headline instantiation <5, PQ table, P01x, integer dither>.
+// The loop below is also the bi-planar twin's (k_fused_up2x_bp, vp_fused_up2x_bp_launch.h): with BP set, stage C loads one chroma texel
+// per iteration and converts with vp_fused_up2x_bp.h's pieces; with BP = 0 every `if constexpr (BP)` falls away and the kernel is what
+// it was.  The twin's kernels are instantiated in vp_fused_up2x_bp_nt{4,5,6}.hip, none of them in the headline-only unit.
 #pragma once
+#include <type_traits>
+
 #include "vp_fused_dev.h"
 #include "vp_fused_prefetch.h"
+#include "vp_fused_up2x_bp.h"
 
 namespace mpcvr {
 
@@ -69,7 +75,7 @@ __device__ __forceinline__ void stage_baked_tables(unsigned char *tables, const 
     }
 }
 
-template <int NT, int TAIL, int SRC, int EPI, int XC>
+template <int NT, int TAIL, int SRC, int EPI, int XC, int BP = 0>
 __device__ __forceinline__ void fused_up2x_body(const FusedArgs &P, const FusedFrame *__restrict__ frames, const unsigned char *__restrict__ baked,
                                                 const FrameTable32 &tab)
 {
@@ -161,28 +167,38 @@ __device__ __forceinline__ void fused_up2x_body(const FusedArgs &P, const FusedF
     // in flight (load_raw_unseen / raw_unseen_arrived, vp_fused_prefetch.h).  SRC_GENERIC — and every source in a
     // -DMPCVR_UP2X_COMPILER_WAITS=1 build — leaves loads and waits to the compiler, which writes vmcnt(3..0) there: each
     // iteration then waits for the stores of the previous one and for the prefetch issued one iteration ago.
-    constexpr int NL = MPCVR_UP2X_COMPILER_WAITS ? 0 : raw_unseen_loads<SRC>();
+    // (the twin: BP_LOADS = 3 loads per group — vmcnt(11) in the steady state, then 7, then 3 — and one more in the segment's first group)
+    static_assert(!BP || (!MPCVR_UP2X_COMPILER_WAITS && XC == XC_NEVER && bp_planned<TAIL, SRC, EPI>()), "the twin: counted waits, the fast convert form, a planned instantiation");
+    constexpr int NL = MPCVR_UP2X_COMPILER_WAITS ? 0 : BP ? BP_LOADS : raw_unseen_loads<SRC>();
     constexpr bool UNSEEN = NL != 0;
     Raw raw2[2];
     RawUnseen<raw_unseen_loads<SRC>() ? raw_unseen_loads<SRC>() : 1> pend2[2];
+    RawUnseenBp pendb[2];                            // the twin's groups (its buffer 1 never holds a fourth load)
+    ChromaCarry keep{0.0f, 0.0f};                    // the twin: chroma row n + 1 of the last convert = row n of the next
     RawAddr ra;
     make_raw_addr<SRC>(P, Xg, ra);
     auto prefetch = [&](int ar, int b) __attribute__((always_inline)) {
-        if constexpr (UNSEEN) load_raw_unseen<SRC>(P, py, ra, clampi(ar, 0, H - 1), clampi(ar + 1, 0, H - 1), pend2[b]);
+        if constexpr (BP) load_raw_unseen_bp<SRC, false>(P, py, ra, clampi(ar, 0, H - 1), clampi(ar + 1, 0, H - 1), pendb[b]);
+        else if constexpr (UNSEEN) load_raw_unseen<SRC>(P, py, ra, clampi(ar, 0, H - 1), clampi(ar + 1, 0, H - 1), pend2[b]);
         else load_raw<SRC>(P, py, ra, clampi(ar, 0, H - 1), clampi(ar + 1, 0, H - 1), raw2[b]);
     };
-    prefetch(s0 - 3, 0);
+    if constexpr (BP) load_raw_unseen_bp<SRC, true>(P, py, ra, clampi(s0 - 3, 0, H - 1), clampi(s0 - 2, 0, H - 1), pendb[0]);     // both chroma rows: nothing is carried yet
+    else prefetch(s0 - 3, 0);
     prefetch(s0 - 1, 1);
 
     // stage C for virtual rows ar, ar+1 (whose raw codes were prefetched into buffer b): convert, write A, prefetch rows ar+4, ar+5;
     // tw = the loop iteration it runs in (0 in front of the loop): what the wait for the raw codes may leave in flight
-    auto stage_c = [&](int ar, int b, int tw) {
+    // first: std::true_type for the convert in front of the loop (the twin takes both chroma rows from its group there)
+    auto stage_c = [&](int ar, int b, int tw, auto first) {
         f2 rc[2][3];
-        if constexpr (UNSEEN) {
+        if constexpr (BP) {
+            raw_unseen_arrived<NL>(tw);
+            convert_block_bp<TAIL, SRC, decltype(first)::value>(P, MM, GG, CC, pendb[b], keep, P.rect_t + clampi(ar, 0, H - 1), P.rect_t + clampi(ar + 1, 0, H - 1), T, rc);
+        } else if constexpr (UNSEEN) {
             raw_unseen_arrived<NL>(tw);
             raw_unseen_finish<SRC>(P, pend2[b], raw2[b]);
         }
-        convert_block<TAIL, SRC, DV_NONE, XC, XC == XC_ALWAYS ? OUT_CODE_F : OUT_NORM>(P, MM, GG, CC, raw2[b], P.rect_t + clampi(ar, 0, H - 1), P.rect_t + clampi(ar + 1, 0, H - 1), T, rc);
+        if constexpr (!BP) convert_block<TAIL, SRC, DV_NONE, XC, XC == XC_ALWAYS ? OUT_CODE_F : OUT_NORM>(P, MM, GG, CC, raw2[b], P.rect_t + clampi(ar, 0, H - 1), P.rect_t + clampi(ar + 1, 0, H - 1), T, rc);
         prefetch(ar + 4, b);
 #pragma unroll
         for (int c = 0; c < 3; c++) {
@@ -195,6 +211,12 @@ __device__ __forceinline__ void fused_up2x_body(const FusedArgs &P, const FusedF
             if (edge_wave) {       // clamp-to-edge of the convert texture: patch the column that hangs over (rare wave;
                                    // an LDS store so that the compiler keeps it a branch instead of 12 selects per iteration)
                 if (X < 0) *(f2 *)(A + (c * AW + 2 * lane + 1) * 2) = qe;
+                else if constexpr (BP) {
+                    // the twin: the same column — W - 1, the odd one of the rect's last block — over the same slots, but written by the
+                    // lane IN FRONT of each clamped lane (the last block's own lane and every clamped one hold that block): lane 63, which
+                    // has no neighbour to take its odd column's chroma from, never supplies it
+                    if (X >= W - 2 && lane != 63) *(f2 *)(A + (c * AW + 2 * lane + 2) * 2) = qo;
+                }
                 else if (X > W - 2) *(f2 *)(A + (c * AW + 2 * lane) * 2) = qo;
             }
         }
@@ -203,7 +225,7 @@ __device__ __forceinline__ void fused_up2x_body(const FusedArgs &P, const FusedF
     // global prefetch behind it) is covered by the Y stage instead of stalling the wave.  A is exchanged between
     // lanes of this wave only: LDS operations of one wave execute in order; the fences keep the compiler from
     // reordering the A reads and writes (which look unrelated thread by thread).
-    stage_c(s0 - 3, 0, 0);
+    stage_c(s0 - 3, 0, 0, std::true_type{});
 
     for (int tb = 0; tb < n_iter; tb += 4) {
 #pragma unroll
@@ -251,7 +273,7 @@ __device__ __forceinline__ void fused_up2x_body(const FusedArgs &P, const FusedF
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 
             // ---------------- stage C of the NEXT iteration ----------------
-            if (t + 1 < n_iter) stage_c(a + 2, (u + 1) & 1, t);
+            if (t + 1 < n_iter) stage_c(a + 2, (u + 1) & 1, t, std::false_type{});
 
             // ---------------- stage Y + final pass ----------------
             // window slot of virtual row r is (r - (s0-3)) & 7; rows a-6 .. a+1 are live: slot(a-6+i) = (2u+2+i) & 7
@@ -419,7 +441,12 @@ hipError_t LaunchFusedUp2xNT(const FusedParams &P, const FusedArgs &a_in, int st
 #ifdef MPCVR_UP2X_HEADLINE_ONLY
     MPCVR_LAUNCH3(NT, TAILK_PQ_LUT, SRC_P01X, EPI_DITHER8);
 #else
-    MPCVR_LAUNCH_NT(NT);
+    // the bi-planar twin where the whole launch qualifies (FusedUp2xBpTakes, decided here, once per launch); MPCVR_UP2X_NO_BP=1 keeps
+    // the generic kernel (A/B runs and the tests that compare the two: read at every launch, unlike its static neighbours)
+    const bool twin = !EnvInt("MPCVR_UP2X_NO_BP", 0) && FusedUp2xBpTakes(a, srck, epik, tailk);
+    FusedUp2xLastForm() = twin ? 1 : 0;
+    if (twin) LaunchFusedUp2xBpNT<NT>(a, grid, lds, tailk, srck, epik, F.dev, baked, tab, s);
+    else MPCVR_LAUNCH_NT(NT);
 #endif
 #undef MPCVR_LAUNCH_NT
 #undef MPCVR_LAUNCH_8

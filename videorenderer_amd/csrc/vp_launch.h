@@ -157,6 +157,9 @@ int ConvertBlocksByValueMax(const FusedParams &P);
 inline int FusedUp2xByValueMax(const FusedParams &P) { return P.jinc_tab ? 0 : TableRows<FrameTable32>(); }
 hipError_t LaunchConvertBlocks(const FusedParams &P, const LaunchFrames &F, hipStream_t s, size_t batch_stride = 0);
 hipError_t LaunchFusedUp2x(const FusedParams &P, const LaunchFrames &F, hipStream_t s);
+// the form the calling thread's last LaunchFusedUp2x took: 0 = k_fused_up2x, 1 = its bi-planar twin k_fused_up2x_bp (vp_fused_up2x_bp.h),
+// -1 = none yet or another kernel (the fused Jinc2m one); GetLastBatchInfo reports it
+int &FusedUp2xLastForm();
 
 // arbitrary-ratio fused path (vp_fused_strip.hip): block convert + both draws of an unrotated two-pass resize + final pass in one
 // kernel, driven by the tap tables of BuildAxisTaps; wave-autonomous strips like the 2x kernel, the vertical window in LDS.
