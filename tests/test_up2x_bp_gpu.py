@@ -27,7 +27,7 @@ import numpy as np
 import pytest
 
 from tests.golden.cases import case_frame, oracle_params
-from tests.test_parity_gpu import BG, _HLG, _PQ, _SDR, compare, compare_rgb10, has_tail, internal_is_8bit, make_vp
+from tests.test_parity_gpu import BG, _HLG, _PQ, _SDR, CarvedTargets, compare, compare_rgb10, has_tail, internal_is_8bit, make_vp
 
 KNOB = "MPCVR_UP2X_NO_BP"
 TAPS = {4: dict(iUpscaling=2), 5: dict(iUpscaling=4), 6: dict(iUpscaling=4, flags=1)}      # Catmull-Rom, Lanczos3 (Q1 folded), Lanczos3 fixed
@@ -51,26 +51,41 @@ def case_of(plan, w, h, taps=5, seed=9100, **over):
     return c
 
 
-def draw(mpcvr, torch, c, generic, batch=0):
-    """The case as a single frame (batch = 0) or a batch of `batch` frames that alternate between two samples, with the twin allowed or
-    the generic kernel forced -> ([pixels per frame], GetVPInfo, reported form)."""
+def draw(mpcvr, torch, c, generic, batch=0, distinct=2, sample_off=0, target_off=0):
+    """The case as a single frame (batch = 0) or a batch of `batch` frames that cycle through `distinct` samples (sample k: the case's seed
+    + 1000 k), with the twin allowed or the generic kernel forced -> ([pixels per frame], GetVPInfo, reported form).  sample_off / target_off:
+    a single frame whose sample / render target starts that many bytes behind a 256-byte boundary (the target then in the `off4` layout
+    of tests/test_parity_gpu.py: a patterned buffer around it, a pitch of window_w * 4 + 4)."""
     old = os.environ.pop(KNOB, None)
     if generic:
         os.environ[KNOB] = "1"
     try:
         vp, (ww, wh) = make_vp(mpcvr, c)
         frames = []
-        for i in range(2 if batch else 1):
+        for i in range(distinct if batch else 1):
             f, pitch = case_frame(dict(c, seed=c["seed"] + 1000 * i))
             frames.append(torch.from_numpy(f).cuda())
         if batch:
             dsts = [torch.full((wh, ww, 4), BG, dtype=torch.uint8, device="cuda") for _ in range(batch)]
-            vp.ProcessBatch([frames[i % 2] for i in range(batch)], dsts, ww * 4)
+            vp.ProcessBatch([frames[i % distinct] for i in range(batch)], dsts, ww * 4)
         else:
+            if sample_off:
+                big = torch.zeros(frames[0].numel() + 256, dtype=torch.uint8, device="cuda")
+                big[sample_off:sample_off + frames[0].numel()] = frames[0]
+                frames[0] = big[sample_off:sample_off + frames[0].numel()]
+                assert frames[0].data_ptr() % 256 == sample_off
+            carved = CarvedTargets(torch, ww, wh, ww * 4 + 4, [target_off]) if target_off else None
             dsts = [torch.full((wh, ww, 4), BG, dtype=torch.uint8, device="cuda")]
             vp.CopySample(frames[0], pitch)
-            vp.Process(dsts[0], ww * 4)
+            if carved:
+                assert carved.ptrs[0] % 256 == target_off
+                vp.Process(carved.ptrs[0], carved.pitch)
+            else:
+                vp.Process(dsts[0], ww * 4)
         vp.Synchronize()
+        if not batch and carved:
+            carved.assert_guards_intact(f"target at +{target_off} [{vp.GetVPInfo()}]")
+            dsts = [carved.window(0).contiguous()]
         out = [d.cpu().numpy() for d in dsts], vp.GetVPInfo(), vp.GetUp2xForm()
         vp.close()
         return out
@@ -91,10 +106,10 @@ def against_oracle(oracle, c, got, what, seed_shift=0):
         compare(got, want, what, min_same=0.99)
 
 
-def twin_equals_generic(mpcvr, torch, c, what, batch=0):
-    twin, info, form = draw(mpcvr, torch, c, False, batch)
+def twin_equals_generic(mpcvr, torch, c, what, batch=0, **layout):
+    twin, info, form = draw(mpcvr, torch, c, False, batch, **layout)
     assert info == "fused_up2x" and form == "bp", (what, info, form)
-    gen, info_g, form_g = draw(mpcvr, torch, c, True, batch)
+    gen, info_g, form_g = draw(mpcvr, torch, c, True, batch, **layout)
     assert info_g == "fused_up2x" and form_g == "generic", (what, info_g, form_g)
     for i, (a, b) in enumerate(zip(twin, gen)):
         assert not bool((a[..., :3] == BG).all()), (what, i)
