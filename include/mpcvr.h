@@ -635,6 +635,86 @@ int32_t mpcvr_deband_pass(const void *src, int32_t src_pitch, int32_t src_fmt, i
  * written, when there is no sample (as mpcvr_render). */
 int32_t mpcvr_render_deband(mpcvr_ctx *ctx, int32_t field, const mpcvr_deband_params *params, uint32_t seed, void *dst, int32_t dst_pitch, int32_t dst_fmt);
 
+/* EXTENSION — sharpening of a rendered frame: a binomial unsharp mask in integers, with soft coring and an overshoot limiter; the step users
+ * of the reference load into its post-scale shader slot (LumaSharpen, adaptive sharpen, CAS).  A 2x Lanczos or Jinc upscale leaves edges a
+ * few texels wide; the pass adds the difference between the picture and its binomial blur back, leaves differences below a threshold alone
+ * (noise is not detail) and keeps every channel within the range of its 3 x 3 neighbourhood plus an allowed overshoot (no halos).  The
+ * reference has no sharpener; there is no reference line to cite.  The definition is the integer text below, modelled bit for bit by
+ * tests/sharpen_model.py (arithmetic: csrc/vp_sharpen_core.h, which the kernel and mpcvr_sharpen_host both compile).
+ *   Surfaces: the rules of mpcvr_deband_pass.  src and dst are w x h 32-bit texels, w and h in 1 .. 32768, each MPCVR_OUT_BGRA8 (largest
+ *     code 255) or MPCVR_OUT_RGB10A2 (1023), chosen independently: maxin and maxout.  The A / X bits of src are ignored, those of dst
+ *     written as all ones.  Pointers and pitches are multiples of 4 and pitches >= 4 w; 16-byte loads and stores are taken where pointers
+ *     and pitches allow them.  NOT in place: any overlap of dst with src is refused.  Source bytes between a row's pixels and the pitch
+ *     never reach a pixel.  All address arithmetic is 64-bit.
+ *   Parameters (mpcvr_sharpen_params, a uint32_t seed beside it): radius r 1 .. 3; amount a 0 .. 256 in 1/64 (64 adds the detail once);
+ *     threshold t 0 .. 4 maxin in QUARTER codes of the source (the coring); overshoot o 0 .. maxin in source codes; mode
+ *     MPCVR_SHARPEN_RGB_EXT or MPCVR_SHARPEN_LUMA_EXT; dither 0 or 1.  mpcvr_sharpen_params_default: radius 2, amount 32, mode 1, dither 1,
+ *     threshold 4 for BGRA8 and 16 for RGB10A2 (one 8-bit code), overshoot 2 for BGRA8 and 8 for RGB10A2 (two 8-bit codes).
+ *   Per texel (x, y), every neighbour coordinate clamped to the surface, everything in signed 32-bit integers.  b_j = C(2 r, j + r) for
+ *   j = -r .. r (1 2 1, 1 4 6 4 1, 1 6 15 20 15 6 1: sum 4^r per axis);  S = 16^r.
+ *     1. The field f: mode 0, each channel's code, and steps 2 - 4 run per channel; mode 1, f = L = (54 R + 183 G + 19 B + 128) >> 8, one
+ *        field for the texel, in 0 .. maxin (the weights sum to 256).
+ *     2. Blur = sum_j sum_i b_j b_i f(x + i, y + j) <= S maxin;  d = S f(x, y) - Blur,  |d| <= S maxin <= 4,190,208.
+ *     3. Soft coring: T = t (S / 4);  e = d - min(max(d, -T), T): zero inside +-T, continuous outside.
+ *     4. Per channel c of the texel: v = 64 S c + a e (in mode 1 e is the luma's).  |a e| <= 1,072,693,248 and 64 S c <= 268,173,312, so
+ *        |v| < 2^31.
+ *     5. The limiter, per channel: mn and mx the least and greatest source code of that channel over the 3 x 3 neighbourhood (clamped
+ *        coordinates, the centre included);  lo = max(mn - o, 0),  hi = min(mx + o, maxin);  v = min(max(v, 64 S lo), 64 S hi).
+ *     6. Quarter codes: q = (v + 8 S) >> (4 r + 4), in 0 .. 4 maxin (v >= 0 here).
+ *     7. The output stage is step 3 of the deband definition verbatim, and the same function: den = 4 maxin; dd = den / 2 with dither 0,
+ *        dd = ((H(x, y, 0, seed) >> 8) den) >> 24 with dither 1 (the hash of mpcvr_deband_pass, one value for the texel's three channels,
+ *        the 34-bit product taken as a high word); out = (q maxout + dd) / den.
+ *   Consequences (tests/test_sharpen.py asserts them; the first five at equal depths with dither 0 — across depths "unchanged" reads
+ *   out = (2 c maxout + maxin) / (2 maxin)):
+ *     - a = 0 returns the code; t = 4 maxin returns the code (|d| never exceeds T);
+ *     - a flat surface comes back unchanged for every parameter set;
+ *     - a surface of two levels A <= B per channel (every channel at its A on the same texels) comes back unchanged at o = 0 for every a, r
+ *       and mode, whatever the edge's shape: where the 3 x 3 neighbourhood holds one level, lo = hi; where it holds both, the code is A or
+ *       B and the detail points away from the other level (in mode 1 because L rises with every channel; with a channel that runs the
+ *       other way it would not); with overshoot o every output lies in A - o .. B + o;
+ *     - a gray surface (R = G = B) whose code is affine in x and y comes back unchanged wherever no tap clamps, r texels in from every
+ *       border: the binomial weights are symmetric, so Blur = S f;
+ *     - on a gray surface mode 0 and mode 1 give identical texels, dither included (L of a gray texel is its code);
+ *     - at o = 0 every output channel lies within the least and greatest code of its own 3 x 3 source neighbourhood.
+ *   What it does to an edge (the model, tests/test_sharpen.py): a 10-bit row stepping 100 -> 900, blurred by the 9-tap binomial (C(8, j),
+ *   sum 256, floor division), has 4 texels strictly between 180 and 820 (its 10 - 90 % width); at radius 2, amount 64, threshold 0 the pass
+ *   leaves 2.  With o = 0 no code is below 100 or above 900; with o = 16 the extremes are 91 and 908.
+ * Refusals, with nothing launched and nothing written: MPCVR_E_POINTER for a NULL src, params or dst; MPCVR_E_INVALIDARG for another
+ * src_fmt or dst_fmt, w or h out of range, a parameter outside the rules above, a pointer or pitch that breaks them, and any overlap of
+ * dst with src (a surface counts as the bytes from its first pixel to the last pixel of its last row).  No byte outside dst's pixels is ever
+ * written: not the pitch padding, nothing in front of or behind the surface. */
+#define MPCVR_SHARPEN_RGB_EXT 0
+#define MPCVR_SHARPEN_LUMA_EXT 1
+typedef struct mpcvr_sharpen_params {
+    int32_t radius;         /* 1 .. 3: the blur is the (2 r + 1)-tap binomial in x and in y */
+    int32_t amount;         /* 0 .. 256, in 1/64: 64 adds the detail once */
+    int32_t threshold;      /* 0 .. 4 * maxin, quarter codes of the source: detail below it is left alone */
+    int32_t overshoot;      /* 0 .. maxin, source codes: how far a channel may leave the range of its 3 x 3 neighbourhood */
+    int32_t mode;           /* MPCVR_SHARPEN_RGB_EXT: per channel, MPCVR_SHARPEN_LUMA_EXT: the luma's detail added to every channel */
+    int32_t dither;         /* 0: round to nearest, 1: hashed dither on the output quantisation */
+} mpcvr_sharpen_params;
+/* Host, no GPU: the defaults for a source of src_fmt.  MPCVR_E_POINTER for NULL, MPCVR_E_INVALIDARG for another format. */
+int32_t mpcvr_sharpen_params_default(int32_t src_fmt, mpcvr_sharpen_params *params);
+/* Host, no GPU: the whole pass over surfaces in HOST memory, bit for bit what the kernel writes.  The refusals of mpcvr_sharpen_pass. */
+int32_t mpcvr_sharpen_host(const void *src_host, int64_t src_pitch, int32_t src_fmt, int32_t w, int32_t h, const mpcvr_sharpen_params *params,
+                           uint32_t seed, void *dst_host, int64_t dst_pitch, int32_t dst_fmt);
+/* Host, no GPU: what a launch over a w x h surface decides by rule.  *halo = r, the texels a workgroup stages around its tile on every
+ * side; *lds_bytes = the LDS of one workgroup (the staged image and the row sums: DESIGN.md section 4.15), which depends on r and the mode.
+ * Each pointer optional.  MPCVR_E_POINTER for NULL params, MPCVR_E_INVALIDARG for what mpcvr_sharpen_pass refuses about the format, the
+ * parameters and the extent. */
+int32_t mpcvr_plan_sharpen(int32_t src_fmt, const mpcvr_sharpen_params *params, int32_t w, int32_t h, int32_t *halo, int32_t *lds_bytes);
+/* One standalone pass over one device surface, like mpcvr_deband_pass; stream = a hipStream_t or NULL.  One kernel launch (k_sharpen,
+ * csrc/vp_sharpen.hip).  The environment variable MPCVR_SHARPEN_STAGING = dword, read per launch, makes the kernel stage its tile with
+ * 4-byte loads where it would take 16-byte ones (A/B runs); the bytes written do not depend on it. */
+int32_t mpcvr_sharpen_pass(const void *src, int32_t src_pitch, int32_t src_fmt, int32_t w, int32_t h, const mpcvr_sharpen_params *params,
+                           uint32_t seed, void *dst, int32_t dst_pitch, int32_t dst_fmt, void *stream);
+/* mpcvr_render, then the pass from the back buffer over the whole window into dst, ordered exactly as mpcvr_render_deband: Process into the
+ * context-owned back buffer with the letterbox cleared to black, on the context stream, the pass queued behind it, and everything queued
+ * later, lanes included, behind the pass.  dst is complete after mpcvr_synchronize; the back buffer is only read.  The source format is the
+ * context's output_format.  Everything mpcvr_sharpen_pass refuses is answered before anything is drawn.  S_FALSE, with nothing drawn or
+ * written, when there is no sample (as mpcvr_render). */
+int32_t mpcvr_render_sharpen(mpcvr_ctx *ctx, int32_t field, const mpcvr_sharpen_params *params, uint32_t seed, void *dst, int32_t dst_pitch, int32_t dst_fmt);
+
 /* Configure — DX11VideoProcessor.cpp:3800-4050: diff each field, rebuild only what changed. */
 int32_t mpcvr_configure(mpcvr_ctx *ctx, const mpcvr_settings *settings);
 
@@ -906,6 +986,23 @@ int32_t mpcvr_plan_batch_deband(int32_t window_w, int32_t window_h, int32_t n, s
                                 int32_t *surface_pitch, size_t *frame_stride, int32_t *frames_per_chunk, int32_t *chunks);
 int32_t mpcvr_process_batch_deband(mpcvr_ctx *ctx, int32_t n, const void *const *srcs, const mpcvr_deband_params *params, uint32_t seed,
                                    void *const *dsts, int32_t dst_pitch, int32_t dst_fmt);
+/* EXTENSION — a batch through the sharpen pass (the pass itself: mpcvr_sharpen_pass above).  dsts[i] is the render target of frame i, all n
+ * of dst_pitch and dst_fmt.  Target i holds, byte for byte, what
+ *     mpcvr_process_batch(srcs -> n window-sized RGB targets of the context's output_format, black outside the video rect), then
+ *     mpcvr_sharpen_pass(target i, output_format, window_w, window_h, params, seed + i (mod 2^32), dsts[i], dst_pitch, dst_fmt), n times
+ * leave, with ONE k_sharpen launch per chunk of frames (its frame dimension) where the composition takes n, and no intermediate targets of
+ * the caller's.  The machinery is that of mpcvr_process_batch_deband: the RGB frames live in the context-owned surfaces laid out by
+ * mpcvr_plan_batch_sharpen — the formulas of mpcvr_plan_batch_tensor — under the budget of mpcvr_set_batch_yuv_budget; chunks, routes, the
+ * letterbox and the order are as described for mpcvr_process_batch_yuv.  The targets are complete after mpcvr_synchronize.
+ * Refusals, answered before anything is drawn, allocated or written: MPCVR_E_NOT_VALID_STATE before mpcvr_set_input; MPCVR_E_POINTER for
+ * a NULL array, entry or params; MPCVR_E_INVALIDARG for n <= 0, whatever mpcvr_sharpen_pass refuses about the parameters, dst_pitch,
+ * dst_fmt and a dsts[i], and any two targets that overlap each other.
+ * mpcvr_get_last_batch_info afterwards: "launches" counts one pass per chunk, and ";sharpen_chunks=<k>;sharpen_lanes=<lane,lane,...>"
+ * follow (the lane of each chunk, -1 = the context stream; the first 64 chunks). */
+int32_t mpcvr_plan_batch_sharpen(int32_t window_w, int32_t window_h, int32_t n, size_t budget_bytes,
+                                 int32_t *surface_pitch, size_t *frame_stride, int32_t *frames_per_chunk, int32_t *chunks);
+int32_t mpcvr_process_batch_sharpen(mpcvr_ctx *ctx, int32_t n, const void *const *srcs, const mpcvr_sharpen_params *params, uint32_t seed,
+                                    void *const *dsts, int32_t dst_pitch, int32_t dst_fmt);
 
 /* Multi-GPU: the parameter blob (colour matrix, luminance scale, gamut matrix, resize phase weights,
  * dither table) a rank-0 context computes and every other rank adopts after an RCCL broadcast.

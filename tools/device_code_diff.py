@@ -5,7 +5,8 @@
 For every object file of python -m videorenderer_amd.build: the .hip_fatbin section is dumped (llvm-objcopy), the gfx950 code object is
 unbundled from it (clang-offload-bundler) and compared byte for byte.  Where whole code objects differ, every kernel is compared by the
 bytes of its code (the symbol's range of .text), by its descriptor and by the registers, LDS and scratch its metadata note states.
-Prints one line per translation unit and a total; exit status 1 when a kernel differs or the sets of kernels are not equal.
+Prints one line per translation unit and a total; exit status 1 when a kernel differs or the sets of kernels of a translation unit both
+builds hold are not equal.  A translation unit only one build holds is listed with its number of kernels and not compared.
 """
 import os
 import re
@@ -70,12 +71,14 @@ def kernels(blob, tmp):
 
 
 def main(a_dir, b_dir):
-    names = sorted(f for f in os.listdir(a_dir) if f.endswith(".o"))
-    if names != sorted(f for f in os.listdir(b_dir) if f.endswith(".o")):
-        print("the two builds do not hold the same object files")
-        return 1
+    in_a, in_b = (set(f for f in os.listdir(d) if f.endswith(".o")) for d in (a_dir, b_dir))
+    names = sorted(in_a & in_b)
     total = same_units = differing = 0
     with tempfile.TemporaryDirectory() as tmp:
+        # a translation unit only one build has (a new kernel family, a removed one) is listed, not compared: it cannot change an existing kernel
+        for n in sorted(in_a ^ in_b):
+            blob = code_object(os.path.join(a_dir if n in in_a else b_dir, n), tmp)
+            print(f"{n}: only in the {'first' if n in in_a else 'second'} build ({len(kernels(blob, tmp)) if blob else 0} kernels)")
         for n in names:
             a, b = code_object(os.path.join(a_dir, n), tmp), code_object(os.path.join(b_dir, n), tmp)
             if a is None and b is None:

@@ -184,6 +184,13 @@ class DebandParams(C.Structure):       # mpcvr_deband_params
     _fields_ = [("range", C.c_int32), ("iterations", C.c_int32), ("threshold", C.c_int32), ("dither", C.c_int32)]
 
 
+class SharpenParams(C.Structure):      # mpcvr_sharpen_params
+    _fields_ = [("radius", C.c_int32), ("amount", C.c_int32), ("threshold", C.c_int32), ("overshoot", C.c_int32), ("mode", C.c_int32), ("dither", C.c_int32)]
+
+
+SHARPEN_RGB_EXT, SHARPEN_LUMA_EXT = 0, 1
+
+
 class MpcvrError(RuntimeError):
     def __init__(self, hr, msg):
         super().__init__(f"HRESULT 0x{hr & 0xffffffff:08X}: {msg}")
@@ -213,6 +220,7 @@ EXPORTS = [
     "mpcvr_plan_deint_planes", "mpcvr_deint_plane_host", "mpcvr_deint_pass", "mpcvr_copy_sample_fields", "mpcvr_plan_batch_deint", "mpcvr_process_batch_deint",
     "mpcvr_plan_lut3d_entries", "mpcvr_plan_lut3d_value", "mpcvr_lut3d_pass", "mpcvr_render_lut3d", "mpcvr_plan_batch_lut3d", "mpcvr_process_batch_lut3d",
     "mpcvr_deband_params_default", "mpcvr_deband_host", "mpcvr_plan_deband", "mpcvr_deband_pass", "mpcvr_render_deband", "mpcvr_plan_batch_deband", "mpcvr_process_batch_deband",
+    "mpcvr_sharpen_params_default", "mpcvr_sharpen_host", "mpcvr_plan_sharpen", "mpcvr_sharpen_pass", "mpcvr_render_sharpen", "mpcvr_plan_batch_sharpen", "mpcvr_process_batch_sharpen",
 ]
 
 _lib = None
@@ -349,6 +357,13 @@ def load_library():
         "mpcvr_render_deband": [vp, i32, P(DebandParams), u32, vp, i32, i32],
         "mpcvr_plan_batch_deband": [i32, i32, i32, C.c_size_t, P(i32), P(C.c_size_t), P(i32), P(i32)],
         "mpcvr_process_batch_deband": [vp, i32, P(vp), P(DebandParams), u32, P(vp), i32, i32],
+        "mpcvr_sharpen_params_default": [i32, P(SharpenParams)],
+        "mpcvr_sharpen_host": [vp, C.c_int64, i32, i32, i32, P(SharpenParams), u32, vp, C.c_int64, i32],
+        "mpcvr_plan_sharpen": [i32, P(SharpenParams), i32, i32, P(i32), P(i32)],
+        "mpcvr_sharpen_pass": [vp, i32, i32, i32, i32, P(SharpenParams), u32, vp, i32, i32, vp],
+        "mpcvr_render_sharpen": [vp, i32, P(SharpenParams), u32, vp, i32, i32],
+        "mpcvr_plan_batch_sharpen": [i32, i32, i32, C.c_size_t, P(i32), P(C.c_size_t), P(i32), P(i32)],
+        "mpcvr_process_batch_sharpen": [vp, i32, P(vp), P(SharpenParams), u32, P(vp), i32, i32],
     }
     for name, args in sig.items():
         if lib_path != LIB_PATH and not hasattr(L, name):
@@ -669,6 +684,80 @@ def plan_batch_deband(window_w, window_h, n, budget_bytes=0):
     hr = load_library().mpcvr_plan_batch_deband(int(window_w), int(window_h), int(n), int(budget_bytes), C.byref(pitch), C.byref(stride), C.byref(fpc), C.byref(chunks))
     if hr != S_OK:
         raise MpcvrError(hr, "mpcvr_plan_batch_deband")
+    return dict(surface_pitch=pitch.value, frame_stride=stride.value, frames_per_chunk=fpc.value, chunks=chunks.value)
+
+
+def _sharpen_params(params):
+    """a SharpenParams from one, from a dict of its fields, or from a (radius, amount, threshold, overshoot, mode, dither) sequence"""
+    if isinstance(params, SharpenParams):
+        return params
+    if isinstance(params, dict):
+        return SharpenParams(**{k: int(v) for k, v in params.items()})
+    return SharpenParams(*[int(v) for v in params])
+
+
+def sharpen_params_default(src_fmt):
+    """(extension) The default parameters of the sharpen pass for a source of src_fmt (0 = BGRA8, 1 = RGB10A2) as a SharpenParams
+    (include/mpcvr.h: mpcvr_sharpen_params_default): radius 2, amount 32 / 64, threshold one 8-bit code, overshoot two, luma mode, dither
+    on.  Host only."""
+    p = SharpenParams()
+    hr = load_library().mpcvr_sharpen_params_default(int(src_fmt), C.byref(p))
+    if hr != S_OK:
+        raise MpcvrError(hr, "mpcvr_sharpen_params_default")
+    return p
+
+
+def sharpen_host(src, src_fmt, params, seed, dst_fmt, src_pitch=None, dst=None, dst_pitch=None, w=None):
+    """(extension) The sharpen pass over a surface in HOST memory, bit for bit what the kernel writes (include/mpcvr.h: mpcvr_sharpen_host).
+    `src`: a (h, w) uint32 numpy array, or with src_pitch and w a uint8 array of h rows of src_pitch bytes.  Returns a (h, w) uint32 array,
+    or fills `dst` (uint8, h rows of dst_pitch bytes) and returns it.  No GPU."""
+    import numpy as np
+    if src_pitch is None:
+        src = np.ascontiguousarray(src, dtype=np.uint32)
+        h, w = src.shape
+        src_pitch = 4 * w
+    else:
+        h = (src.size + src_pitch - 4 * w) // src_pitch
+    out = dst
+    if out is None:
+        out, dst_pitch = np.empty((h, w), dtype=np.uint32), 4 * w
+    p = _sharpen_params(params)
+    hr = load_library().mpcvr_sharpen_host(C.c_void_p(src.ctypes.data), int(src_pitch), int(src_fmt), int(w), int(h), C.byref(p), int(seed) & 0xffffffff,
+                                           C.c_void_p(out.ctypes.data), int(dst_pitch), int(dst_fmt))
+    if hr != S_OK:
+        raise MpcvrError(hr, "mpcvr_sharpen_host")
+    return out
+
+
+def plan_sharpen(src_fmt, params, w, h):
+    """(extension) (halo = radius, the LDS bytes of one workgroup) of a launch over a w x h surface (include/mpcvr.h: mpcvr_plan_sharpen).
+    Host only, no GPU."""
+    halo, lds = C.c_int32(), C.c_int32()
+    p = _sharpen_params(params)
+    hr = load_library().mpcvr_plan_sharpen(int(src_fmt), C.byref(p), int(w), int(h), C.byref(halo), C.byref(lds))
+    if hr != S_OK:
+        raise MpcvrError(hr, "mpcvr_plan_sharpen")
+    return halo.value, lds.value
+
+
+def sharpen_pass(src, src_pitch, src_fmt, w, h, params, seed, dst, dst_pitch, dst_fmt, stream=None):
+    """(extension) One device surface of 32-bit RGB texels (0 = BGRA8, 1 = RGB10A2) through the sharpen pass into the surface at `dst`, of
+    either format; dst must not overlap src (include/mpcvr.h: mpcvr_sharpen_pass).  Complete in stream order."""
+    p = _sharpen_params(params)
+    hr = load_library().mpcvr_sharpen_pass(C.c_void_p(_ptr(src)), int(src_pitch), int(src_fmt), int(w), int(h), C.byref(p), int(seed) & 0xffffffff,
+                                           C.c_void_p(_ptr(dst)), int(dst_pitch), int(dst_fmt), C.c_void_p(stream or 0))
+    if hr != S_OK:
+        raise MpcvrError(hr, "mpcvr_sharpen_pass")
+    return hr
+
+
+def plan_batch_sharpen(window_w, window_h, n, budget_bytes=0):
+    """(extension) The layout integers of mpcvr_process_batch_sharpen (include/mpcvr.h: mpcvr_plan_batch_sharpen): plan_batch_tensor's formulas.
+    dict(surface_pitch, frame_stride, frames_per_chunk, chunks).  Host only, no GPU."""
+    pitch, stride, fpc, chunks = C.c_int32(), C.c_size_t(), C.c_int32(), C.c_int32()
+    hr = load_library().mpcvr_plan_batch_sharpen(int(window_w), int(window_h), int(n), int(budget_bytes), C.byref(pitch), C.byref(stride), C.byref(fpc), C.byref(chunks))
+    if hr != S_OK:
+        raise MpcvrError(hr, "mpcvr_plan_batch_sharpen")
     return dict(surface_pitch=pitch.value, frame_stride=stride.value, frames_per_chunk=fpc.value, chunks=chunks.value)
 
 
@@ -1225,6 +1314,41 @@ class VideoProcessor:
         self._keep = keep
         return self._check(self._L.mpcvr_process_batch_deband(self._ctx, m, keep[0], C.byref(p), int(seed) & 0xffffffff, keep[1], int(dst_pitch), int(dst_fmt)))
 
+    def RenderSharpen(self, params=None, seed=0, dst_fmt=None, out=None, out_pitch=None, field=1):
+        """(extension) Render, then the back buffer through the sharpen pass (params: a SharpenParams, a dict of its fields or None for
+        sharpen_params_default of the context's output_format) into a target of dst_fmt (OUT_BGRA8 / OUT_RGB10A2; None: the context's
+        output_format) (mpcvr_render_sharpen).  `out`: a device tensor or address of window_h rows of out_pitch bytes (None: 4 * window_w);
+        else a (H, W, 4) uint8 tensor is allocated.  Returns the target, complete after Synchronize; None when there is no sample
+        (S_FALSE).  The back buffer stays the plain frame."""
+        import torch
+        ww, wh = self._window_size()
+        if dst_fmt is None:
+            dst_fmt = self.settings.output_format
+        p = sharpen_params_default(self.settings.output_format) if params is None else _sharpen_params(params)
+        if out is None:
+            out = torch.empty((wh, ww, 4), dtype=torch.uint8, device="cuda")
+            out_pitch = ww * 4
+        elif out_pitch is None:
+            out_pitch = ww * 4
+        self._keep = (out,)
+        hr = self._check(self._L.mpcvr_render_sharpen(self._ctx, field, C.byref(p), int(seed) & 0xffffffff, C.c_void_p(_ptr(out)), int(out_pitch), int(dst_fmt)))
+        return out if hr == S_OK else None
+
+    def ProcessBatchSharpen(self, srcs, params, seed, dsts, dst_pitch, dst_fmt=None):
+        """(extension) ProcessBatch with every frame taken through the sharpen pass on its way to its render target, frame i with seed + i
+        (mpcvr_process_batch_sharpen): dsts[i] are device tensors or addresses of window_h rows of dst_pitch bytes, of dst_fmt (None: the
+        context's output_format).  One k_sharpen launch per chunk; complete after Synchronize.  GetLastBatchInfo adds sharpen_chunks /
+        sharpen_lanes."""
+        m = len(srcs)
+        assert m == len(dsts) and m > 0
+        if dst_fmt is None:
+            dst_fmt = self.settings.output_format
+        p = sharpen_params_default(self.settings.output_format) if params is None else _sharpen_params(params)
+        arr = C.c_void_p * m
+        keep = (arr(*[_ptr(s) for s in srcs]), arr(*[_ptr(d) for d in dsts]), (srcs, dsts))
+        self._keep = keep
+        return self._check(self._L.mpcvr_process_batch_sharpen(self._ctx, m, keep[0], C.byref(p), int(seed) & 0xffffffff, keep[1], int(dst_pitch), int(dst_fmt)))
+
     def MeasureBackBuffer(self, hist=None):
         """(extension) The histogram of max(R, G, B) of the frame the last Render / RenderYuv left, over video rect ∩ window
         (mpcvr_measure_backbuffer): a device tensor of 1024 int32 words holding the uint32 counts (allocated when `hist` is None), complete
@@ -1401,7 +1525,7 @@ class VideoProcessor:
         return buf.value.decode()
 
     def GetLastBatchInfo(self):
-        """'frames=<n>;launches=<kernel launches>;lane=<0 | 1: the batch ran on that lane beside its predecessor, -1: on the context stream>;waits=<frames / batches still in flight on other lanes, into memory this batch's targets overlap, that it was ordered behind>[;dovi_runs=...]' of the last ProcessBatch / ProcessBatchDovi / ProcessBatchYuv call, as a dict; behind a ProcessBatchYuv also yuv_chunks and yuv_lanes (the lane of each chunk), behind a ProcessBatchTensor tensor_chunks and tensor_lanes, behind a ProcessBatchFromTensors sample_chunks, behind a ProcessBatchLut3d lut3d_chunks, lut3d_lanes and lut3d_table, behind a ProcessBatchDeband deband_chunks, deband_lanes and deband_taps."""
+        """'frames=<n>;launches=<kernel launches>;lane=<0 | 1: the batch ran on that lane beside its predecessor, -1: on the context stream>;waits=<frames / batches still in flight on other lanes, into memory this batch's targets overlap, that it was ordered behind>[;dovi_runs=...]' of the last ProcessBatch / ProcessBatchDovi / ProcessBatchYuv call, as a dict; behind a ProcessBatchYuv also yuv_chunks and yuv_lanes (the lane of each chunk), behind a ProcessBatchTensor tensor_chunks and tensor_lanes, behind a ProcessBatchFromTensors sample_chunks, behind a ProcessBatchLut3d lut3d_chunks, lut3d_lanes and lut3d_table, behind a ProcessBatchDeband deband_chunks, deband_lanes and deband_taps, behind a ProcessBatchSharpen sharpen_chunks and sharpen_lanes."""
         buf = C.create_string_buffer(512)
         self._check(self._L.mpcvr_get_last_batch_info(self._ctx, buf, 512))
         d = dict(kv.split("=", 1) for kv in buf.value.decode().split(";"))
@@ -1418,6 +1542,8 @@ class VideoProcessor:
             out.update(lut3d_chunks=int(d["lut3d_chunks"]), lut3d_lanes=[int(x) for x in d["lut3d_lanes"].split(",") if x], lut3d_table=d.get("lut3d_table", ""))
         if "deband_chunks" in d:     # (only behind a ProcessBatchDeband: the lane of each chunk, and where the pass read its taps from)
             out.update(deband_chunks=int(d["deband_chunks"]), deband_lanes=[int(x) for x in d["deband_lanes"].split(",") if x], deband_taps=d.get("deband_taps", ""))
+        if "sharpen_chunks" in d:    # (only behind a ProcessBatchSharpen: the lane of each chunk)
+            out.update(sharpen_chunks=int(d["sharpen_chunks"]), sharpen_lanes=[int(x) for x in d["sharpen_lanes"].split(",") if x])
         return out
 
     def GetUp2xForm(self):

@@ -56,6 +56,7 @@ SOURCES = [
     ("vp_deint.hip", []),
     ("vp_lut3d.hip", []),
     ("vp_deband.hip", []),
+    ("vp_sharpen.hip", []),
     ("vp_probe.hip", []),
 ]
 

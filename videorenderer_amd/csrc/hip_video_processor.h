@@ -18,6 +18,7 @@
 #include "vp_deint.h"
 #include "vp_lut3d.h"
 #include "vp_deband.h"
+#include "vp_sharpen.h"
 #include "vp_launch.h"
 #include "vp_params.h"
 #include "vp_plan.h"
@@ -86,6 +87,11 @@ HRESULT Lut3dSurface(const void *src, int srcPitch, int srcFmt, int w, int h, co
 HRESULT DebandSurface(const void *src, int srcPitch, int srcFmt, int w, int h, const mpcvr_deband_params *params, uint32_t seed, void *dst, int dstPitch,
                       int dstFmt, hipStream_t stream, bool checkOnly, const char **why = nullptr);
 
+// EXTENSION (mpcvr_sharpen_pass, include/mpcvr.h): checks every argument, then — unless checkOnly — launches k_sharpen on `stream`.
+// MPCVR_E_POINTER / MPCVR_E_INVALIDARG with nothing launched or written.  checkOnly takes src = nullptr as DebandSurface does
+HRESULT SharpenSurface(const void *src, int srcPitch, int srcFmt, int w, int h, const mpcvr_sharpen_params *params, uint32_t seed, void *dst, int dstPitch,
+                       int dstFmt, hipStream_t stream, bool checkOnly, const char **why = nullptr);
+
 class CHipVideoProcessor {
 public:
     CHipVideoProcessor();
@@ -148,6 +154,10 @@ public:
     // the caller's targets; frame i of a batch takes seed + i; the batch shares ProcessBatchYuv's surfaces, budget and chunk loop
     HRESULT RenderDeband(int field, const mpcvr_deband_params *params, uint32_t seed, void *dst, int dstPitch, int dstFmt);
     HRESULT ProcessBatchDeband(int n, const void *const *srcs, const mpcvr_deband_params *params, uint32_t seed, void *const *dsts, int dstPitch, int dstFmt);
+    // EXTENSION (mpcvr_render_sharpen / mpcvr_process_batch_sharpen): Render / the batch, then k_sharpen (vp_sharpen.h) behind it in stream order
+    // into the caller's targets; frame i of a batch takes seed + i; the batch shares ProcessBatchYuv's surfaces, budget and chunk loop
+    HRESULT RenderSharpen(int field, const mpcvr_sharpen_params *params, uint32_t seed, void *dst, int dstPitch, int dstFmt);
+    HRESULT ProcessBatchSharpen(int n, const void *const *srcs, const mpcvr_sharpen_params *params, uint32_t seed, void *const *dsts, int dstPitch, int dstFmt);
     HRESULT SetBatchYuvBudget(size_t bytes) { m_yuvBudget = bytes; return MPCVR_S_OK; }
     std::string GetLastBatchInfo() const;
     HRESULT ProcessBatchDovi(int n, const void *const *srcs, void *const *dsts, int rtPitch, const mpcvr_dovi_metadata *rpus);
@@ -501,7 +511,7 @@ private:
     };
     YuvSurface m_yuvSurf[FrameLanes::kFrameLanes];
     size_t m_yuvBudget = 0;            // SetBatchYuvBudget; 0: kBatchYuvDefaultBudget
-    std::string m_yuvLastInfo;         // ";yuv_chunks=..;yuv_lanes=.." (";tensor_chunks=..;tensor_lanes=..", ";lut3d_chunks=..;lut3d_lanes=..;lut3d_table=..", ";deband_chunks=..;deband_lanes=..;deband_taps=..") of the last batch call, if it was a ProcessBatchYuv (ProcessBatchTensor, ProcessBatchLut3d, ProcessBatchDeband)
+    std::string m_yuvLastInfo;         // ";yuv_chunks=..;yuv_lanes=.." (";tensor_chunks=..;tensor_lanes=..", ";lut3d_chunks=..;lut3d_lanes=..;lut3d_table=..", ";deband_chunks=..;deband_lanes=..;deband_taps=..", ";sharpen_chunks=..;sharpen_lanes=..") of the last batch call, if it was a ProcessBatchYuv (ProcessBatchTensor, ProcessBatchLut3d, ProcessBatchDeband, ProcessBatchSharpen)
     DevBuffer m_sampleSurf;            // ProcessBatchFromTensors / ProcessBatchDeint: the samples of one chunk side by side (PlanBatchSamples), written and read in stream order on the context stream
     // the chunk loop of ProcessBatchYuv / ProcessBatchTensor: surfaces, lanes and order; writesOf(at, m): what the chunk writes for the caller, pass(run, at): its pass
     template <class WritesOf, class Pass>

@@ -955,4 +955,108 @@ HRESULT CHipVideoProcessor::ProcessBatchDeband(int n, const void *const *srcs, c
     return hr;
 }
 
+// ------------------------------------------------------------------------------------------------
+// EXTENSION — sharpening of rendered frames (include/mpcvr.h: mpcvr_sharpen_pass, mpcvr_render_sharpen, mpcvr_process_batch_sharpen;
+// kernel: vp_sharpen.hip).  No reference line: the reference has no sharpener.
+// ------------------------------------------------------------------------------------------------
+static SharpenArgs SharpenArgsOf(const mpcvr_sharpen_params &p) { return SharpenArgs{p.radius, p.amount, p.threshold, p.overshoot, p.mode, p.dither}; }
+
+// What a k_sharpen launch is given, but for its surfaces and seed(s), as DebandLaunchParams
+static SharpenParams SharpenLaunchParams(int w, int h, int srcPitch, int dstPitch, const mpcvr_sharpen_params &params)
+{
+    SharpenParams p{};
+    p.src_pitch = srcPitch; p.dst_pitch = dstPitch; p.w = w; p.h = h;
+    p.a = SharpenArgsOf(params);
+    p.src16 = (srcPitch & 15) == 0;
+    p.dst16 = (dstPitch & 15) == 0;
+    return p;
+}
+
+HRESULT SharpenSurface(const void *src, int srcPitch, int srcFmt, int w, int h, const mpcvr_sharpen_params *params, uint32_t seed, void *dst, int dstPitch,
+                       int dstFmt, hipStream_t stream, bool checkOnly, const char **why)
+{
+    const char *dummy;
+    if (!why) why = &dummy;
+    if ((!src && !checkOnly) || !params || !dst) { *why = "null surface, parameters or destination"; return MPCVR_E_POINTER; }      // (checkOnly: a source still to be allocated)
+    if ((srcFmt != MPCVR_OUT_BGRA8 && srcFmt != MPCVR_OUT_RGB10A2) || (dstFmt != MPCVR_OUT_BGRA8 && dstFmt != MPCVR_OUT_RGB10A2)) {
+        *why = "source and destination BGRA8 or RGB10A2"; return MPCVR_E_INVALIDARG;
+    }
+    if (w < 1 || h < 1 || w > 32768 || h > 32768) { *why = "width and height must be 1 .. 32768"; return MPCVR_E_INVALIDARG; }
+    if (!SharpenArgsValid(SharpenArgsOf(*params), srcFmt == MPCVR_OUT_RGB10A2)) { *why = "radius 1 .. 3, amount 0 .. 256, threshold 0 .. 4 maxin, overshoot 0 .. maxin, mode 0 / 1, dither 0 / 1"; return MPCVR_E_INVALIDARG; }
+    if (srcPitch < 4 * w || dstPitch < 4 * w) { *why = "pitch smaller than a row"; return MPCVR_E_INVALIDARG; }
+    if (((uintptr_t)src | (uintptr_t)srcPitch | (uintptr_t)dst | (uintptr_t)dstPitch) & 3) { *why = "surfaces and pitches must be multiples of 4"; return MPCVR_E_INVALIDARG; }
+    const RtSpan s = RowsSpan(src, (size_t)srcPitch, h, (size_t)4 * w), d = RowsSpan(dst, (size_t)dstPitch, h, (size_t)4 * w);
+    // the pass reads neighbours: no overlap at all, in place included
+    if (src && d.Overlaps(s)) { *why = "the destination overlaps the source"; return MPCVR_E_INVALIDARG; }
+    if (checkOnly) return MPCVR_S_OK;
+    SharpenParams p = SharpenLaunchParams(w, h, srcPitch, dstPitch, *params);
+    p.src = (const uint8_t *)src; p.dst = (uint8_t *)dst; p.seed = seed;
+    p.src16 &= (s.lo & 15) == 0;
+    p.dst16 &= (d.lo & 15) == 0;
+    if (LaunchSharpen(p, srcFmt == MPCVR_OUT_RGB10A2, dstFmt == MPCVR_OUT_RGB10A2, stream) != hipSuccess) { *why = "k_sharpen launch failed"; return MPCVR_E_FAIL; }
+    return MPCVR_S_OK;
+}
+
+// Render, then the pass from the back buffer over the whole window into the caller's target, ordered as RenderDeband
+HRESULT CHipVideoProcessor::RenderSharpen(int /*field*/, const mpcvr_sharpen_params *params, uint32_t seed, void *dst, int dstPitch, int dstFmt)
+{
+    if (!m_bInit || !m_srcParams) return Fail(MPCVR_E_NOT_VALID_STATE, "InitMediaType has not been called");
+    (void)hipSetDevice(m_device);
+    const int w = m_windowRect.Width(), h = m_windowRect.Height();
+    // everything about the parameters and the target is answered before anything is drawn (a back buffer Render has yet to allocate cannot overlap it)
+    const bool have = m_BackBuffer.ptr && m_BackBuffer.size >= (size_t)w * 4 * h;
+    HRESULT hr;
+    const char *why = "";
+    if ((hr = SharpenSurface(have ? m_BackBuffer.ptr : nullptr, w * 4, m_cfg.output_format, w, h, params, seed, dst, dstPitch, dstFmt, nullptr, true, &why))) return Fail(hr, why);
+    if (!m_curSample) return MPCVR_S_FALSE;          // nothing to draw, as Render
+    if ((hr = RenderBackBuffer(true)) != MPCVR_S_OK) return hr;
+    hr = SharpenSurface(m_BackBuffer.ptr, w * 4, m_cfg.output_format, w, h, params, seed, dst, dstPitch, dstFmt, m_stream, false, &why);
+    m_launches++;
+    m_lanes.NoteStreamWork();
+    return hr ? Fail(hr, why) : MPCVR_S_OK;
+}
+
+// A batch through the pass (include/mpcvr.h: mpcvr_process_batch_sharpen): ProcessBatchDeband with k_sharpen as the chunk's pass.
+// Everything about the arguments is answered first; the chunks, their surfaces, lanes and order are RunSurfaceChunks'.
+HRESULT CHipVideoProcessor::ProcessBatchSharpen(int n, const void *const *srcs, const mpcvr_sharpen_params *params, uint32_t seed, void *const *dsts, int dstPitch, int dstFmt)
+{
+    const BatchRecord record(*this, n > 0 ? n : 0);
+    if (!m_bInit || !m_srcParams) return Fail(MPCVR_E_NOT_VALID_STATE, "InitMediaType has not been called");
+    if (n <= 0) return Fail(MPCVR_E_INVALIDARG, "empty batch");
+    if (!srcs || !dsts || !params) return Fail(MPCVR_E_POINTER, "null array of frames or targets, or null parameters");
+    for (int i = 0; i < n; i++)
+        if (!srcs[i] || !dsts[i]) return Fail(MPCVR_E_POINTER, "null frame or target in batch");
+    const int w = m_windowRect.Width(), h = m_windowRect.Height();
+    BatchYuvLayout lay;
+    if (!PlanBatchTensor(w, h, n, m_yuvBudget, &lay)) return Fail(MPCVR_E_INVALIDARG, "the pass needs a window width and height of 1 .. 32768");
+    // what the pass refuses, per frame (the surface is still to be allocated: it cannot overlap a target) ...
+    const char *why = "";
+    for (int i = 0; i < n; i++)
+        if (HRESULT bad = SharpenSurface(nullptr, lay.surfacePitch, m_cfg.output_format, w, h, params, seed, dsts[i], dstPitch, dstFmt, nullptr, true, &why)) return Fail(bad, why);
+    // ... and the targets against each other
+    std::vector<RtSpan> targets((size_t)n);
+    for (int i = 0; i < n; i++) targets[i] = RowsSpan(dsts[i], (size_t)dstPitch, h, (size_t)4 * w);
+    if (AnyTwoSpansOverlap(targets)) return Fail(MPCVR_E_INVALIDARG, "two targets of the batch overlap");
+
+    (void)hipSetDevice(m_device);
+    if (HRESULT bad = m_planDirty ? UpdatePlan() : MPCVR_S_OK) return bad;
+    const SharpenParams lp = SharpenLaunchParams(w, h, lay.surfacePitch, dstPitch, *params);      // (src16 holds for every chunk: every frame of a surface starts on 256 bytes)
+    const bool in10 = m_cfg.output_format == MPCVR_OUT_RGB10A2, out10 = dstFmt == MPCVR_OUT_RGB10A2;
+    return RunSurfaceChunks(n, srcs, lay, "sharpen",
+        [&](int at, int m) { return std::vector<RtSpan>(targets.begin() + (size_t)at, targets.begin() + (size_t)(at + m)); },
+        [&](BatchRun &run, int at) {
+            // the targets' and seeds' table through the frame tables' ring; the lease ends behind the pass
+            SlotLease table;
+            SharpenParams p = lp;
+            if (HRESULT bad = m_tableRing.SendRows<SharpenFrame>(run.n, run.on.stream, "sharpen frame table", &table, [&](SharpenFrame *fr) {
+                    for (int i = 0; i < run.n; i++) {
+                        fr[i] = SharpenFrame{(const uint8_t *)run.dsts[i], (uint8_t *)dsts[at + i], seed + (uint32_t)(at + i), 0u};
+                        p.dst16 &= ((uintptr_t)dsts[at + i] & 15) == 0;      // the 16-byte stores only if every target of the launch allows them
+                    }
+                })) return bad;
+            p.frames = (const SharpenFrame *)table.dev;
+            return CheckHip(LaunchSharpen(p, in10, out10, run.on.stream, run.n), "k_sharpen");
+        });
+}
+
 }  // namespace mpcvr

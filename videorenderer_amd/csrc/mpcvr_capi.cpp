@@ -460,6 +460,69 @@ int32_t mpcvr_process_batch_deband(mpcvr_ctx *ctx, int32_t n, const void *const 
     return ctx->vp.ProcessBatchDeband(n, srcs, params, seed, dsts, dst_pitch, dst_fmt);
 }
 
+// EXTENSION: sharpening of rendered frames (include/mpcvr.h; k_sharpen vp_sharpen.hip, the arithmetic vp_sharpen_core.h, SharpenSurface and
+// CHipVideoProcessor::RenderSharpen / ProcessBatchSharpen hip_video_processor_ext.cpp, PlanSharpenDefaults / PlanSharpenHost vp_plan.cpp)
+static mpcvr::SharpenArgs SharpenArgsOf(const mpcvr_sharpen_params &p)
+{
+    return mpcvr::SharpenArgs{p.radius, p.amount, p.threshold, p.overshoot, p.mode, p.dither};
+}
+
+int32_t mpcvr_sharpen_params_default(int32_t src_fmt, mpcvr_sharpen_params *params)
+{
+    if (!params) return MPCVR_E_POINTER;
+    mpcvr::SharpenArgs a;
+    if (!mpcvr::PlanSharpenDefaults(src_fmt, &a)) return MPCVR_E_INVALIDARG;
+    *params = mpcvr_sharpen_params{a.radius, a.amount, a.threshold, a.overshoot, a.mode, a.dither};
+    return MPCVR_S_OK;
+}
+
+int32_t mpcvr_sharpen_host(const void *src_host, int64_t src_pitch, int32_t src_fmt, int32_t w, int32_t h, const mpcvr_sharpen_params *params,
+                           uint32_t seed, void *dst_host, int64_t dst_pitch, int32_t dst_fmt)
+{
+    if (!src_host || !params || !dst_host) return MPCVR_E_POINTER;
+    return mpcvr::PlanSharpenHost(src_host, src_pitch, src_fmt, w, h, SharpenArgsOf(*params), seed, dst_host, dst_pitch, dst_fmt) ? MPCVR_S_OK : MPCVR_E_INVALIDARG;
+}
+
+int32_t mpcvr_plan_sharpen(int32_t src_fmt, const mpcvr_sharpen_params *params, int32_t w, int32_t h, int32_t *halo, int32_t *lds_bytes)
+{
+    if (!params) return MPCVR_E_POINTER;
+    if ((src_fmt != MPCVR_OUT_BGRA8 && src_fmt != MPCVR_OUT_RGB10A2) || w < 1 || h < 1 || w > 32768 || h > 32768 ||
+        !mpcvr::SharpenArgsValid(SharpenArgsOf(*params), src_fmt == MPCVR_OUT_RGB10A2))
+        return MPCVR_E_INVALIDARG;
+    if (halo) *halo = params->radius;
+    if (lds_bytes) *lds_bytes = mpcvr::SharpenLdsBytes(params->radius, params->mode);
+    return MPCVR_S_OK;
+}
+
+int32_t mpcvr_sharpen_pass(const void *src, int32_t src_pitch, int32_t src_fmt, int32_t w, int32_t h, const mpcvr_sharpen_params *params,
+                           uint32_t seed, void *dst, int32_t dst_pitch, int32_t dst_fmt, void *stream)
+{
+    return mpcvr::SharpenSurface(src, src_pitch, src_fmt, w, h, params, seed, dst, dst_pitch, dst_fmt, (hipStream_t)stream, false);
+}
+
+int32_t mpcvr_render_sharpen(mpcvr_ctx *ctx, int32_t field, const mpcvr_sharpen_params *params, uint32_t seed, void *dst, int32_t dst_pitch, int32_t dst_fmt)
+{
+    CTX_OR_FAIL();
+    if (!params || !dst) return MPCVR_E_POINTER;
+    return ctx->vp.RenderSharpen(field, params, seed, dst, dst_pitch, dst_fmt);
+}
+
+int32_t mpcvr_plan_batch_sharpen(int32_t window_w, int32_t window_h, int32_t n, size_t budget_bytes,
+                                 int32_t *surface_pitch, size_t *frame_stride, int32_t *frames_per_chunk, int32_t *chunks)
+{
+    mpcvr::BatchYuvLayout lay;
+    const bool planned = mpcvr::PlanBatchTensor(window_w, window_h, n, budget_bytes, &lay);      // (the same surface of 32-bit texels)
+    if (planned && surface_pitch) *surface_pitch = lay.surfacePitch;
+    return ChunkLayoutOut(planned, lay, frame_stride, frames_per_chunk, chunks);
+}
+
+int32_t mpcvr_process_batch_sharpen(mpcvr_ctx *ctx, int32_t n, const void *const *srcs, const mpcvr_sharpen_params *params, uint32_t seed,
+                                    void *const *dsts, int32_t dst_pitch, int32_t dst_fmt)
+{
+    CTX_OR_FAIL();
+    return ctx->vp.ProcessBatchSharpen(n, srcs, params, seed, dsts, dst_pitch, dst_fmt);
+}
+
 int32_t mpcvr_get_param_blob(mpcvr_ctx *ctx, void *buf, size_t *size) { CTX_OR_FAIL(); return ctx->vp.GetParamBlob(buf, size); }
 int32_t mpcvr_get_fused_tables(mpcvr_ctx *ctx, void *buf, size_t *size) { CTX_OR_FAIL(); return ctx->vp.GetFusedTables(buf, size); }
 int32_t mpcvr_set_param_blob(mpcvr_ctx *ctx, const void *buf, size_t size) { CTX_OR_FAIL(); return ctx->vp.SetParamBlob(buf, size); }

@@ -13,6 +13,7 @@
 #include "vp_tensor_in.h"
 #include "vp_lut3d.h"
 #include "vp_deband.h"
+#include "vp_sharpen.h"
 #include "vp_deint.h"
 #include "vp_crmath.h"      // the shaders' sin / cos as defined functions (the weights the resize shaders compute per pixel are computed here, once)
 
@@ -389,6 +390,32 @@ bool PlanDebandHost(const void *src, int64_t src_pitch, int src_fmt, int w, int 
     const uintptr_t d0 = (uintptr_t)dst, d1 = d0 + (size_t)(h - 1) * (size_t)dst_pitch + (size_t)4 * w;
     if (s0 < d1 && d0 < s1) return false;
     DebandSurfaceHost((const uint8_t *)src, src_pitch, src_fmt == MPCVR_OUT_RGB10A2, w, h, a, seed, (uint8_t *)dst, dst_pitch, dst_fmt == MPCVR_OUT_RGB10A2);
+    return true;
+}
+
+// ------------------------------------------------------------------------------------------------
+// EXTENSION — the sharpen pass on the host (include/mpcvr.h: mpcvr_sharpen_params_default, mpcvr_sharpen_host): the defaults, and a whole
+// surface through the functions of vp_sharpen_core.h the kernel compiles.  No reference line: the reference has no sharpener.
+// ------------------------------------------------------------------------------------------------
+bool PlanSharpenDefaults(int src_fmt, SharpenArgs *a)
+{
+    if (src_fmt != MPCVR_OUT_BGRA8 && src_fmt != MPCVR_OUT_RGB10A2) return false;
+    const bool in10 = src_fmt == MPCVR_OUT_RGB10A2;
+    *a = SharpenArgs{2, 32, in10 ? 16 : 4, in10 ? 8 : 2, SHARPEN_LUMA, 1};      // (threshold one 8-bit code, overshoot two, in the source's codes)
+    return true;
+}
+
+bool PlanSharpenHost(const void *src, int64_t src_pitch, int src_fmt, int w, int h, const SharpenArgs &a, uint32_t seed, void *dst, int64_t dst_pitch, int dst_fmt)
+{
+    if ((src_fmt != MPCVR_OUT_BGRA8 && src_fmt != MPCVR_OUT_RGB10A2) || (dst_fmt != MPCVR_OUT_BGRA8 && dst_fmt != MPCVR_OUT_RGB10A2)) return false;
+    if (w < 1 || h < 1 || w > 32768 || h > 32768 || !SharpenArgsValid(a, src_fmt == MPCVR_OUT_RGB10A2)) return false;
+    if (src_pitch < (int64_t)4 * w || dst_pitch < (int64_t)4 * w) return false;
+    if (((uintptr_t)src | (uintptr_t)src_pitch | (uintptr_t)dst | (uintptr_t)dst_pitch) & 3) return false;
+    // a surface: the bytes from its first pixel to the last pixel of its last row
+    const uintptr_t s0 = (uintptr_t)src, s1 = s0 + (size_t)(h - 1) * (size_t)src_pitch + (size_t)4 * w;
+    const uintptr_t d0 = (uintptr_t)dst, d1 = d0 + (size_t)(h - 1) * (size_t)dst_pitch + (size_t)4 * w;
+    if (s0 < d1 && d0 < s1) return false;
+    SharpenSurfaceHost((const uint8_t *)src, src_pitch, src_fmt == MPCVR_OUT_RGB10A2, w, h, a, seed, (uint8_t *)dst, dst_pitch, dst_fmt == MPCVR_OUT_RGB10A2);
     return true;
 }
 
