@@ -10,15 +10,16 @@ OUT=gpurun_out/$TAG; rm -rf $OUT; mkdir -p $OUT
 # ramping); the counter passes below only need a few dispatches
 FULL="python bench.py --no-cpu-baseline --no-host-path $*"
 BENCH="python bench.py --steps 12 --warmup 4 --settle 0 --no-cpu-baseline --no-host-path $*"
-$FULL > $OUT/bench_plain.json 2> $OUT/bench_plain.err
-timeout -k 5 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o kt -- $FULL > $OUT/bench_under_kernel_trace.json 2> $OUT/kt.err
+# (every step under its own time limit; a step that failed or ran out of time ends the script: nothing more is started on the GPU behind it)
+timeout -k 10 300 $FULL > $OUT/bench_plain.json 2> $OUT/bench_plain.err || { rc=$?; tail -3 $OUT/bench_plain.err; exit $rc; }
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o kt -- $FULL > $OUT/bench_under_kernel_trace.json 2> $OUT/kt.err || { rc=$?; tail -3 $OUT/kt.err; exit $rc; }
 i=0
 for set in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_WAIT_INST_ANY SQ_WAIT_ANY" \
            "SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAIT_INST_LDS" \
            "GRBM_GUI_ACTIVE GRBM_COUNT SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VALU_TRANS SQ_INST_CYCLES_VMEM SQ_ACTIVE_INST_MISC SQ_ACTIVE_INST_SCA" \
            "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum"; do
   i=$((i+1))
-  timeout -k 5 300 rocprofv3 --pmc $set --kernel-trace --output-format csv -d $OUT/pmc$i -o p -- $BENCH > $OUT/pmc$i.log 2>&1 || tail -3 $OUT/pmc$i.log
+  timeout -k 10 300 rocprofv3 --pmc $set --kernel-trace --output-format csv -d $OUT/pmc$i -o p -- $BENCH > $OUT/pmc$i.log 2>&1 || { rc=$?; tail -3 $OUT/pmc$i.log; exit $rc; }
 done
 python - "$OUT" <<'PY'
 import csv, glob, sys, collections, json, os

@@ -142,12 +142,18 @@ __device__ __forceinline__ void fused_up2x_body(const FusedArgs &P, const FusedF
                         {f2{P.wo[0], P.wo[1]}, f2{P.wo[2], P.wo[3]}, f2{P.wo[4], P.wo[5]}}};
     // colour matrix and gamut matrix, two coefficients per SGPR pair
     const f2 MM[5] = {f2{P.m[0], P.m[1]}, f2{P.m[2], P.m[3]}, f2{P.m[4], P.m[5]}, f2{P.m[6], P.m[7]}, f2{P.m[8], 0.0f}};
+    // the twin's odd luma column: its chroma arrives as the SUM of two texels, the halving sits in these (exact: FusedUp2xBpTakes)
+    const f2 HH[2] = {f2{0.5f * P.m[2], 0.5f * P.m[4]}, f2{0.5f * P.m[5], 0.5f * P.m[7]}};
     const f2 GG[5] = {f2{P.gamut[0], P.gamut[1]}, f2{P.gamut[2], P.gamut[3]}, f2{P.gamut[4], P.gamut[5]}, f2{P.gamut[6], P.gamut[7]}, f2{P.gamut[8], 0.0f}};
     constexpr bool FASTEPI = EPI == EPI_DITHER8;     // integer final pass; EPI_DIRECT8 shares its alignment preconditions
     const f2 maxv2 = splat((FASTEPI || P.final_pass) ? P.maxv : P.quant);
     const f2 cmax2 = splat(P.maxv), cinv2 = splat(P.inv_maxv);
     f2 big2 = splat(8388608.0f);                     // 2^23, pinned in VGPRs (see unorm_round2)
     asm volatile("" : "+v"(big2));
+    // the twin reads the convert output back inside an FMA: (2^23 + q) * inv - 2^23 * inv rounds q * inv once, as float(q) * inv does,
+    // and the addend is exact (a power of two times a float) — pinned in VGPRs like big2
+    f2 nbc2 = splat(-8388608.0f * P.inv_maxv);
+    if constexpr (BP) asm volatile("" : "+v"(nbc2));
     f2 CC[3] = {splat(P.c[0]), splat(P.c[1]), splat(P.c[2])};     // matrix offsets: FMA addends must be VGPRs anyway
     asm volatile("" : "+v"(CC[0]), "+v"(CC[1]), "+v"(CC[2]));
 
@@ -193,7 +199,7 @@ __device__ __forceinline__ void fused_up2x_body(const FusedArgs &P, const FusedF
         f2 rc[2][3];
         if constexpr (BP) {
             raw_unseen_arrived<NL>(tw);
-            convert_block_bp<TAIL, SRC, decltype(first)::value>(P, MM, GG, CC, pendb[b], keep, P.rect_t + clampi(ar, 0, H - 1), P.rect_t + clampi(ar + 1, 0, H - 1), T, rc);
+            convert_block_bp<TAIL, SRC, decltype(first)::value>(P, MM, HH, GG, CC, pendb[b], keep, P.rect_t + clampi(ar, 0, H - 1), P.rect_t + clampi(ar + 1, 0, H - 1), T, rc);
         } else if constexpr (UNSEEN) {
             raw_unseen_arrived<NL>(tw);
             raw_unseen_finish<SRC>(P, pend2[b], raw2[b]);
@@ -206,6 +212,10 @@ __device__ __forceinline__ void fused_up2x_body(const FusedArgs &P, const FusedF
             // (the exact form hands over the codes themselves)
             f2 qe = (XC == XC_ALWAYS ? rc[0][c] : unorm_round2(rc[0][c], cmax2, big2)) * cinv2;             // even column, rows (a, a+1)
             f2 qo = (XC == XC_ALWAYS ? rc[1][c] : unorm_round2(rc[1][c], cmax2, big2)) * cinv2;             // odd column
+            if constexpr (BP) {    // the same bits in two FMAs: 2^23 stays on, the read-back takes it off (nbc2)
+                qe = pk_fma(pk_fma(rc[0][c], cmax2, big2), cinv2, nbc2);
+                qo = pk_fma(pk_fma(rc[1][c], cmax2, big2), cinv2, nbc2);
+            }
             // A[ch][col][row]: columns 2l, 2l+1 as (row a, row a+1) pairs = one 16-byte store
             *(f4 *)(A + (c * AW + 2 * lane) * 2) = f4{qe.x, qe.y, qo.x, qo.y};
             if (edge_wave) {       // clamp-to-edge of the convert texture: patch the column that hangs over (rare wave;

@@ -9,8 +9,10 @@
 // they are row n), takes the vertically interpolated pairs of column c0 + 1 from lane j + 1 with a wave-wide shift by one lane (DPP:
 // no LDS round trip) and drops the two matrix FMAs whose coefficient is a structural zero.  Everything else of the loop — stage X,
 // stage Y, the epilogues, the software pipeline, the counted wait — is fused_up2x_body's own text (vp_fused_up2x.h), which reads this header's pieces where its BP argument is set.
-// Same values, same operations on them, in the same order as the generic stage: the two kernels agree bit for bit
-// (tests/test_up2x_bp_gpu.py), and LaunchFusedUp2xNT takes the twin only where FusedUp2xBpTakes says the identities above hold for
+// Same values, same operations on them, in the same order as the generic stage — but for two rescalings that are exact and sit inside
+// a neighbouring FMA here (the odd column's halved chroma: HH below; the convert output's read-back: nbc2, vp_fused_up2x.h; both
+// identities are checked in tests/test_up2x_bp_folds.py): the two kernels agree bit for bit
+// (tests/test_up2x_bp_gpu.py, tests/test_up2x_bp_folds_gpu.py), and LaunchFusedUp2xNT takes the twin only where FusedUp2xBpTakes says the identities above hold for
 // the whole launch — anything else runs the generic kernel, so a disagreement costs the fast path, never a pixel.
 // New device code lives here and not in vp_fused_dev.h, which every fused kernel's traffic record is tied to (profiles/hbm_traffic.json).
 #pragma once
@@ -111,16 +113,20 @@ __device__ __forceinline__ f2 from_next_lane(f2 v) { return f2{from_next_lane(v.
 // convert_block_yuv (vp_fused_dev.h) for the plans of bp_planned(): no Dolby Vision, the table tails or none — its text with
 // the matrix FMAs of m[1] (R from U) and m[8] (B from V) left out: 0 * x added to a sum (FusedUp2xBpTakes checks both are 0).
 template <int TAIL>
-__device__ __forceinline__ void convert_block_yuv_bp(const FusedArgs &P, const f2 (&MM)[5], const f2 (&GG)[5], const f2 (&CC)[3], const f2 (&Ycol)[2], const f2 (&Ucol)[2],
+__device__ __forceinline__ void convert_block_yuv_bp(const FusedArgs &P, const f2 (&MM)[5], const f2 (&HH)[2], const f2 (&GG)[5], const f2 (&CC)[3], const f2 (&Ycol)[2], const f2 (&Ucol)[2],
                                                      const f2 (&Vcol)[2], const f2 *T, f2 out[2][3])
 {
     static_assert(TAIL == TAILK_PQ_LUT || TAIL == TAILK_HLG || TAIL == TAILK_NONE, "tails the twin is planned for");
     f2 rgbc[2][3];
 #pragma unroll
     for (int rr = 0; rr < 2; rr++) {              // rr = luma column of the block
-        rgbc[rr][0] = fma_k<true>(MM, 0, Ycol[rr], fma_k<false>(MM, 2, Vcol[rr], CC[0]));
-        rgbc[rr][1] = fma_k<true>(MM, 3, Ycol[rr], fma_k<false>(MM, 4, Ucol[rr], fma_k<false>(MM, 5, Vcol[rr], CC[1])));
-        rgbc[rr][2] = fma_k<true>(MM, 6, Ycol[rr], fma_k<false>(MM, 7, Ucol[rr], CC[2]));
+        // the odd column's Ucol / Vcol are twice its chroma (convert_block_bp) and meet the halved coefficients HH = {m2, m4, m5, m7} / 2:
+        // fma(m / 2, 2x, acc) is fma(m, x, acc) bit for bit, halving and doubling being exact
+        const f2 *KK = rr ? HH : MM;
+        const int k2 = rr ? 0 : 2, k4 = rr ? 1 : 4, k5 = rr ? 2 : 5, k7 = rr ? 3 : 7;
+        rgbc[rr][0] = fma_k<true>(MM, 0, Ycol[rr], fma_k<false>(KK, k2, Vcol[rr], CC[0]));
+        rgbc[rr][1] = fma_k<true>(MM, 3, Ycol[rr], fma_k<false>(KK, k4, Ucol[rr], fma_k<false>(KK, k5, Vcol[rr], CC[1])));
+        rgbc[rr][2] = fma_k<true>(MM, 6, Ycol[rr], fma_k<false>(KK, k7, Ucol[rr], CC[2]));
     }
     if constexpr (!tail_has_table(TAIL)) {
 #pragma unroll
@@ -194,7 +200,7 @@ __device__ __forceinline__ void convert_block_yuv_bp(const FusedArgs &P, const f
 // convert_block (vp_fused_dev.h) for the twin: the block's luma and ONE new chroma texel (column c0, row n + 1) from `u`, row n from
 // `keep` (FIRST: from u.v[3], a segment's first convert), column c0 + 1 from the next lane.  sy0 / sy1 as convert_block takes them.
 template <int TAIL, int SRC, bool FIRST>
-__device__ __forceinline__ void convert_block_bp(const FusedArgs &P, const f2 (&MM)[5], const f2 (&GG)[5], const f2 (&CC)[3], const RawUnseenBp &u, ChromaCarry &keep,
+__device__ __forceinline__ void convert_block_bp(const FusedArgs &P, const f2 (&MM)[5], const f2 (&HH)[2], const f2 (&GG)[5], const f2 (&CC)[3], const RawUnseenBp &u, ChromaCarry &keep,
                                                  int sy0, int sy1, const f2 *T, f2 out[2][3])
 {
     // vertical weights of chroma rows n (w0) and n+1 (w1) for (row 0, row 1): wave-uniform, one SGPR pair each
@@ -216,10 +222,11 @@ __device__ __forceinline__ void convert_block_bp(const FusedArgs &P, const f2 (&
         Ycol[0] = f2{(float)(u.v[0] & 0xffu), (float)(u.v[1] & 0xffu)};
         Ycol[1] = f2{(float)((u.v[0] >> 8) & 0xffu), (float)((u.v[1] >> 8) & 0xffu)};
     }
-    const f2 cwa = splat(P.cw_own), cwb = splat(P.cw_next);         // {0.5, 0.5}: FusedUp2xBpTakes
-    Ucol[1] = pk_fma(Un, cwb, Ucol[0] * cwa);
-    Vcol[1] = pk_fma(Vn, cwb, Vcol[0] * cwa);
-    convert_block_yuv_bp<TAIL>(P, MM, GG, CC, Ycol, Ucol, Vcol, T, out);
+    // the odd luma column's chroma is fma(Un, 0.5, Ucol[0] * 0.5) (cw_own == cw_next == 0.5: FusedUp2xBpTakes) = 0.5 * RNE(Un + Ucol[0]),
+    // scaling by a half being exact: the sum goes on as it is and the halving into the matrix coefficients it meets (HH)
+    Ucol[1] = Un + Ucol[0];
+    Vcol[1] = Vn + Vcol[0];
+    convert_block_yuv_bp<TAIL>(P, MM, HH, GG, CC, Ycol, Ucol, Vcol, T, out);
 }
 
 }  // namespace

@@ -31,6 +31,9 @@ bool FusedUp2xBpTakes(const FusedArgs &a, int srck, int epik, int tailk)
     if (a.sub422 || a.sub444 || a.packed422 || a.packed444 || a.gray || a.nearest || a.center_h || a.cw_own != 0.5f || a.cw_next != 0.5f) return false;
     // the matrix' structural zeros (every non-constant-luminance YCbCr matrix; a hue-rotated ProcAmp matrix has none)
     if (a.m[1] != 0.0f || a.m[8] != 0.0f) return false;
+    // the odd column's chroma coefficients are used halved (HH, fused_up2x_body): halving must be exact — it is unless m is subnormal-small
+    for (int i : {2, 4, 5, 7})
+        if (a.m[i] != 0.0f && (0.5f * a.m[i]) * 2.0f != a.m[i]) return false;
     // the lane identity: lane j + 1's texel c0 is lane j's c0 + 1.  Inside the rect that takes even W and rect_l (blocks start on even
     // columns); at the left edge the clamped lanes' odd columns are patched over (stage C's edge branch); at the right edge the lanes
     // clamped to block W - 2 all hold texel c0 = (rect_l + W - 2) / 2, which is their c0 + 1 only where the frame's chroma ends there
